@@ -2,16 +2,20 @@
 """bench.py - nuPGCM hot path on MI355X: timesteps/sec of the evolve! + invert! loop and the inversion SpMV's achieved
 bandwidth on a bowl3D mesh (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload bowl3D_h0.02]
+    python bench.py --gpus N --steps K --warmup W [--workload bowl3D_h0.02] [--dump-outputs DIR] [--full]
 
 One process per GPU (torch.distributed.run launches N of them; RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the env).
-A step = one timestep of /root/reference/src/model.jl:128-209 (advection assembly + CG evolution solve + GMRES inversion)
+A step = one timestep of the reference's src/model.jl:128-209 (advection assembly + CG evolution solve + GMRES inversion)
 with the parameters of examples/bowl_mixing.jl, state resident in HBM.  The timed region is bracketed by barrier +
 device sync on both sides and the maximum over ranks is reported; rank 0 prints ONE JSON line.
 
-Extra objects in the line:
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`, `config`).
+--dump-outputs DIR writes the state the last timed step left (u, p, b) as DIR/<name>.npy (see dump_outputs).
+--full adds everything else the line used to carry, each measured after the timed region:
   roofline     - the dominant kernel (the fused Arnoldi kernel: CSR SpMV of A_inversion + Gram-Schmidt dots), timed live
                  with HIP events on the library's stream in a profile pass right after the timed region
+  spmv_*       - the stand-alone SpMV kernels (node-block records, gather layout, plain CSR)
+  multigrid, extrapolated_guess, fp64_basis, dense_inverse - the same loop in other solver configurations
   cpu_baseline - the CPU oracle (a port of the reference recipe) timed on this host's cores on a bounded sample
 """
 import argparse
@@ -42,15 +46,40 @@ def parse():
     ap.add_argument("--extrapolate-guess", type=int, nargs="?", const=1, default=0,
                     help="start each inversion from 2 x_{n-1} - x_{n-2} instead of the reference's warm start x_{n-1} "
                          "(model.extrapolate_guess; NOT the reference's recipe: the run is labelled in `config`)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-multigrid", action="store_true", help="skip the extra multigrid-preconditioned run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the roofline profile pass, the stand-alone SpMV kernels, the other "
+                         "solver configurations and the CPU baseline (off: the line carries the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write u, p, b after the last timed step as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-multigrid", action="store_true",
+                    help="with --full: skip the extra multigrid / extrapolated-guess / fp64-basis / dense-inverse runs")
     ap.add_argument("--no-profile-pass", action="store_true",
-                    help="skip the HIP-event profile pass (use when the whole run is under rocprofv3)")
+                    help="with --full: skip the HIP-event profile pass (use when the whole run is under rocprofv3)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="CPU budget of the cpu_baseline sample")
     return ap.parse_args()
 
 
 PMC_FILE = "profiles/r05_pmc.json"
+DUMP_BYTES = 64_000_000      # --dump-outputs: at most this many bytes in all
+
+
+def dump_outputs(model, out_dir, rank):
+    """What the timed path leaves its caller after the last timed step: model.state's u, p and b (host copies in the native
+    DoF order) as out_dir/<name>.npy in float64.  Reading the state of a partitioned model is collective: every rank calls
+    this, rank 0 writes.  When the three together exceed DUMP_BYTES, each is cut to a fixed sample of its entries (sorted
+    indices drawn by np.random.default_rng(0), the same for every run of the same arguments)."""
+    arrays = {"u": model.state.u, "p": model.state.p, "b": model.state.b}
+    if rank != 0:
+        return
+    total = sum(8 * x.size for x in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in arrays.items():
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if total > DUMP_BYTES:
+            keep = int(x.size * DUMP_BYTES // total)
+            x = x[np.sort(np.random.default_rng(0).choice(x.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), x)
 
 
 def pmc_traffic(workload, kernel="k_gmres_arnoldi", stored=None):
@@ -256,6 +285,8 @@ def main():
     stats = model.stats[-a.steps:]
     gm_its = [s[1]["niter"] for s in stats]
     cg_its = [s[0]["niter"] for s in stats]
+    if a.dump_outputs:
+        dump_outputs(model, a.dump_outputs, rank)
 
     # ---- profile pass: HIP events around every Arnoldi (SpMV) kernel of one more timestep -------------------------
     A = model.inversion.solver.A
@@ -265,7 +296,7 @@ def main():
         nnz_glob = int(round(ctx.allreduce_sum([float(nnz)])[0]))
     ws = model.inversion.solver.workspace
     ms_total, launches = 0.0, 0
-    if not a.no_profile_pass and hasattr(ws, "set_profile"):
+    if a.full and not a.no_profile_pass and hasattr(ws, "set_profile"):
         ws.set_profile(True)
         npg.run(model, n_steps=1)
         ms_total, launches = ws.get_profile()
@@ -306,21 +337,23 @@ def main():
                             "in record form, fewer bytes than the 12 B per stored entry of a CSR SpMV - `csr_equivalent_GBps` "
                             "is the rate in those algorithmic bytes of SURVEY 8(d) and may exceed the HBM peak")
     # stand-alone SpMV kernel (same tiles, no Krylov epilogue) for reference
-    x = npg.DeviceVector.from_host(ctx, np.sin(np.arange(A.shape[1], dtype=float)))
-    y = npg.DeviceVector(ctx, N)
-    for _ in range(3):
-        A.mul(x, y)
-    reps = 20
-    ctx.timer_start()
-    for _ in range(reps):
-        A.mul(x, y)
-    spmv_ms = ctx.timer_stop() / reps
+    spmv_ms = None
+    if a.full:
+        x = npg.DeviceVector.from_host(ctx, np.sin(np.arange(A.shape[1], dtype=float)))
+        y = npg.DeviceVector(ctx, N)
+        for _ in range(3):
+            A.mul(x, y)
+        reps = 20
+        ctx.timer_start()
+        for _ in range(reps):
+            A.mul(x, y)
+        spmv_ms = ctx.timer_stop() / reps
 
     # the inversion SpMV AS THE SOLVER RUNS IT, stand-alone: the gather-layout product on the windowed tiles (npg_spmv_gather32 - the
     # tile code of the Arnoldi kernel without its Givens prologue and its epilogue's wt / w / basis-column traffic), priced in the
     # bytes of the windowed set as stored.  Wall clock over back-to-back launches (the entry point synchronises once at the end).
     spmv_g32 = None
-    if rank == 0 and world == 1 and getattr(A, "paired", False) and hasattr(A, "window_info"):
+    if a.full and rank == 0 and world == 1 and getattr(A, "paired", False) and hasattr(A, "window_info"):
         wi = A.window_info()
         if wi.get("tiles"):
             A.mul_gather32(x, y, windowed=True, reps=3)
@@ -336,7 +369,7 @@ def main():
     # the same product on a plain-CSR copy of the matrix (what the reference's cuSPARSE path streams): real bytes = algorithmic
     # bytes there, so this is the kernel's bandwidth figure without the node-block storage's byte savings
     spmv_plain = None
-    if getattr(A, "paired", False) and rank == 0 and world == 1:
+    if a.full and getattr(A, "paired", False) and rank == 0 and world == 1:
         Ap = npg.build_A_inversion(arch, model.fe_data, model.params, model.forcings.nu)
         for _ in range(3):
             Ap.mul(x, y)
@@ -381,21 +414,24 @@ def main():
                    "setup_seconds": round(t_setup, 1),
                    "parallelism": ("1 GPU" if world == 1 else
                                    f"mesh, matrices and state partitioned x{world} (node-aligned, one ghost-cell layer)")},
-        "roofline": roofline,
-        # stand-alone k_spmv (ordinary tiles, fp64 gathers): priced in the bytes its layout moves; the CSR-equivalent rate (the
-        # algorithmic bytes of SURVEY 8(d) over the same time) is labelled as such and may exceed the HBM peak
-        "spmv_standalone": {"avg_launch_us": spmv_ms * 1e3, "stored_bytes_per_launch": int(A.stored_spmv_bytes() + 8 * A.shape[1] + 8 * N),
-                            "GBps": (A.stored_spmv_bytes() + 8 * A.shape[1] + 8 * N) / (spmv_ms * 1e-3) / 1e9,
-                            "frac_of_8TBps": (A.stored_spmv_bytes() + 8 * A.shape[1] + 8 * N) / (spmv_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                            "csr_equivalent_GBps": alg_bytes / (spmv_ms * 1e-3) / 1e9,
-                            "note": "GBps = bytes of the stored layout (records) per launch time; csr_equivalent_GBps = what a plain-CSR "
-                                    "SpMV of the same matrix would have had to stream in that time (not a physical rate)"},
-        "spmv_gather32_standalone": spmv_g32,
-        "spmv_plain_csr": spmv_plain,
     }
+    if a.full:
+        out.update({
+            "roofline": roofline,
+            # stand-alone k_spmv (ordinary tiles, fp64 gathers): priced in the bytes its layout moves; the CSR-equivalent rate (the
+            # algorithmic bytes of SURVEY 8(d) over the same time) is labelled as such and may exceed the HBM peak
+            "spmv_standalone": {"avg_launch_us": spmv_ms * 1e3, "stored_bytes_per_launch": int(A.stored_spmv_bytes() + 8 * A.shape[1] + 8 * N),
+                                "GBps": (A.stored_spmv_bytes() + 8 * A.shape[1] + 8 * N) / (spmv_ms * 1e-3) / 1e9,
+                                "frac_of_8TBps": (A.stored_spmv_bytes() + 8 * A.shape[1] + 8 * N) / (spmv_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                "csr_equivalent_GBps": alg_bytes / (spmv_ms * 1e-3) / 1e9,
+                                "note": "GBps = bytes of the stored layout (records) per launch time; csr_equivalent_GBps = what a plain-CSR "
+                                        "SpMV of the same matrix would have had to stream in that time (not a physical rate)"},
+            "spmv_gather32_standalone": spmv_g32,
+            "spmv_plain_csr": spmv_plain,
+        })
     # ---- the same loop with the multigrid-preconditioned inversion (new work; the headline above stays the reference's
     # configuration): refined bowl meshes on one GPU
-    if (rank == 0 and world == 1 and not channel and a.preconditioner == "diagonal" and not a.no_multigrid
+    if (a.full and rank == 0 and world == 1 and not channel and a.preconditioner == "diagonal" and not a.no_multigrid
             and workloads.BOWL_MESHES[a.workload][1] >= 1):
         t_mg = time.time()
         mg = workloads.example_model(arch, a.workload, dt=a.dt, preconditioner="multigrid", fine_fe_data=model.fe_data)
@@ -447,7 +483,7 @@ def main():
     # ---- the reference's solver configuration with ONE change outside the solver: each inversion starts from the extrapolation
     # 2 x_{n-1} - x_{n-2} of the last two solutions instead of x_{n-1} (model.extrapolate_guess; the answer moves within the
     # solver tolerance only).  Same steps as the headline, on a fresh model.
-    if (rank == 0 and world == 1 and not channel and a.preconditioner == "diagonal" and not a.no_multigrid
+    if (a.full and rank == 0 and world == 1 and not channel and a.preconditioner == "diagonal" and not a.no_multigrid
             and not a.extrapolate_guess):
         t_x = time.time()
         ex = workloads.example_model(arch, mesh_model, dt=a.dt, fine_fe_data=model.fe_data)
@@ -472,7 +508,7 @@ def main():
         del ex
     # ---- the like-for-like precision: the headline loop with the Krylov basis and the SpMV input stored in fp64 throughout, as
     # Krylov.jl's CuVector{Float64} workspaces are (src/inversion.jl:84)
-    if rank == 0 and world == 1 and not channel and a.preconditioner == "diagonal" and not a.no_multigrid and N >= 8192:
+    if a.full and rank == 0 and world == 1 and not channel and a.preconditioner == "diagonal" and not a.no_multigrid and N >= 8192:
         t_x = time.time()
         f64 = workloads.example_model(arch, mesh_model, dt=a.dt, fine_fe_data=model.fe_data)
         if a.extrapolate_guess:
@@ -516,7 +552,7 @@ def main():
                 "csr_equivalent_GBps": alg_bytes / (ms64 / l64 * 1e-3) / 1e9}
         del f64
     # ---- small meshes (the reference's own): the explicit inverse in HBM instead of latency-bound Krylov iterations
-    if rank == 0 and world == 1 and not channel and a.preconditioner == "diagonal" and not a.no_multigrid and N <= 40000:
+    if a.full and rank == 0 and world == 1 and not channel and a.preconditioner == "diagonal" and not a.no_multigrid and N <= 40000:
         t_d = time.time()
         dm = workloads.example_model(arch, mesh_model, dt=a.dt, preconditioner="dense_inverse")
         npg.invert(dm)
@@ -538,7 +574,7 @@ def main():
             "all_solved": all(x[1]["solved"] == 1 for x in st), "preconditioner": repr(dm.inversion.solver.P),
             "setup_seconds": round(t_d, 1)}
         del dm
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not channel:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not channel:
         big = N > 40000
         A_host = None
         base_model = mesh_model

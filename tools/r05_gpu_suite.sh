@@ -4,7 +4,7 @@ O=gpurun_out; mkdir -p $O
 timeout -k 10 900 python3 -m pytest tests -m gpu -x -q --durations=15 > $O/r05_gputests.log 2>&1; rc=$?
 tail -30 $O/r05_gputests.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 400 python3 bench.py --steps 3 --warmup 1 > $O/r05_bench_short.json 2> $O/r05_bench_short.err || { tail -20 $O/r05_bench_short.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full --steps 3 --warmup 1 > $O/r05_bench_short.json 2> $O/r05_bench_short.err || { tail -20 $O/r05_bench_short.err; exit 1; }
 python3 - <<'PY'
 import json
 d = json.loads(open('gpurun_out/r05_bench_short.json').read().strip().splitlines()[-1])
