@@ -261,6 +261,13 @@ int npg_gmres_set_split(npg_gmres *ws, int mode);
 int npg_gmres_get_profile(npg_gmres *ws, double *ms_total, int64_t *launches);
 /* residual history of the last solve (workspace.stats.residuals with history=true): returns entries written */
 int64_t npg_gmres_history(npg_gmres *ws, double *buf, int64_t cap);
+/* The kernel instances the last solve launched, as up to n int32 entries in this order: split organisation, stored basis bits
+ * (64 / 32), fast orthogonalisation kernels, SpMV input from the fp32 gather copy (0 = off, 1 = node records, 2 = plain CSR),
+ * windowed tile set, lanes per node of the windowed segmented sums, windowed set with ordinary tiles, lanes per row of the
+ * tiled SpMV, full node records, distributed (halo attached), Pythagorean norm, tiles of the Arnoldi launch, workgroups of the
+ * Arnoldi launch, workgroups of the row / orthogonalisation kernels, rows, memory, lazy second-pass sums.  Returns the number of
+ * entries written (0 before the first solve and after a solve that failed). */
+int npg_gmres_last_config(const npg_gmres *ws, int32_t *cfg, int n);
 
 /* CgWorkspace(n, n, VT)  (src/evolution.jl:120) */
 int npg_cg_create(npg_ctx *ctx, int64_t n, npg_cg **out);

@@ -2310,6 +2310,12 @@ __global__ void k_fill_gather32(const double *__restrict__ x, GatherMap g, int64
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         g.p[g.pos((int)i)] = (float)x[i];
 }
+// a rank's row block with ghost nodes (npg_csr_set_ghost_nodes): the windowed tiles read ghost column i ALSO from its node slot
+// gslot[i] of the copy - what the halo unpack writes in a solve (k_ghosts_to_f32); xg = x + m, the ghost segment
+__global__ void k_fill_ghost_slots(const double *__restrict__ xg, float *__restrict__ p, int64_t ng, const int32_t *__restrict__ gslot) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < ng; i += (int64_t)gridDim.x * blockDim.x)
+        if (gslot[i] >= 0) p[gslot[i]] = (float)xg[i];
+}
 
 // y = A x with x read from its fp32 gather-layout copy: the SpMV of the Krylov kernels' gather-layout instance, stand-alone.
 // WL > 0: the matrix's windowed tile set (block tiles gather every distinct column once into LDS); 0: its ordinary tiles.
@@ -2589,6 +2595,9 @@ NPG_API int npg_spmv_gather32(const npg_csr *A, const npg_vec *x, npg_vec *y, in
     const GatherMap g{buf, 3 * A->nfull, A->nfull, (int)nbr, (int)(4 * gather32_nodes(A) - nbr)};
     hipLaunchKernelGGL(k_fill_gather32, dim3((unsigned)std::min<int64_t>(4096, (A->n + 255) / 256)), dim3(256), 0, A->ctx->stream, x->d, g,
                        A->n);
+    if (A->gslot && A->n > A->m)
+        hipLaunchKernelGGL(k_fill_ghost_slots, dim3((unsigned)std::min<int64_t>(4096, (A->n - A->m + 255) / 256)), dim3(256), 0,
+                           A->ctx->stream, x->d + A->m, buf, A->n - A->m, A->gslot);
     for (int r = 0; r < std::max(1, reps); ++r) switch (A->lanes) {
             case 4: launch_spmv_g32<4>(A, g, y->d, windowed != 0); break;
             case 8: launch_spmv_g32<8>(A, g, y->d, windowed != 0); break;

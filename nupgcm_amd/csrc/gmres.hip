@@ -852,6 +852,9 @@ __global__ void __launch_bounds__(1024) k_reduce_rows(const double *__restrict__
 
 using namespace npg;
 
+// npg_gmres_last_config: entries of the report, in this order (nupgcm_amd/iterative_solvers.py names them)
+constexpr int kCfgLen = 17;
+
 struct npg_gmres {
     npg_ctx *ctx = nullptr;
     int64_t n = 0;
@@ -894,6 +897,8 @@ struct npg_gmres {
     npg_halo *halo = nullptr;
     double *Rg = nullptr;         // 3 x 32 doubles: all-reduced rows (distributed mode)
     int64_t n_ghost = 0;
+    int32_t cfg[kCfgLen] = {};    // the kernel instances the last solve launched (npg_gmres_last_config)
+    bool have_cfg = false;
 };
 
 // fold one set of partial rows into a single row (split and distributed modes) and sum it over the ranks (distributed)
@@ -1170,6 +1175,7 @@ NPG_API int npg_gmres_solve(npg_gmres *ws, const npg_csr *A_in, int precond_kind
                             const npg_vec *precond_diag, const npg_vec *y, npg_vec *x, double atol, double rtol,
                             int64_t itmax, double reorth_eta, npg_solve_stats *stats) {
     NPG_REQUIRE(ws && A_in && y && x, "npg_gmres_solve: NULL argument");
+    ws->have_cfg = false;         // (npg_gmres_last_config reports nothing for a solve that fails)
     if (A_in->uperm && !A_in->uperm_active) {
         // npg_csr_block_nodes_dofs: right-hand side, iterate (warm start in, solution out) and a vector preconditioner come and go
         // in the CALLER's DoF order - three gather passes in, one scatter pass out, then the solve proper on the library's order
@@ -1531,6 +1537,16 @@ NPG_API int npg_gmres_solve(npg_gmres *ws, const npg_csr *A_in, int precond_kind
         }
     }
     ws->hist_len = std::min<int64_t>((int64_t)last.iter + 1, ws->hist_cap);
+    {
+        // what launch_cycle dispatched on (the selection rules above reroute on size, tolerance, matrix form and safe_mode)
+        const int a_nt = d.wt_ptr ? d.nwt : d.ntiles;
+        const int32_t cfg[kCfgLen] = {d.split, d.Vf ? 32 : 64, d.fast, d.xg.p ? (d.xg.nbr == 0 ? 2 : 1) : 0, d.wt_ptr ? 1 : 0,
+                                      d.wt_ptr ? d.wl : 0, d.wt_ptr ? d.word : 0, A->lanes, A->pk9 ? 1 : 0, dist ? 1 : 0, d.pyth,
+                                      a_nt, d.split ? std::min(d.G1, std::max(1, a_nt)) : d.G1, d.split ? d.GR : d.G2, d.n, d.mem,
+                                      d.lazy2};
+        memcpy(ws->cfg, cfg, sizeof cfg);
+        ws->have_cfg = true;
+    }
     if (dist) {
         int rcc = comm_check(ctx);      // a replayed cycle reports communication timeouts through the status word only
         if (rcc) return rcc;
@@ -1593,6 +1609,13 @@ NPG_API int npg_gmres_get_profile(npg_gmres *ws, double *ms_total, int64_t *laun
     *ms_total = ws->prof_ms;
     *launches = ws->prof_launches;
     return NPG_OK;
+}
+
+NPG_API int npg_gmres_last_config(const npg_gmres *ws, int32_t *cfg, int n) {
+    if (!ws || !cfg || n <= 0 || !ws->have_cfg) return 0;
+    const int k = std::min(n, kCfgLen);
+    memcpy(cfg, ws->cfg, (size_t)k * sizeof(int32_t));
+    return k;
 }
 
 NPG_API int64_t npg_gmres_history(npg_gmres *ws, double *buf, int64_t cap) {

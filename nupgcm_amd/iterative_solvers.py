@@ -90,6 +90,18 @@ class GmresWorkspace(_Workspace):
         k = L.lib().npg_gmres_history(self.h, L.ptr(buf), buf.size)
         return buf[:max(k, 0)]
 
+    CONFIG_KEYS = ("split", "basis", "fast", "xg", "windowed", "wl", "word", "L", "pk9", "distributed", "pyth", "tiles",
+                   "grid", "row_grid", "n", "memory", "lazy2")
+
+    def last_config(self):
+        """the kernel instances the last solve launched (npg_gmres_last_config): dict over CONFIG_KEYS - split organisation, stored
+        basis bits, fast orthogonalisation kernels, gather-copy input mode (0 / 1 node records / 2 plain CSR), windowed tiles, their
+        lanes per node, windowed set with ordinary tiles, lanes per row, full node records, distributed, Pythagorean norm, tiles and
+        workgroups of the Arnoldi launch, workgroups of the row kernels, rows, memory, lazy second-pass sums; {} before any solve"""
+        buf = np.zeros(len(self.CONFIG_KEYS), dtype=np.int32)
+        k = L.lib().npg_gmres_last_config(self.h, L.ptr(buf), buf.size)
+        return {name: int(v) for name, v in zip(self.CONFIG_KEYS, buf[:k])}
+
     def set_split(self, mode):
         """-1: by size (default), 0: fused Arnoldi kernel, 1: split kernels + column-major basis (npg_gmres_set_split)"""
         L.check(L.lib().npg_gmres_set_split(self.h, int(mode)))
