@@ -40,6 +40,8 @@ typedef struct npg_precond npg_precond;
 typedef struct npg_ilu0 npg_ilu0;
 typedef struct npg_index npg_index;
 typedef struct npg_fgmres npg_fgmres;
+typedef struct npg_locator npg_locator;
+typedef struct npg_located npg_located;
 
 /* ---- context: replaces the implicit CUDA.jl device/stream (ext/nuPGCMCUDAExt.jl:8-16) ------------------------- */
 int npg_ctx_create(int device, npg_ctx **out);
@@ -466,6 +468,36 @@ int npg_fe_restrict_coeff(npg_fe *coarse, const npg_fe *fine, const char *name);
 int npg_fe_coeff_cell_mean(const npg_fe *fe, const char *name, npg_vec *out);
 /* CFL:  min_K h_K / max(max_q |u|, u_min)   (update_dt!, src/timesteppers.jl:108-119) */
 int npg_fe_cfl_ratio(npg_fe *fe, const double *h_cells_host, double u_min, const npg_vec *x_inv, double *out);
+
+/* ---- point sampling of the device-resident state: nan_eval / plot_slice / plot_profiles (src/plotting.jl:9-90) ------
+ * The reference evaluates FEFunctions at points through Gridap's point search and returns NaN outside the domain
+ * (src/plotting.jl:13-24); its `cache` argument (plot_slice(cache, u, b)) is the split kept here: a set of points is
+ * LOCATED once (npg_locator_find -> npg_located: cell id and barycentric coordinates per point, device-resident) and
+ * EVALUATED as often as the state changes (npg_fe_sample).
+ * Locator: anchor = [ncell][3] host doubles, the coordinates of each cell's OWN local vertex 0 (cells across a periodic seam
+ * are located where they lie); with the engine's grad_lambda, lambda_i(x) = G_i . (x - x0) (i = 1..3), lambda_0 = 1 - sum.
+ * A uniform bin grid over the mesh's bounding box lists per bin the cells whose bounding box overlaps it; nbins = 0 picks
+ * about one bin per cell.  A point belongs to the candidate of its bin with the largest min lambda, ties to the lowest cell
+ * id, if that min lambda >= -1e-10; otherwise cell = -1 and lambda = NaN. */
+int npg_locator_create(npg_fe *fe, const double *anchor, int64_t nbins, npg_locator **out);
+int npg_locator_destroy(npg_locator *loc);
+/* dims[3] bins per axis, box[6] = {lo[3], hi[3]}, total bin entries, longest candidate list (any may be NULL) */
+int npg_locator_info(const npg_locator *loc, int64_t *dims, double *box, int64_t *nentries, int64_t *max_per_bin);
+/* n located points: int32 cell ids [n] and fp64 barycentric coordinates [n][4] on the device.  upload takes them from the
+ * caller instead of a locator (npg_fe_sample checks every cell id against the engine's cell count before using it). */
+int npg_located_create(npg_ctx *ctx, int64_t n, npg_located **out);
+int npg_located_destroy(npg_located *pts);
+int npg_located_upload(npg_located *pts, const int32_t *cell, const double *lambda);
+int npg_located_download(const npg_located *pts, int32_t *cell, double *lambda);
+/* points: [n][3] coordinates (a vector of 3 n doubles); out: created for n points */
+int npg_locator_find(npg_locator *loc, const npg_vec *points, int64_t n, npg_located *out);
+#define NPG_SAMPLE_U 1        /* velocity, 3 values: P2 through cell_u and the Dirichlet table; vec = [u; p]            */
+#define NPG_SAMPLE_P 2        /* pressure, 1 value: P1 through cell_p, the pinned vertex reads 0; vec = [u; p]          */
+#define NPG_SAMPLE_B 3        /* buoyancy perturbation b', 1 value: P2 or P1 by nloc_b; vec = the buoyancy vector       */
+#define NPG_SAMPLE_GRAD_B 4   /* grad b', 3 values: shape derivatives in lambda contracted with the cell's grad_lambda  */
+/* out[n][ncomp] (a vector of ncomp n doubles) = the field at the located points; NaN in every component where cell = -1
+ * (or a cell id outside the engine's cells).  Shape functions in closed form from lambda, local ordering of the DoF tables. */
+int npg_fe_sample(npg_fe *fe, int field, const npg_vec *vec, const npg_located *pts, npg_vec *out);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (new work: the reference is single-device) ----------------- */
 #define NPG_UNIQUE_ID_BYTES 128

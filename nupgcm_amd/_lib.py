@@ -150,6 +150,10 @@ def _declare(L, partial=False):
         "npg_fe_assemble_matrix": [P, C.c_int, D, C.c_int, P, P], "npg_fe_assemble_rhs_diff": [P, D, P],
         "npg_fe_update_kappa_convection": [P, VP, D, D, D, D, P],
         "npg_fe_update_nu_eddy": [P, D, D, D, D, D, P], "npg_fe_restrict_coeff": [P, P, C.c_char_p], "npg_fe_coeff_cell_mean": [P, C.c_char_p, P], "npg_fe_cfl_ratio": [P, VP, D, P, C.POINTER(D)],
+        "npg_locator_create": [P, VP, I64, PP], "npg_locator_destroy": [P],
+        "npg_locator_info": [P, VP, VP, C.POINTER(I64), C.POINTER(I64)],
+        "npg_located_create": [P, I64, PP], "npg_located_destroy": [P], "npg_located_upload": [P, VP, VP],
+        "npg_located_download": [P, VP, VP], "npg_locator_find": [P, P, I64, P], "npg_fe_sample": [P, C.c_int, P, P, P],
         "npg_comm_unique_id": [VP], "npg_comm_init": [P, VP, C.c_int, C.c_int],
         "npg_comm_allreduce_sum": [P, C.POINTER(D), C.c_int], "npg_comm_info": [P, C.c_char_p, C.c_size_t], "npg_comm_disable_peer": [P], "npg_comm_allreduce_vec": [P, P],
         "npg_comm_allgather_segments": [P, P, C.c_int, VP, VP, VP, VP, P],
@@ -202,4 +206,5 @@ NPG_PRECOND_NONE, NPG_PRECOND_SCALAR, NPG_PRECOND_DIAG = 0, 1, 2
 NPG_PC_BLOCKDIAG, NPG_PC_MG, NPG_PC_DENSE = 1, 2, 3
 NPG_BDF1, NPG_BDF2 = 1, 2
 NPG_FE_FP64, NPG_FE_FP32 = 0, 1
+NPG_SAMPLE_U, NPG_SAMPLE_P, NPG_SAMPLE_B, NPG_SAMPLE_GRAD_B = 1, 2, 3, 4
 NPG_MAT_M, NPG_MAT_KH, NPG_MAT_KV, NPG_MAT_A, NPG_MAT_B = 1, 2, 3, 4, 5

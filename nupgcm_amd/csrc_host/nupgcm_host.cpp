@@ -1125,3 +1125,116 @@ NPG_API int npg_fe_cfl_ratio(npg_fe *fe, const double *h_cells_host, double u_mi
     *out = best;
     return NPG_OK;
 }
+
+// ---- point sampling of the state (csrc/sample.hip on the host): the bins, the acceptance rule, the tie-break and the shape
+// functions are the SAME code (csrc/sample_core.h), looped over the points with OpenMP --------------------------------------------
+#include "../csrc/sample_core.h"
+
+struct npg_locator {
+    npg_ctx *ctx = nullptr;
+    int64_t ncell = 0;
+    npg::BinTables t;
+};
+struct npg_located {
+    npg_ctx *ctx = nullptr;
+    int64_t n = 0;
+    std::vector<int32_t> cell;
+    std::vector<double> lam;
+};
+namespace {
+struct HostTables {      // the engine's tables as sample_point reads them ([cell][component])
+    const npg_fe *fe;
+    const double *udiri, *bdiri;
+    int nb;
+    int32_t cu(int l, int64_t c) const { return fe->cu[(size_t)c * 30 + l]; }
+    int32_t cp(int m, int64_t c) const { return fe->cp[(size_t)c * 4 + m]; }
+    int32_t cb(int i, int64_t c) const { return fe->cb[(size_t)c * nb + i]; }
+    double G(int k, int64_t c) const { return fe->G[(size_t)c * 12 + k]; }
+};
+}  // namespace
+
+NPG_API int npg_locator_create(npg_fe *fe, const double *anchor, int64_t nbins, npg_locator **out) {
+    REQUIRE(fe && anchor && out, "npg_locator_create: NULL argument");
+    REQUIRE(nbins >= 0 && nbins <= ((int64_t)1 << 26), "npg_locator_create: nbins must be 0 (automatic) .. 2^26");
+    npg_locator *loc = new npg_locator();
+    loc->ctx = fe->ctx;
+    loc->ncell = fe->ncell;
+    const char *err = npg::build_bins(fe->G.data(), anchor, fe->ncell, nbins, loc->t);
+    if (err) {
+        delete loc;
+        REQUIRE(false, "%s", err);
+    }
+    *out = loc;
+    return NPG_OK;
+}
+NPG_API int npg_locator_destroy(npg_locator *loc) {
+    delete loc;
+    return NPG_OK;
+}
+NPG_API int npg_locator_info(const npg_locator *loc, int64_t *dims, double *box, int64_t *nentries, int64_t *max_per_bin) {
+    REQUIRE(loc, "npg_locator_info: NULL handle");
+    for (int a = 0; a < 3; ++a) {
+        if (dims) dims[a] = loc->t.grid.nb[a];
+        if (box) box[a] = loc->t.grid.lo[a], box[3 + a] = loc->t.grid.hi[a];
+    }
+    if (nentries) *nentries = (int64_t)loc->t.bin_cells.size();
+    if (max_per_bin) *max_per_bin = loc->t.max_per_bin;
+    return NPG_OK;
+}
+NPG_API int npg_located_create(npg_ctx *ctx, int64_t n, npg_located **out) {
+    REQUIRE(ctx && out && n >= 0, "npg_located_create: bad argument");
+    REQUIRE(n <= ((int64_t)1 << 32), "npg_located_create: too many points for one launch (sample in chunks)");
+    npg_located *p = new npg_located();
+    p->ctx = ctx;
+    p->n = n;
+    p->cell.assign((size_t)n, -1);
+    p->lam.assign((size_t)n * 4, NAN);
+    *out = p;
+    return NPG_OK;
+}
+NPG_API int npg_located_destroy(npg_located *p) {
+    delete p;
+    return NPG_OK;
+}
+NPG_API int npg_located_upload(npg_located *p, const int32_t *cell, const double *lambda) {
+    REQUIRE(p && (p->n == 0 || (cell && lambda)), "npg_located_upload: NULL argument");
+    std::copy(cell, cell + p->n, p->cell.begin());
+    std::copy(lambda, lambda + 4 * p->n, p->lam.begin());
+    return NPG_OK;
+}
+NPG_API int npg_located_download(const npg_located *p, int32_t *cell, double *lambda) {
+    REQUIRE(p, "npg_located_download: NULL handle");
+    if (cell) std::copy(p->cell.begin(), p->cell.end(), cell);
+    if (lambda) std::copy(p->lam.begin(), p->lam.end(), lambda);
+    return NPG_OK;
+}
+NPG_API int npg_locator_find(npg_locator *loc, const npg_vec *points, int64_t n, npg_located *out) {
+    REQUIRE(loc && points && out, "npg_locator_find: NULL argument");
+    REQUIRE(n >= 0 && points->n == 3 * n && out->n == n, "npg_locator_find: points must hold 3 n doubles and out n points");
+    const npg::BinTables &t = loc->t;
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; ++i)
+        npg::locate_point(t.grid, t.bin_ptr.data(), t.bin_cells.data(), t.geo.data(), points->d + 3 * i, &out->cell[(size_t)i],
+                          &out->lam[(size_t)4 * i]);
+    return NPG_OK;
+}
+NPG_API int npg_fe_sample(npg_fe *fe, int field, const npg_vec *vec, const npg_located *pts, npg_vec *out) {
+    REQUIRE(fe && vec && pts && out, "npg_fe_sample: NULL argument");
+    REQUIRE(field >= NPG_SAMPLE_U && field <= NPG_SAMPLE_GRAD_B, "npg_fe_sample: unknown field %d", field);
+    const bool flow = field == NPG_SAMPLE_U || field == NPG_SAMPLE_P;
+    REQUIRE(vec->n == (flow ? fe->n_inv : fe->n_b), "npg_fe_sample: the field's vector has %lld entries, expected %lld",
+            (long long)vec->n, (long long)(flow ? fe->n_inv : fe->n_b));
+    const int64_t n = pts->n;
+    const int nc = npg::sample_ncomp(field);
+    REQUIRE(out->n == n * nc, "npg_fe_sample: out must hold %d values per point", nc);
+    const HostTables t{fe, fe->u_diri.data(), fe->b_diri.data(), fe->nb};
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t c = pts->cell[(size_t)i];
+        if (c >= 0 && c < fe->ncell)         // cell ids may come from the caller (npg_located_upload)
+            npg::sample_point(t, field, vec->d, c, &pts->lam[(size_t)4 * i], out->d + (size_t)nc * i);
+        else
+            for (int a = 0; a < nc; ++a) out->d[(size_t)nc * i + a] = NAN;
+    }
+    return NPG_OK;
+}

@@ -129,7 +129,9 @@ def run(model: Model, n_info=10, n_save=float("inf"), n_plot=float("inf"), advec
     """run!(model; n_info, n_save, n_plot, advection) - src/model.jl:90-211.  `n_steps` (extension) bounds the number of
     steps taken by this call so that a caller can time a fixed number of steps; state carries over between calls.
     Every n_save steps the state goes to <out_dir>/data/state_<i>.jld2 and .vtu (src/model.jl:194-197, io.set_out_dir);
-    n_plot is accepted and ignored: sim_plots is plotting (out of scope)."""
+    Every n_plot steps `model.on_plot(model, t)` is called where the reference calls sim_plots (src/model.jl:199-200) if the model
+    has a callable `on_plot` (unset by default: nothing happens); nupgcm_amd.sampling supplies what such a hook samples, drawing
+    the pictures is the caller's."""
     ts, prm, frc = model.timestepper, model.params, model.forcings
     inv_x, b = model.inversion.solver.x, model.b_vec
     fe = model.evolution.fe
@@ -208,6 +210,8 @@ def run(model: Model, n_info=10, n_save=float("inf"), n_plot=float("inf"), advec
         if n_save != float("inf") and i % int(n_save) == 0:                                     # src/model.jl:194-197
             from . import io as _io
             _io.save_checkpoint(model, i)                         # collective for distributed models; rank 0 writes
+        if n_plot != float("inf") and i % int(n_plot) == 0 and callable(getattr(model, "on_plot", None)):   # src/model.jl:199-200
+            model.on_plot(model, ts.t)
         model.step_index += 1
         taken += 1
     ctx.sync()

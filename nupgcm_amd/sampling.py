@@ -1,0 +1,282 @@
+"""Sampling the device-resident state at points - nan_eval, plot_slice's and plot_profiles' grids (src/plotting.jl:9-90,
+279-300) and the evenly spaced grid the reference's post-processing starts from (postprocess/utils.py:33-83,
+postprocess/streamfunctions.py:14-45).
+
+The state never leaves the device to be looked at: a `PointLocator` (npg_locator: uniform bins over the mesh's bounding box)
+finds, for every point, the cell that contains it and its barycentric coordinates; `npg_fe_sample` evaluates u, p, b' or
+grad b' there from the solver vectors through the engine's DoF tables.  Outside the mesh every value is NaN, as nan_eval returns
+it.  Locating and evaluating are separate steps: the `Located` points of a fixed slice are the reference's plotting `cache`
+(plot_slice(cache, u, b)) - located once, re-evaluated every n_plot steps.  Drawing the pictures (matplotlib) is not part of this
+package; `model.on_plot` (model.run) is where a caller hangs it."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+from .architectures import DeviceVector
+from .inversion import device_fe
+
+_FIELDS = {"u": (L.NPG_SAMPLE_U, 3), "p": (L.NPG_SAMPLE_P, 1), "b": (L.NPG_SAMPLE_B, 1), "grad_b": (L.NPG_SAMPLE_GRAD_B, 3)}
+_trapz = getattr(np, "trapezoid", None) or np.trapz
+CHUNK = 1 << 21          # points located / evaluated per call by sample_to_grid: ~150 MB of device memory at a time
+
+
+def _single_device(model):
+    if getattr(model, "partition", None) is not None or getattr(model, "comm", None) is not None \
+            or getattr(model.arch.ctx, "nranks", 1) > 1:
+        raise NotImplementedError("sampling a partitioned / distributed model is not implemented: every rank holds a part of "
+                                  "the state only; sample a single-device model (or a checkpoint loaded into one)")
+    if getattr(model.fe_data.mesh, "dim", 3) != 3:
+        raise NotImplementedError("sampling is implemented for tetrahedral (3-D) meshes")
+
+
+class Located:
+    """n located points on the device (npg_located): the cell id of each (-1 outside the mesh) and its barycentric coordinates
+    there.  The reference's evaluation `cache`."""
+
+    def __init__(self, ctx, n):
+        h = C.c_void_p()
+        L.check(L.lib().npg_located_create(ctx.h, int(n), C.byref(h)))
+        self.h, self.ctx, self.n = h, ctx, int(n)
+
+    @classmethod
+    def from_host(cls, ctx, cells, lambdas):
+        """points located by the caller: cells (n,) int, lambdas (n, 4).  Cell ids are checked when they are used."""
+        c, lam = L.as_i32(cells), L.as_f64(lambdas)
+        if lam.shape != (c.size, 4):
+            raise ValueError(f"Located.from_host: lambdas must be ({c.size}, 4), got {lam.shape}")
+        out = cls(ctx, c.size)
+        L.check(L.lib().npg_located_upload(out.h, L.ptr(c), L.ptr(lam)))
+        return out
+
+    def __del__(self):
+        try:
+            if self.h:
+                L.lib().npg_located_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self.n
+
+    @property
+    def cells(self):
+        c = np.empty(self.n, dtype=np.int32)
+        L.check(L.lib().npg_located_download(self.h, L.ptr(c), None))
+        return c
+
+    @property
+    def lambdas(self):
+        lam = np.empty((self.n, 4))
+        L.check(L.lib().npg_located_download(self.h, None, L.ptr(lam)))
+        return lam
+
+    @property
+    def valid(self):
+        """mask of the points that lie in the mesh (downloaded on request)"""
+        return self.cells >= 0
+
+
+class PointLocator:
+    """PointLocator(model, nbins=0): the point search of one mesh on the model's architecture.  nbins = 0 chooses about one bin
+    per cell.  `.locate(points)` -> Located."""
+
+    def __init__(self, model, nbins=0):
+        _single_device(model)
+        m = model.fe_data.mesh
+        self.ctx, self.fe = model.arch.ctx, device_fe(model.arch, model.fe_data)
+        # each cell's OWN first vertex: across a periodic seam a cell lies where its geometry says, not where its vertices' masters do
+        anchor = L.as_f64(m.geo_coords[m.cell_geo[:, 0]])
+        h = C.c_void_p()
+        L.check(L.lib().npg_locator_create(self.fe.h, L.ptr(anchor), int(nbins), C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if self.h:
+                L.lib().npg_locator_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def info(self):
+        """bins per axis, bounding box (lo, hi), total candidate entries, mean and max candidates per bin"""
+        dims, box = np.zeros(3, dtype=np.int64), np.zeros(6)
+        ne, mx = C.c_int64(), C.c_int64()
+        L.check(L.lib().npg_locator_info(self.h, L.ptr(dims), L.ptr(box), C.byref(ne), C.byref(mx)))
+        return dict(dims=tuple(int(v) for v in dims), lo=box[:3].copy(), hi=box[3:].copy(), entries=ne.value,
+                    mean_per_bin=ne.value / float(np.prod(dims)), max_per_bin=mx.value)
+
+    @property
+    def bounding_box(self):
+        i = self.info()
+        return i["lo"], i["hi"]
+
+    def locate(self, points) -> Located:
+        pts = L.as_f64(points).reshape(-1, 3)
+        out = Located(self.ctx, len(pts))
+        if len(pts):
+            pv = DeviceVector.from_host(self.ctx, pts.ravel())
+            L.check(L.lib().npg_locator_find(self.h, pv.h, len(pts), out.h))
+        return out
+
+
+def locator(model) -> PointLocator:
+    """the model's point locator, built on first use"""
+    loc = model.__dict__.get("_point_locator")
+    if loc is None:
+        loc = model.__dict__["_point_locator"] = PointLocator(model)
+    return loc
+
+
+def _evaluate(model, field, located: Located):
+    code, nc = _FIELDS[field]
+    fe = device_fe(model.arch, model.fe_data)
+    vec = model.b_vec if field in ("b", "grad_b") else model.inversion.solver.x
+    out = DeviceVector(model.arch.ctx, max(1, located.n * nc))
+    if located.n == 0:
+        return np.empty((0, nc) if nc > 1 else (0,))
+    L.check(L.lib().npg_fe_sample(fe.h, code, vec.h, located.h, out.h))
+    a = out.to_host()
+    return a.reshape(-1, nc) if nc > 1 else a
+
+
+def nan_eval(model, field, points, cache: Located = None, perturbation=False):
+    """nan_eval(u, x) of src/plotting.jl:9-31 for the model's fields: field "u" (n, 3), "p" (n,), "b" (n,), "grad_b" (n, 3) at
+    points (n, 3), NaN outside the mesh.  "b" is the full buoyancy N2 z + b' and "grad_b" its gradient (N2 added to the z
+    component), as save_vtk / plot_slice show it; perturbation=True returns b' / grad b' alone.  cache: the `Located` of an earlier
+    call on the same points (returned by PointLocator.locate) - the points are then not searched again."""
+    _single_device(model)
+    if field not in _FIELDS:
+        raise ValueError(f"nan_eval: field must be one of {sorted(_FIELDS)}, got {field!r}")
+    pts = L.as_f64(points).reshape(-1, 3)
+    if cache is None:
+        cache = locator(model).locate(pts)
+    elif cache.n != len(pts):
+        raise ValueError(f"nan_eval: the cache holds {cache.n} points, got {len(pts)}")
+    v = _evaluate(model, field, cache)
+    if not perturbation and model.params.N2 != 0.0:
+        if field == "b":
+            v = v + model.params.N2 * pts[:, 2]            # NaN + finite = NaN: outside stays outside
+        elif field == "grad_b":
+            v[:, 2] += model.params.N2
+    return v
+
+
+def sample_slice(model, x=None, y=None, z=None, bbox=(-1, -1, 1, 1), n=256, cache=None):
+    """The grid of plot_slice (src/plotting.jl:61-80): one of x, y, z fixes the plane, bbox = (a_min, b_min, a_max, b_max) bounds the
+    two remaining axes (in the order x, y, z), n points each way.  Returns a dict: `axes` (the two coordinate arrays), `dir`,
+    u (n, n, 3), b (n, n) (full buoyancy) and `cache`, which a later call takes back as cache= to skip the point search."""
+    a = np.linspace(bbox[0], bbox[2], n)
+    b = np.linspace(bbox[1], bbox[3], n)
+    A, B = np.meshgrid(a, b, indexing="ij")
+    if x is not None:
+        d, pts = "x", np.stack([np.full_like(A, float(x)), A, B], axis=-1)
+    elif y is not None:
+        d, pts = "y", np.stack([A, np.full_like(A, float(y)), B], axis=-1)
+    elif z is not None:
+        d, pts = "z", np.stack([A, B, np.full_like(A, float(z))], axis=-1)
+    else:
+        raise ValueError("One of x, y, or z must be specified for slice.")
+    pts = pts.reshape(-1, 3)
+    if cache is None:
+        cache = locator(model).locate(pts)
+    return dict(dir=d, axes=(a, b), points=pts, cache=cache,
+                u=nan_eval(model, "u", pts, cache).reshape(n, n, 3), b=nan_eval(model, "b", pts, cache).reshape(n, n))
+
+
+def find_H(model, x, y, tol=1e-8, n_probe=256):
+    """Depth of the water column at (x, y) - find_H, src/plotting.jl:38-57: the lowest valid point of a probe of n_probe points
+    between the bottom of the bounding box and z = 0, refined by bisection on validity to tol.  0 if the column is dry."""
+    loc = locator(model)
+    zlo = float(loc.bounding_box[0][2])
+    zs = np.linspace(zlo, 0.0, n_probe)
+    ok = loc.locate(np.column_stack([np.full(n_probe, float(x)), np.full(n_probe, float(y)), zs])).valid
+    if not ok.any():
+        return 0.0
+    k = int(np.argmax(ok))
+    if k == 0:
+        return -zlo
+    z_in, z_out = zs[k], zs[k - 1]
+    while abs(z_in - z_out) > tol:
+        zm = 0.5 * (z_in + z_out)
+        if loc.locate([[x, y, zm]]).valid[0]:
+            z_in = zm
+        else:
+            z_out = zm
+    return -z_in
+
+
+def sample_profiles(model, x, y, n=256):
+    """The column of plot_profiles (src/plotting.jl:279-300): n points from z = -H to 0 at (x, y) with H from find_H.  Returns a
+    dict: H, z (n,), u (n, 3), b (n,) (full buoyancy) and the `cache` of the column's points."""
+    H = find_H(model, x, y)
+    z = np.linspace(-H, 0.0, n)
+    pts = np.column_stack([np.full(n, float(x)), np.full(n, float(y)), z])
+    cache = locator(model).locate(pts)
+    return dict(H=H, z=z, points=pts, cache=cache, u=nan_eval(model, "u", pts, cache), b=nan_eval(model, "b", pts, cache))
+
+
+class GridSamples:
+    """An evenly spaced grid over the mesh's bounding box (postprocess/utils.py:33-45) and what was sampled on it: x, y, z axes,
+    valid (nx, ny, nz) bool, fields[name] of shape (nx, ny, nz[, 3]) with NaN outside."""
+
+    def __init__(self, x, y, z, valid, fields):
+        self.x, self.y, self.z, self.valid, self.fields = x, y, z, valid, fields
+        self.nx, self.ny, self.nz = len(x), len(y), len(z)
+
+    def __getitem__(self, name):
+        return self.fields[name]
+
+
+def sample_to_grid(model, nx=256, ny=256, nz=256, fields=("u", "b"), chunk=CHUNK):
+    """sample_to_grid of postprocess/utils.py:48-78 without the VTK round trip: nx x ny x nz evenly spaced points over the mesh's
+    bounding box, located and evaluated on the device.  The grid is worked through in chunks of `chunk` points (default 2^21), so the
+    extra device memory stays near 72 bytes per chunk point (coordinates, cell ids, lambdas, one field) - about 150 MB - whatever
+    the grid; the result lives on the host."""
+    _single_device(model)
+    loc = locator(model)
+    lo, hi = loc.bounding_box
+    x, y, z = (np.linspace(lo[a], hi[a], k) for a, k in enumerate((nx, ny, nz)))
+    n = nx * ny * nz
+    valid = np.empty(n, dtype=bool)
+    out = {f: np.empty((n, _FIELDS[f][1]) if _FIELDS[f][1] > 1 else n) for f in fields}
+    per_x = ny * nz
+    step = max(1, int(chunk) // per_x)                     # whole x-planes per chunk
+    Y, Z = np.meshgrid(y, z, indexing="ij")
+    for i0 in range(0, nx, step):
+        i1 = min(nx, i0 + step)
+        pts = np.empty((i1 - i0, per_x, 3))
+        pts[:, :, 0] = x[i0:i1, None]
+        pts[:, :, 1] = Y.ravel()
+        pts[:, :, 2] = Z.ravel()
+        pts = pts.reshape(-1, 3)
+        c = loc.locate(pts)
+        sl = slice(i0 * per_x, i1 * per_x)
+        valid[sl] = c.valid
+        for f in fields:
+            out[f][sl] = nan_eval(model, f, pts, c)
+    shp = (nx, ny, nz)
+    return GridSamples(x, y, z, valid.reshape(shp), {f: v.reshape(shp + v.shape[1:]) for f, v in out.items()})
+
+
+def depth(samples: GridSamples):
+    """depth of postprocess/utils.py:81-83: the vertical trapezoid of the valid mask, (nx, ny)"""
+    return _trapz(samples.valid.astype(float), x=samples.z, axis=2)
+
+
+def barotropic_streamfunction(samples: GridSamples):
+    """calculate_barotropic_streamfunction of postprocess/streamfunctions.py:14-45 on sampled u: U = vertical trapezoid of u_x (zero
+    outside the mesh, as VTK's sampling leaves it), Psi(x, y) = int_y^ymax U dy'; both NaN where the depth is 0.  Returns (Psi, U)."""
+    ux = np.nan_to_num(samples["u"][..., 0], nan=0.0)
+    U = _trapz(ux, x=samples.z, axis=2)
+    H = depth(samples)
+    dy = np.diff(samples.y)
+    cum = np.concatenate([np.zeros((U.shape[0], 1)), np.cumsum(0.5 * (U[:, 1:] + U[:, :-1]) * dy, axis=1)], axis=1)
+    Psi = cum[:, -1:] - cum
+    U[H == 0] = np.nan
+    Psi[H == 0] = np.nan
+    return Psi, U
