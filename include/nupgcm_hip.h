@@ -498,6 +498,18 @@ int npg_locator_find(npg_locator *loc, const npg_vec *points, int64_t n, npg_loc
 /* out[n][ncomp] (a vector of ncomp n doubles) = the field at the located points; NaN in every component where cell = -1
  * (or a cell id outside the engine's cells).  Shape functions in closed form from lambda, local ordering of the DoF tables. */
 int npg_fe_sample(npg_fe *fe, int field, const npg_vec *vec, const npg_located *pts, npg_vec *out);
+/* The reductions of the reference's post-processing (postprocess/utils.py:81-94, streamfunctions.py:14-80,
+ * stratification.py:45-62) over the tensor grid x[nx] (x) y[ny] (x) z[nz], in one pass over the device-resident state: every
+ * grid point is generated, located and evaluated (as npg_locator_find / npg_fe_sample would) and added to the trapezoid of its
+ * column and of its zonal line; the nx ny nz samples are never stored.  axes = [x; y; z] (nx + ny + nz doubles, each axis
+ * strictly increasing, n >= 2); the trapezoid weights come from the axes (w_0 = (a_1 - a_0) / 2, w_i = (a_{i+1} - a_{i-1}) / 2).
+ *   col[4][nx][ny], reduced over z: count of valid points, H = int mask dz, int u_x dz, int u_y dz
+ *   zon[6][ny][nz], reduced over x: count, width = int mask dx, int u_y dx, int u_z dx, int b dx with b = N2 z + b',
+ *                                   int max(d_z b, 0) dx with d_z b = N2 + d_z b'
+ * x_inv = [u; p], b = the buoyancy vector.  A point outside the mesh adds 0 to every entry.  No atomics: one fixed summation
+ * order per entry, the same bits on every call.  The locator keeps the working memory (ceil(nx / 16) partial zon arrays). */
+int npg_fe_grid_integrals(npg_fe *fe, npg_locator *loc, const npg_vec *x_inv, const npg_vec *b, double N2, const npg_vec *axes,
+                          int64_t nx, int64_t ny, int64_t nz, npg_vec *col, npg_vec *zon);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (new work: the reference is single-device) ----------------- */
 #define NPG_UNIQUE_ID_BYTES 128

@@ -154,6 +154,7 @@ def _declare(L, partial=False):
         "npg_locator_info": [P, VP, VP, C.POINTER(I64), C.POINTER(I64)],
         "npg_located_create": [P, I64, PP], "npg_located_destroy": [P], "npg_located_upload": [P, VP, VP],
         "npg_located_download": [P, VP, VP], "npg_locator_find": [P, P, I64, P], "npg_fe_sample": [P, C.c_int, P, P, P],
+        "npg_fe_grid_integrals": [P, P, P, P, D, P, I64, I64, I64, P, P],
         "npg_comm_unique_id": [VP], "npg_comm_init": [P, VP, C.c_int, C.c_int],
         "npg_comm_allreduce_sum": [P, C.POINTER(D), C.c_int], "npg_comm_info": [P, C.c_char_p, C.c_size_t], "npg_comm_disable_peer": [P], "npg_comm_allreduce_vec": [P, P],
         "npg_comm_allgather_segments": [P, P, C.c_int, VP, VP, VP, VP, P],

@@ -7,7 +7,16 @@
 // [component][cell] layout (a point's 10 - 30 indices are a gather either way).  No LDS, no scratch.
 // The bins are built on the host when the locator is created (set-up cost; build_bins in sample_core.h, shared with the host
 // library so that CPU() and GPU() locate identically).
+//
+// Integrals over a tensor grid (npg_fe_grid_integrals: the reductions postprocess/streamfunctions.py and stratification.py apply to
+// the 256^3 grid) without the grid ever existing in memory:
+//   k_grid_integrals   a workgroup owns one y index and kGridChunk consecutive x indices; its lanes run along z.  Per point:
+//                      locate, evaluate u, b, dz b one after another, add to the lane's zonal accumulators (registers, over the
+//                      x chunk) and to the column sums (wave_sum over z, then the 4 waves and the z tiles in a fixed order)
+//   k_grid_fold        zonal line = the sum of its chunks' partials, in chunk order
+// No atomics: every output element has one owner and one summation order.
 #include "common.h"
+#include "device_utils.h"
 #include "fe_dev.h"
 #include "sample_core.h"
 
@@ -60,6 +69,67 @@ __global__ void __launch_bounds__(kBlock) k_sample(DevTables t, const double *__
     for (int a = 0; a < NC; ++a) out[NC * i + a] = v[a];
 }
 
+// One workgroup: y index j = blockIdx.x / nchunk, x indices [kGridChunk * cx, ...) with cx = blockIdx.x % nchunk; thread t works
+// on z indices t, t + kBlock, ...  part[cx][channel][ny][nz], col[channel][nx][ny].
+template <int NB>
+__global__ void __launch_bounds__(kBlock) k_grid_integrals(BinGrid g, const int32_t *__restrict__ bin_ptr,
+                                                           const int32_t *__restrict__ bin_cells, const double *__restrict__ geo,
+                                                           DevTables t, const double *__restrict__ xu, const double *__restrict__ xb,
+                                                           double N2, const double *__restrict__ axes, int nx, int ny, int nz,
+                                                           int nchunk, double *__restrict__ col, double *__restrict__ part) {
+    constexpr int NW = kBlock / 64;
+    __shared__ double sh[kGridChunk][NW][kGridCol];
+    const int j = blockIdx.x / nchunk, cx = blockIdx.x % nchunk;
+    const int i0 = cx * kGridChunk, i1 = min(nx, i0 + kGridChunk);
+    const double *ax = axes, *az = axes + nx + ny;
+    const double y = axes[nx + j];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int ci = threadIdx.x / kGridCol, cch = threadIdx.x % kGridCol;      // the column sum this thread keeps across the z tiles
+    const bool col_owner = ci < i1 - i0;
+    double colacc = 0.0;
+    t.nb = NB;                               // a compile-time constant: the P2 / P1 branch folds away
+    for (int k0 = 0; k0 < nz; k0 += kBlock) {
+        const int k = k0 + (int)threadIdx.x;
+        const bool in = k < nz;
+        const double z = in ? az[k] : 0.0;
+        const double wz = in ? trapezoid_weight(az, nz, k) : 0.0;
+        double acc[kGridZon];
+#pragma unroll
+        for (int a = 0; a < kGridZon; ++a) acc[a] = 0.0;
+        for (int i = i0; i < i1; ++i) {
+            const double p[3] = {ax[i], y, z};
+            int32_t c = -1;
+            double l[4] = {0.0, 0.0, 0.0, 0.0};
+            if (in) locate_point(g, bin_ptr, bin_cells, geo, p, &c, l);
+            double v[kGridVal], term[kGridCol];
+            grid_point_values(t, xu, xb, N2, z, c, l, v);
+            grid_zon_add(trapezoid_weight(ax, nx, i), v, acc);
+            grid_col_terms(wz, v, term);
+#pragma unroll
+            for (int a = 0; a < kGridCol; ++a) {
+                const double s = wave_sum(term[a]);
+                if (lane == 0) sh[i - i0][wave][a] = s;
+            }
+        }
+        if (in) {
+#pragma unroll
+            for (int a = 0; a < kGridZon; ++a) part[(((size_t)cx * kGridZon + a) * ny + j) * nz + k] = acc[a];
+        }
+        __syncthreads();
+        if (col_owner) colacc += (sh[ci][0][cch] + sh[ci][1][cch]) + (sh[ci][2][cch] + sh[ci][3][cch]);
+        __syncthreads();
+    }
+    if (col_owner) col[((size_t)cch * nx + i0 + ci) * ny + j] = colacc;
+}
+
+__global__ void __launch_bounds__(kBlock) k_grid_fold(const double *__restrict__ part, int nchunk, int64_t n, double *__restrict__ zon) {
+    const int64_t e = blockIdx.x * (int64_t)kBlock + threadIdx.x;
+    if (e >= n) return;
+    double s = 0.0;
+    for (int cx = 0; cx < nchunk; ++cx) s += part[(size_t)cx * n + e];
+    zon[e] = s;
+}
+
 }  // namespace npg
 
 using namespace npg;
@@ -71,6 +141,8 @@ struct npg_locator {
     int32_t *bin_ptr = nullptr, *bin_cells = nullptr;
     double *geo = nullptr;
     int64_t nentries = 0, max_per_bin = 0;
+    double *grid_part = nullptr;     // npg_fe_grid_integrals: the zonal partials [nchunk][kGridZon][ny][nz], grown on demand
+    size_t grid_part_n = 0;
 };
 
 struct npg_located {
@@ -86,6 +158,7 @@ NPG_API int npg_locator_destroy(npg_locator *loc) {
     hipFree(loc->bin_ptr);
     hipFree(loc->bin_cells);
     hipFree(loc->geo);
+    hipFree(loc->grid_part);
     delete loc;
     return NPG_OK;
 }
@@ -214,6 +287,58 @@ NPG_API int npg_fe_sample(npg_fe *fe, int field, const npg_vec *vec, const npg_l
     else if (d.nb == 10) NPG_SAMPLE_LAUNCH(NPG_SAMPLE_GRAD_B, 10);
     else NPG_SAMPLE_LAUNCH(NPG_SAMPLE_GRAD_B, 4);
 #undef NPG_SAMPLE_LAUNCH
+    NPG_HIP(hipGetLastError());
+    return NPG_OK;
+}
+
+NPG_API int npg_fe_grid_integrals(npg_fe *fe, npg_locator *loc, const npg_vec *x_inv, const npg_vec *b, double N2, const npg_vec *axes,
+                                  int64_t nx, int64_t ny, int64_t nz, npg_vec *col, npg_vec *zon) {
+    NPG_REQUIRE(fe && loc && x_inv && b && axes && col && zon, "npg_fe_grid_integrals: NULL argument");
+    NPG_REQUIRE(nx >= 2 && ny >= 2 && nz >= 2, "npg_fe_grid_integrals: every axis needs at least 2 points");
+    NPG_REQUIRE(nx <= 65536 && ny <= 65536 && nz <= 65536, "npg_fe_grid_integrals: at most 65536 points per axis");
+    NPG_REQUIRE(loc->ctx == fe->ctx && x_inv->ctx == fe->ctx && b->ctx == fe->ctx && axes->ctx == fe->ctx && col->ctx == fe->ctx &&
+                    zon->ctx == fe->ctx, "npg_fe_grid_integrals: arguments of different contexts");
+    NPG_REQUIRE(loc->ncell == fe->d.ncell, "npg_fe_grid_integrals: the locator was built for another mesh");
+    NPG_REQUIRE(x_inv->n == fe->n_inv, "npg_fe_grid_integrals: the flow vector has %lld entries, expected %lld", (long long)x_inv->n,
+                (long long)fe->n_inv);
+    NPG_REQUIRE(b->n == fe->n_b, "npg_fe_grid_integrals: the buoyancy vector has %lld entries, expected %lld", (long long)b->n,
+                (long long)fe->n_b);
+    NPG_REQUIRE(axes->n == nx + ny + nz, "npg_fe_grid_integrals: axes must hold nx + ny + nz doubles");
+    NPG_REQUIRE(col->n == kGridCol * nx * ny && zon->n == kGridZon * ny * nz,
+                "npg_fe_grid_integrals: col must hold %d nx ny and zon %d ny nz doubles", kGridCol, kGridZon);
+    NPG_HIP(hipSetDevice(fe->ctx->device));
+    hipStream_t st = fe->ctx->stream;
+    // the axes are a few hundred doubles: checked on the host before anything is launched
+    std::vector<double> h((size_t)(nx + ny + nz));
+    NPG_HIP(hipMemcpyAsync(h.data(), axes->d, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    NPG_HIP(hipStreamSynchronize(st));
+    const int64_t len[3] = {nx, ny, nz};
+    const double *a = h.data();
+    for (int d = 0; d < 3; a += len[d], ++d) {
+        const char *err = check_axis(a, len[d]);
+        NPG_REQUIRE(!err, "npg_fe_grid_integrals: %s (axis %c)", err, "xyz"[d]);
+    }
+    const int64_t nchunk = (nx + kGridChunk - 1) / kGridChunk, nzon = kGridZon * ny * nz;
+    NPG_REQUIRE(ny * nchunk < ((int64_t)1 << 31), "npg_fe_grid_integrals: too many workgroups for one launch");
+    const size_t need = (size_t)nchunk * (size_t)nzon;
+    if (need > loc->grid_part_n) {
+        NPG_HIP(hipFree(loc->grid_part));
+        loc->grid_part = nullptr, loc->grid_part_n = 0;
+        NPG_HIP(hipMalloc((void **)&loc->grid_part, need * sizeof(double)));
+        loc->grid_part_n = need;
+    }
+    const FeDev &d = fe->d;
+    const DevTables t{d.cu, d.cp, d.cb, d.G, d.u_diri, d.b_diri, d.ncell, d.nb};
+    const dim3 grid((unsigned)(ny * nchunk)), block(kBlock);
+#define NPG_GRID_LAUNCH(NB)                                                                                                      \
+    hipLaunchKernelGGL((k_grid_integrals<NB>), grid, block, 0, st, loc->grid, loc->bin_ptr, loc->bin_cells, loc->geo, t, x_inv->d, \
+                       b->d, N2, axes->d, (int)nx, (int)ny, (int)nz, (int)nchunk, col->d, loc->grid_part)
+    if (d.nb == 10) NPG_GRID_LAUNCH(10);
+    else NPG_GRID_LAUNCH(4);
+#undef NPG_GRID_LAUNCH
+    NPG_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_grid_fold, dim3((unsigned)((nzon + kBlock - 1) / kBlock)), block, 0, st, loc->grid_part, (int)nchunk, nzon,
+                       zon->d);
     NPG_HIP(hipGetLastError());
     return NPG_OK;
 }

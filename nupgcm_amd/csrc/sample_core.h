@@ -161,6 +161,54 @@ NPG_UNROLL
 
 NPG_HD int sample_ncomp(int field) { return field == NPG_SAMPLE_U || field == NPG_SAMPLE_GRAD_B ? 3 : 1; }
 
+// ---- integrals over a tensor grid x[nx] (x) y[ny] (x) z[nz] (npg_fe_grid_integrals): what one grid point contributes ----------
+// postprocess/utils.py:81-94, streamfunctions.py:14-80, stratification.py:45-62 reduce the sampled grid with trapezoids along z
+// (columns) and along x (zonal lines); a point outside the mesh is a zero there, in the mask and in every field.
+constexpr int kGridCol = 4;    // col[.][nx][ny]: count, H = int mask dz, int u_x dz, int u_y dz
+constexpr int kGridZon = 6;    // zon[.][ny][nz]: count, width = int mask dx, int u_y dx, int u_z dx, int b dx, int max(dz b, 0) dx
+constexpr int kGridVal = 6;    // one point: mask, u_x, u_y, u_z, b (full), max(dz b, 0) (full)
+constexpr int kGridChunk = 16; // consecutive x indices per partial sum of a zonal line (the device folds the partials in order)
+
+// weight of node i in trapezoid(f, x = a): half the distance between its neighbours, one-sided at the ends
+NPG_HD double trapezoid_weight(const double *a, int64_t n, int64_t i) {
+    return 0.5 * ((i + 1 < n ? a[i + 1] : a[i]) - (i > 0 ? a[i - 1] : a[i]));
+}
+
+// The values of grid point p (located: cell c, lambda l; c < 0 = outside the mesh).  The fields are evaluated one after another
+// from the same lambda.  xu = [u; p], xb = b'; the full buoyancy is N2 z + b', its vertical derivative N2 + dz b'.
+template <class T>
+NPG_HD void grid_point_values(const T &t, const double *xu, const double *xb, double N2, double z, int64_t c, const double l[4],
+                              double v[kGridVal]) {
+NPG_UNROLL
+    for (int a = 0; a < kGridVal; ++a) v[a] = 0.0;
+    if (c < 0) return;
+    v[0] = 1.0;
+    sample_point(t, NPG_SAMPLE_U, xu, c, l, v + 1);
+    double bp, g[3];
+    sample_point(t, NPG_SAMPLE_B, xb, c, l, &bp);
+    v[4] = N2 * z + bp;
+    sample_point(t, NPG_SAMPLE_GRAD_B, xb, c, l, g);
+    v[5] = fmax(N2 + g[2], 0.0);
+}
+
+// the terms a point of vertical weight wz adds to its column's integrals
+NPG_HD void grid_col_terms(double wz, const double v[kGridVal], double term[kGridCol]) {
+    term[0] = v[0], term[1] = wz * v[0], term[2] = wz * v[1], term[3] = wz * v[2];
+}
+
+// a point of zonal weight wx added to the integrals of its zonal line
+NPG_HD void grid_zon_add(double wx, const double v[kGridVal], double acc[kGridZon]) {
+    acc[0] += v[0], acc[1] += wx * v[0], acc[2] += wx * v[2], acc[3] += wx * v[3], acc[4] += wx * v[4], acc[5] += wx * v[5];
+}
+
+// nullptr if a[0..n) is a usable axis: n >= 2, finite, strictly increasing
+inline const char *check_axis(const double *a, int64_t n) {
+    if (n < 2) return "every axis needs at least 2 points";
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(a[i]) || (i > 0 && !(a[i] > a[i - 1]))) return "the axes must be finite and strictly increasing";
+    return nullptr;
+}
+
 // ---- set-up on the host (both libraries): cell geometry records, bounding box, bins --------------------------------------
 struct BinTables {
     BinGrid grid;

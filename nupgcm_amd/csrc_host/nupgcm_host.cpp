@@ -1238,3 +1238,65 @@ NPG_API int npg_fe_sample(npg_fe *fe, int field, const npg_vec *vec, const npg_l
     }
     return NPG_OK;
 }
+NPG_API int npg_fe_grid_integrals(npg_fe *fe, npg_locator *loc, const npg_vec *x_inv, const npg_vec *b, double N2, const npg_vec *axes,
+                                  int64_t nx, int64_t ny, int64_t nz, npg_vec *col, npg_vec *zon) {
+    REQUIRE(fe && loc && x_inv && b && axes && col && zon, "npg_fe_grid_integrals: NULL argument");
+    REQUIRE(nx >= 2 && ny >= 2 && nz >= 2, "npg_fe_grid_integrals: every axis needs at least 2 points");
+    REQUIRE(nx <= 65536 && ny <= 65536 && nz <= 65536, "npg_fe_grid_integrals: at most 65536 points per axis");
+    REQUIRE(loc->ctx == fe->ctx && x_inv->ctx == fe->ctx && b->ctx == fe->ctx && axes->ctx == fe->ctx && col->ctx == fe->ctx &&
+                zon->ctx == fe->ctx, "npg_fe_grid_integrals: arguments of different contexts");
+    REQUIRE(loc->ncell == fe->ncell, "npg_fe_grid_integrals: the locator was built for another mesh");
+    REQUIRE(x_inv->n == fe->n_inv, "npg_fe_grid_integrals: the flow vector has %lld entries, expected %lld", (long long)x_inv->n,
+            (long long)fe->n_inv);
+    REQUIRE(b->n == fe->n_b, "npg_fe_grid_integrals: the buoyancy vector has %lld entries, expected %lld", (long long)b->n,
+            (long long)fe->n_b);
+    REQUIRE(axes->n == nx + ny + nz, "npg_fe_grid_integrals: axes must hold nx + ny + nz doubles");
+    REQUIRE(col->n == npg::kGridCol * nx * ny && zon->n == npg::kGridZon * ny * nz,
+            "npg_fe_grid_integrals: col must hold %d nx ny and zon %d ny nz doubles", npg::kGridCol, npg::kGridZon);
+    const double *ax = axes->d, *ay = ax + nx, *az = ay + ny;
+    const int64_t len[3] = {nx, ny, nz};
+    const double *a = ax;
+    for (int d = 0; d < 3; a += len[d], ++d) {
+        const char *err = npg::check_axis(a, len[d]);
+        REQUIRE(!err, "npg_fe_grid_integrals: %s (axis %c)", err, "xyz"[d]);
+    }
+    const npg::BinTables &bt = loc->t;
+    const HostTables t{fe, fe->u_diri.data(), fe->b_diri.data(), fe->nb};
+    auto values = [&](int64_t i, int64_t j, int64_t k, double v[npg::kGridVal]) {
+        const double p[3] = {ax[i], ay[j], az[k]};
+        int32_t c;
+        double l[4];
+        npg::locate_point(bt.grid, bt.bin_ptr.data(), bt.bin_cells.data(), bt.geo.data(), p, &c, l);
+        npg::grid_point_values(t, x_inv->d, b->d, N2, p[2], c, l, v);
+    };
+    // every point is evaluated twice, once for its column and once for its zonal line: each output entry then has one owner and
+    // one summation order (columns: k ascending; zonal lines: chunks of kGridChunk x indices, folded in order, as the device does)
+#pragma omp parallel for collapse(2) schedule(dynamic, 16)
+    for (int64_t i = 0; i < nx; ++i)
+        for (int64_t j = 0; j < ny; ++j) {
+            double s[npg::kGridCol] = {0.0, 0.0, 0.0, 0.0};
+            for (int64_t k = 0; k < nz; ++k) {
+                double v[npg::kGridVal], term[npg::kGridCol];
+                values(i, j, k, v);
+                npg::grid_col_terms(npg::trapezoid_weight(az, nz, k), v, term);
+                for (int ch = 0; ch < npg::kGridCol; ++ch) s[ch] += term[ch];
+            }
+            for (int ch = 0; ch < npg::kGridCol; ++ch) col->d[((size_t)ch * nx + i) * ny + j] = s[ch];
+        }
+#pragma omp parallel for collapse(2) schedule(dynamic, 16)
+    for (int64_t j = 0; j < ny; ++j)
+        for (int64_t k = 0; k < nz; ++k) {
+            double s[npg::kGridZon] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            for (int64_t i0 = 0; i0 < nx; i0 += npg::kGridChunk) {
+                double acc[npg::kGridZon] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+                for (int64_t i = i0; i < std::min(nx, i0 + npg::kGridChunk); ++i) {
+                    double v[npg::kGridVal];
+                    values(i, j, k, v);
+                    npg::grid_zon_add(npg::trapezoid_weight(ax, nx, i), v, acc);
+                }
+                for (int ch = 0; ch < npg::kGridZon; ++ch) s[ch] += acc[ch];
+            }
+            for (int ch = 0; ch < npg::kGridZon; ++ch) zon->d[((size_t)ch * ny + j) * nz + k] = s[ch];
+        }
+    return NPG_OK;
+}

@@ -7,7 +7,13 @@ finds, for every point, the cell that contains it and its barycentric coordinate
 grad b' there from the solver vectors through the engine's DoF tables.  Outside the mesh every value is NaN, as nan_eval returns
 it.  Locating and evaluating are separate steps: the `Located` points of a fixed slice are the reference's plotting `cache`
 (plot_slice(cache, u, b)) - located once, re-evaluated every n_plot steps.  Drawing the pictures (matplotlib) is not part of this
-package; `model.on_plot` (model.run) is where a caller hangs it."""
+package; `model.on_plot` (model.run) is where a caller hangs it.
+
+What the reference does with the evenly spaced grid is reduce it (postprocess/streamfunctions.py, stratification.py): `GridDiagnostics`
+does those reductions where the state lives - one fused pass (npg_fe_grid_integrals) generates, locates and evaluates every grid
+point and accumulates the vertical and the zonal trapezoids, and only the 2-D integrals cross to the host.  The same diagnostics
+from a `GridSamples` on the host (zonal_width, zonal_mean, overturning_streamfunction, average_stratification) are the reference's
+functions restated."""
 from __future__ import annotations
 
 import ctypes as C
@@ -280,3 +286,124 @@ def barotropic_streamfunction(samples: GridSamples):
     U[H == 0] = np.nan
     Psi[H == 0] = np.nan
     return Psi, U
+
+
+def _cumtrapz(f, x, axis):
+    """cumulative_trapezoid(f, x, axis=axis, initial=0)"""
+    f = np.moveaxis(f, axis, -1)
+    c = np.concatenate([np.zeros(f.shape[:-1] + (1,)), np.cumsum(0.5 * (f[..., 1:] + f[..., :-1]) * np.diff(x), axis=-1)], axis=-1)
+    return np.moveaxis(c, -1, axis)
+
+
+def _y_range(y, ymin, ymax):
+    """the rows iymin : iymax + 1 of average_stratification (postprocess/stratification.py:49-52)"""
+    return slice(int(np.searchsorted(y, ymin)), int(np.searchsorted(y, ymax)) + 1)
+
+
+def _ratio(a, b):
+    return np.divide(a, b, where=b != 0, out=np.full_like(a, np.nan))
+
+
+def zonal_width(samples: GridSamples):
+    """zonal_width of postprocess/utils.py:85-87: the zonal trapezoid of the valid mask, (ny, nz)"""
+    return _trapz(samples.valid.astype(float), x=samples.x, axis=0)
+
+
+def zonal_mean(field, samples: GridSamples, width=None):
+    """zonal_mean of postprocess/utils.py:90-94: the zonal trapezoid of a sampled scalar field (nx, ny, nz) (zero outside the mesh)
+    over the zonal width; NaN where the width is 0"""
+    width = zonal_width(samples) if width is None else width
+    return _ratio(_trapz(np.nan_to_num(field, nan=0.0), x=samples.x, axis=0), width)
+
+
+def overturning_streamfunction(samples: GridSamples):
+    """calculate_overturning_streamfunction of postprocess/streamfunctions.py:47-80 on sampled u and b: v_int = zonal trapezoid of
+    u_y, psi_bar(y, z) = -1/alpha int_{-H}^{z} v_int dz' with alpha = -z.min(), both NaN where the zonal width is 0; b_bar the zonal
+    mean of the full buoyancy.  Returns (psi_bar, v_int, b_bar)."""
+    width = zonal_width(samples)
+    v_int = _trapz(np.nan_to_num(samples["u"][..., 1], nan=0.0), x=samples.x, axis=0)
+    b_bar = zonal_mean(samples["b"], samples, width)
+    psi_bar = -1.0 / (-samples.z.min()) * _cumtrapz(v_int, samples.z, axis=1)
+    v_int[width == 0] = np.nan
+    psi_bar[width == 0] = np.nan
+    return psi_bar, v_int, b_bar
+
+
+def average_stratification(samples: GridSamples, ymin=-1, ymax=1, alpha=1.0):
+    """average_stratification of postprocess/stratification.py:45-62 on sampled grad b (ask sample_to_grid for fields=("u", "b",
+    "grad_b")): alpha d_z b, negative values and points outside the mesh set to 0, averaged horizontally over the rows ymin <= y <=
+    ymax (searchsorted bounds, as the reference takes them).  Returns the profile (nz,); NaN at levels without a valid point.  d_z b is
+    the pointwise derivative nan_eval(model, "grad_b") returns; alpha = params.alpha gives the reference's alpha*b_z."""
+    sl = _y_range(samples.y, ymin, ymax)
+    bz = np.where(samples.valid, np.nan_to_num(samples["grad_b"][..., 2], nan=0.0), 0.0)[:, sl, :]
+    bz = alpha * np.maximum(bz, 0.0)
+    mask = samples.valid[:, sl, :].astype(float)
+    area = _trapz(_trapz(mask, x=samples.x, axis=0), x=samples.y[sl], axis=0)
+    return _ratio(_trapz(_trapz(bz, x=samples.x, axis=0), x=samples.y[sl], axis=0), area)
+
+
+class GridIntegrals:
+    """What GridDiagnostics.compute() returns: the axes x, y, z and, finished on the host from the device's 2-D integrals,
+      count_z (nx, ny), count_x (ny, nz)   valid points per column / per zonal line (integers)
+      H, U, V, Psi (nx, ny)                depth, vertical integrals of u_x and u_y, barotropic streamfunction Psi = int_y^ymax U dy'
+                                           (calculate_barotropic_streamfunction); U, V, Psi are NaN where H = 0
+      width, v_int, w_int, b_bar, psi_bar (ny, nz)   zonal width, zonal integrals of u_y and u_z, zonal-mean full buoyancy and the
+                                           overturning streamfunction (calculate_overturning_streamfunction); NaN where width = 0
+      N2_bar(ymin, ymax) (nz,)             the horizontally averaged stratification (average_stratification)
+    col (4, nx, ny) and zon (6, ny, nz) are the raw integrals (zeros, not NaN, where nothing is valid)."""
+
+    def __init__(self, x, y, z, col, zon, alpha):
+        self.x, self.y, self.z, self.col, self.zon, self.alpha = x, y, z, col, zon, float(alpha)
+        self.count_z, self.count_x = np.rint(col[0]).astype(np.int64), np.rint(zon[0]).astype(np.int64)
+        self.H, self.width = col[1].copy(), zon[1].copy()
+        dry, closed = self.H == 0, self.width == 0
+        U, V = col[2].copy(), col[3].copy()
+        Psi = _trapz(U, x=y, axis=1)[:, None] - _cumtrapz(U, y, axis=1)
+        v_int, w_int = zon[2].copy(), zon[3].copy()
+        psi_bar = -1.0 / (-z.min()) * _cumtrapz(v_int, z, axis=1)
+        for a in (U, V, Psi):
+            a[dry] = np.nan
+        for a in (v_int, w_int, psi_bar):
+            a[closed] = np.nan
+        self.U, self.V, self.Psi, self.v_int, self.w_int, self.psi_bar = U, V, Psi, v_int, w_int, psi_bar
+        self.b_bar = _ratio(zon[4], self.width)
+
+    def N2_bar(self, ymin=-1, ymax=1):
+        """average_stratification (postprocess/stratification.py:45-62): params.alpha times the horizontal mean over ymin <= y <= ymax
+        (searchsorted bounds) of max(d_z b, 0), b the full buoyancy; NaN at levels without a valid point.  d_z b is the POINTWISE
+        derivative of the finite-element buoyancy, the one nan_eval(model, "grad_b") returns - not the nodally recovered field that
+        save_vtk writes as alpha*b_z and the reference samples."""
+        sl = _y_range(self.y, ymin, ymax)
+        area = _trapz(self.zon[1][sl], x=self.y[sl], axis=0)
+        return _ratio(self.alpha * _trapz(self.zon[5][sl], x=self.y[sl], axis=0), area)
+
+
+class GridDiagnostics:
+    """GridDiagnostics(model, nx=256, ny=256, nz=256, x=None, y=None, z=None): the streamfunctions, zonal means and the averaged
+    stratification of the model's CURRENT state on the grid x (x) y (x) z - by default the np.linspace grid over the mesh's bounding
+    box that sample_to_grid uses; an axis given explicitly (strictly increasing, at least 2 points; need not be uniform) replaces it.
+    The axes are uploaded once and the output vectors are kept: `.compute()` runs one fused pass on the device
+    (npg_fe_grid_integrals) and downloads 4 nx ny + 6 ny nz doubles.  Call it again after more timesteps - it is what an on_plot hook
+    calls."""
+
+    def __init__(self, model, nx=256, ny=256, nz=256, x=None, y=None, z=None):
+        _single_device(model)
+        self.model, self.loc = model, locator(model)
+        lo, hi = self.loc.bounding_box
+        given = (x, y, z)
+        self.x, self.y, self.z = (np.linspace(lo[a], hi[a], int(k)) if given[a] is None else L.as_f64(given[a]).ravel().copy()
+                                  for a, k in enumerate((nx, ny, nz)))
+        self.nx, self.ny, self.nz = len(self.x), len(self.y), len(self.z)
+        ctx = model.arch.ctx
+        self.fe = device_fe(model.arch, model.fe_data)
+        self._axes = DeviceVector.from_host(ctx, np.concatenate([self.x, self.y, self.z]))
+        self._col = DeviceVector(ctx, max(1, 4 * self.nx * self.ny))
+        self._zon = DeviceVector(ctx, max(1, 6 * self.ny * self.nz))
+
+    def compute(self) -> GridIntegrals:
+        m = self.model
+        L.check(L.lib().npg_fe_grid_integrals(self.fe.h, self.loc.h, m.inversion.solver.x.h, m.b_vec.h, float(m.params.N2),
+                                              self._axes.h, self.nx, self.ny, self.nz, self._col.h, self._zon.h))
+        col = self._col.to_host().reshape(4, self.nx, self.ny)
+        zon = self._zon.to_host().reshape(6, self.ny, self.nz)
+        return GridIntegrals(self.x, self.y, self.z, col, zon, m.params.alpha)
