@@ -480,6 +480,22 @@ int npg_fe_cfl_ratio(npg_fe *fe, const double *h_cells_host, double u_min, const
  * about one bin per cell.  A point belongs to the candidate of its bin with the largest min lambda, ties to the lowest cell
  * id, if that min lambda >= -1e-10; otherwise cell = -1 and lambda = NaN. */
 int npg_locator_create(npg_fe *fe, const double *anchor, int64_t nbins, npg_locator **out);
+/* The locator of ONE RANK of a partitioned mesh, from explicit cell records instead of the engine's cells: the cells the rank OWNS
+ * plus their witness layer - every cell sharing a geometric vertex with an owned cell (nupgcm_amd/partition.py,
+ * RankLayout.locator_cells).  geo12[ncell_loc][12] = {x0, G1, G2, G3} of each cell, engine_cell = its index in the
+ * rank's npg_fe cell tables (-1: a witness cell the engine does not hold), gid = its global cell id, distinct - the tie key: the
+ * election among the records is the serial one (largest min lambda, equal min lambda to the lowest GLOBAL id), owned = 1 where this
+ * rank reports the cell's points.  box6 = {lo[3], hi[3]}, the bounding box of the WHOLE mesh as npg_locator_box gives it (the one
+ * npg_locator_info of the one-device locator of that mesh reports); the bins cover it, those away from the rank's cells stay empty;
+ * nbins = 0: one bin per record.  npg_locator_find then stores the ENGINE cell index of a point whose winner is owned, and -1 / NaN
+ * both for a point outside the mesh and for one whose winner another rank owns; npg_fe_grid_integrals accumulates the owned points
+ * only.  Over the ranks every point is reported exactly once; the sum over ranks (npg_comm_allreduce_long) completes the result. */
+int npg_locator_create_cells(npg_ctx *ctx, const double *geo12, const int32_t *engine_cell, const int64_t *gid,
+                             const uint8_t *owned, int64_t ncell_loc, const double *box6, int64_t nbins, npg_locator **out);
+/* box6 = the bounding box npg_locator_create gives the mesh with grad_lambda[ncell][12] and anchor[ncell][3] (host arrays; no device) */
+int npg_locator_box(const double *grad_lambda, const double *anchor, int64_t ncell, double *box6);
+/* cell records held, how many of them are owned (all of them on a one-device locator), device bytes of records and bins (any may be NULL) */
+int npg_locator_cells(const npg_locator *loc, int64_t *nrecords, int64_t *nowned, int64_t *bytes);
 int npg_locator_destroy(npg_locator *loc);
 /* dims[3] bins per axis, box[6] = {lo[3], hi[3]}, total bin entries, longest candidate list (any may be NULL) */
 int npg_locator_info(const npg_locator *loc, int64_t *dims, double *box, int64_t *nentries, int64_t *max_per_bin);
@@ -498,6 +514,12 @@ int npg_locator_find(npg_locator *loc, const npg_vec *points, int64_t n, npg_loc
 /* out[n][ncomp] (a vector of ncomp n doubles) = the field at the located points; NaN in every component where cell = -1
  * (or a cell id outside the engine's cells).  Shape functions in closed form from lambda, local ordering of the DoF tables. */
 int npg_fe_sample(npg_fe *fe, int field, const npg_vec *vec, const npg_located *pts, npg_vec *out);
+/* Merging the point samples of the ranks of a partitioned model.  buf = [n][ncomp] values (npg_fe_sample wrote them) followed by n
+ * counts, ncomp = 0 .. 3.  mask: where pts holds cell = -1 the values become 0, and count = 1 where this rank reports the point, else
+ * 0.  After the sum over ranks (npg_comm_allreduce_long: one rank's value plus zeros - exact) unmask turns the values of the points
+ * with count 0 into NaN. */
+int npg_sample_mask(const npg_located *pts, int ncomp, npg_vec *buf);
+int npg_sample_unmask(int64_t n, int ncomp, npg_vec *buf);
 /* The reductions of the reference's post-processing (postprocess/utils.py:81-94, streamfunctions.py:14-80,
  * stratification.py:45-62) over the tensor grid x[nx] (x) y[ny] (x) z[nz], in one pass over the device-resident state: every
  * grid point is generated, located and evaluated (as npg_locator_find / npg_fe_sample would) and added to the trapezoid of its
@@ -521,6 +543,9 @@ int npg_comm_info(npg_ctx *ctx, char *buf, size_t cap);
 int npg_comm_disable_peer(npg_ctx *ctx);
 int npg_comm_allreduce_sum(npg_ctx *ctx, double *host_inout, int n);  /* tiny host-side helper for tests/bench */
 int npg_comm_allreduce_vec(npg_ctx *ctx, npg_vec *v);                 /* <= 32 doubles, in place, on the context's stream */
+/* any length, in place; in pieces of what the transport's window takes.  peer and shm windows: summed in rank order (the same bits
+ * on every rank, every call and both transports), synchronises with the host */
+int npg_comm_allreduce_long(npg_ctx *ctx, npg_vec *v);
 /* Replicate a row-block distributed vector on every rank: segment s of `full` ([global_off, global_off + len)) is owned
  * by rank seg_rank[s], who holds it at local[local_off ..].  One grouped ncclBroadcast per segment over xGMI. */
 int npg_comm_allgather_segments(npg_ctx *ctx, const npg_vec *local, int nseg, const int32_t *seg_rank,

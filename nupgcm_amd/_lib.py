@@ -151,6 +151,9 @@ def _declare(L, partial=False):
         "npg_fe_update_kappa_convection": [P, VP, D, D, D, D, P],
         "npg_fe_update_nu_eddy": [P, D, D, D, D, D, P], "npg_fe_restrict_coeff": [P, P, C.c_char_p], "npg_fe_coeff_cell_mean": [P, C.c_char_p, P], "npg_fe_cfl_ratio": [P, VP, D, P, C.POINTER(D)],
         "npg_locator_create": [P, VP, I64, PP], "npg_locator_destroy": [P],
+        "npg_locator_create_cells": [P, VP, VP, VP, VP, I64, VP, I64, PP], "npg_locator_box": [VP, VP, I64, VP],
+        "npg_locator_cells": [P, C.POINTER(I64), C.POINTER(I64), C.POINTER(I64)],
+        "npg_sample_mask": [P, C.c_int, P], "npg_sample_unmask": [I64, C.c_int, P], "npg_comm_allreduce_long": [P, P],
         "npg_locator_info": [P, VP, VP, C.POINTER(I64), C.POINTER(I64)],
         "npg_located_create": [P, I64, PP], "npg_located_destroy": [P], "npg_located_upload": [P, VP, VP],
         "npg_located_download": [P, VP, VP], "npg_locator_find": [P, P, I64, P], "npg_fe_sample": [P, C.c_int, P, P, P],

@@ -1168,6 +1168,26 @@ int npg::allreduce_big_device(npg_ctx *ctx, double *buf, int64_t n) {
     return peer_status(ctx);
 }
 
+// In-place sum over the ranks of a device vector of any length (the grid integrals and point samples of a partitioned model,
+// sampling.py): allreduce_big_device in pieces of what the transport's window takes.  peer and shm add the ranks' pieces in rank
+// order starting from 0.0, so both give the same bits and every call gives them again; RCCL chooses its own order.  Synchronises
+// with the host on peer and shm.
+NPG_API int npg_comm_allreduce_long(npg_ctx *ctx, npg_vec *v) {
+    NPG_REQUIRE(ctx && v && v->ctx == ctx && v->n >= 1, "npg_comm_allreduce_long: a vector of this context with at least 1 entry");
+    if (single_rank_shortcut(ctx)) return NPG_OK;
+    NPG_HIP(hipSetDevice(ctx->device));
+    size_t window = (size_t)1 << 30;
+    if (ctx->shm) window = ((ShmComm *)ctx->shm)->slot;
+    else if (!ctx->comm && ctx->peer) window = ((PeerComm *)ctx->peer)->stage_bytes;
+    const int64_t piece = (int64_t)std::min<size_t>(window, (size_t)1 << 30) / (int64_t)sizeof(double);
+    NPG_REQUIRE(piece >= 1, "npg_comm_allreduce_long: the transport's window holds no double");
+    for (int64_t i0 = 0; i0 < v->n; i0 += piece) {
+        int rc = allreduce_big_device(ctx, v->d + i0, std::min(piece, v->n - i0));
+        if (rc) return rc;
+    }
+    return NPG_OK;
+}
+
 bool npg::comm_is_kernel_only(const npg_ctx *ctx) { return ctx->peer != nullptr; }
 
 int npg::comm_check(const npg_ctx *ctx) { return ctx->peer ? peer_status(ctx) : NPG_OK; }

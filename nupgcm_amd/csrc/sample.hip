@@ -22,6 +22,7 @@
 
 namespace npg {
 
+template <bool PART>
 __global__ void __launch_bounds__(kBlock) k_locate(BinGrid g, const int32_t *__restrict__ bin_ptr,
                                                    const int32_t *__restrict__ bin_cells, const double *__restrict__ geo,
                                                    const double *__restrict__ pts, int64_t n, int32_t *__restrict__ cell,
@@ -31,7 +32,7 @@ __global__ void __launch_bounds__(kBlock) k_locate(BinGrid g, const int32_t *__r
     const double p[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
     int32_t c;
     double l[4];
-    locate_point(g, bin_ptr, bin_cells, geo, p, &c, l);
+    locate_point<PART>(g, bin_ptr, bin_cells, geo, p, &c, l);
     cell[i] = c;
     lam[4 * i] = l[0], lam[4 * i + 1] = l[1], lam[4 * i + 2] = l[2], lam[4 * i + 3] = l[3];
 }
@@ -71,7 +72,8 @@ __global__ void __launch_bounds__(kBlock) k_sample(DevTables t, const double *__
 
 // One workgroup: y index j = blockIdx.x / nchunk, x indices [kGridChunk * cx, ...) with cx = blockIdx.x % nchunk; thread t works
 // on z indices t, t + kBlock, ...  part[cx][channel][ny][nz], col[channel][nx][ny].
-template <int NB>
+// PART: the locator of one rank of a partitioned mesh - a point whose winner another rank owns counts as outside here.
+template <int NB, bool PART>
 __global__ void __launch_bounds__(kBlock) k_grid_integrals(BinGrid g, const int32_t *__restrict__ bin_ptr,
                                                            const int32_t *__restrict__ bin_cells, const double *__restrict__ geo,
                                                            DevTables t, const double *__restrict__ xu, const double *__restrict__ xb,
@@ -100,7 +102,7 @@ __global__ void __launch_bounds__(kBlock) k_grid_integrals(BinGrid g, const int3
             const double p[3] = {ax[i], y, z};
             int32_t c = -1;
             double l[4] = {0.0, 0.0, 0.0, 0.0};
-            if (in) locate_point(g, bin_ptr, bin_cells, geo, p, &c, l);
+            if (in) locate_point<PART>(g, bin_ptr, bin_cells, geo, p, &c, l);
             double v[kGridVal], term[kGridCol];
             grid_point_values(t, xu, xb, N2, z, c, l, v);
             grid_zon_add(trapezoid_weight(ax, nx, i), v, acc);
@@ -122,6 +124,24 @@ __global__ void __launch_bounds__(kBlock) k_grid_integrals(BinGrid g, const int3
     if (col_owner) col[((size_t)cch * nx + i0 + ci) * ny + j] = colacc;
 }
 
+// Merging the ranks' point samples (npg_sample_mask / npg_sample_unmask): buf = [n][nc] values, then n counts.  Before the sum over
+// ranks a point this rank does not report holds zeros and count 0; after it a point no rank reported (count 0) is NaN.
+__global__ void __launch_bounds__(kBlock) k_sample_mask(const int32_t *__restrict__ cell, int64_t n, int nc, double *__restrict__ buf) {
+    const int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x;
+    if (i >= n) return;
+    const bool mine = cell[i] >= 0;
+    if (!mine)
+        for (int a = 0; a < nc; ++a) buf[nc * i + a] = 0.0;
+    buf[(size_t)nc * n + i] = mine ? 1.0 : 0.0;
+}
+
+__global__ void __launch_bounds__(kBlock) k_sample_unmask(int64_t n, int nc, double *__restrict__ buf) {
+    const int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x;
+    if (i >= n) return;
+    if (buf[(size_t)nc * n + i] == 0.0)
+        for (int a = 0; a < nc; ++a) buf[nc * i + a] = __builtin_nan("");
+}
+
 __global__ void __launch_bounds__(kBlock) k_grid_fold(const double *__restrict__ part, int nchunk, int64_t n, double *__restrict__ zon) {
     const int64_t e = blockIdx.x * (int64_t)kBlock + threadIdx.x;
     if (e >= n) return;
@@ -136,7 +156,9 @@ using namespace npg;
 
 struct npg_locator {
     npg_ctx *ctx = nullptr;
-    int64_t ncell = 0;
+    int64_t ncell = 0;           // cells of the engine it serves; partitioned: 1 + the largest engine index among its records
+    bool part = false;           // npg_locator_create_cells: records = owned cells + witness layer (sample_core.h, locate_point<true>)
+    int64_t nrec = 0, nowned = 0;
     BinGrid grid{};
     int32_t *bin_ptr = nullptr, *bin_cells = nullptr;
     double *geo = nullptr;
@@ -163,6 +185,8 @@ NPG_API int npg_locator_destroy(npg_locator *loc) {
     return NPG_OK;
 }
 
+static int locator_upload(npg_locator *loc, const BinTables &bt, npg_locator **out);
+
 NPG_API int npg_locator_create(npg_fe *fe, const double *anchor, int64_t nbins, npg_locator **out) {
     NPG_REQUIRE(fe && anchor && out, "npg_locator_create: NULL argument");
     NPG_REQUIRE(nbins >= 0 && nbins <= ((int64_t)1 << 26), "npg_locator_create: nbins must be 0 (automatic) .. 2^26");
@@ -179,7 +203,50 @@ NPG_API int npg_locator_create(npg_fe *fe, const double *anchor, int64_t nbins, 
     NPG_REQUIRE(!err, "%s", err);
     npg_locator *loc = new npg_locator();
     loc->ctx = fe->ctx;
-    loc->ncell = nc;
+    loc->ncell = loc->nrec = loc->nowned = nc;
+    return locator_upload(loc, bt, out);
+}
+
+NPG_API int npg_locator_box(const double *grad_lambda, const double *anchor, int64_t ncell, double *box) {
+    NPG_REQUIRE(grad_lambda && anchor && box && ncell >= 1, "npg_locator_box: bad argument");
+    const char *err = mesh_box(grad_lambda, anchor, ncell, box);
+    NPG_REQUIRE(!err, "%s", err);
+    return NPG_OK;
+}
+
+NPG_API int npg_locator_create_cells(npg_ctx *ctx, const double *geo12, const int32_t *engine_cell, const int64_t *gid,
+                                     const uint8_t *owned, int64_t ncell_loc, const double *box6, int64_t nbins, npg_locator **out) {
+    NPG_REQUIRE(ctx && geo12 && engine_cell && gid && owned && box6 && out, "npg_locator_create_cells: NULL argument");
+    NPG_REQUIRE(ncell_loc >= 1 && ncell_loc < INT32_MAX, "npg_locator_create_cells: 1 .. 2^31 - 2 cells");
+    NPG_REQUIRE(nbins >= 0 && nbins <= ((int64_t)1 << 26), "npg_locator_create_cells: nbins must be 0 (automatic) .. 2^26");
+    // records in ascending global id: the kernel's tie on the record index is then the tie on the global cell id
+    std::vector<int64_t> order((size_t)ncell_loc);
+    for (int64_t c = 0; c < ncell_loc; ++c) order[(size_t)c] = c;
+    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return gid[a] < gid[b]; });
+    std::vector<double> geo((size_t)ncell_loc * 12);
+    std::vector<int32_t> eng((size_t)ncell_loc);
+    int64_t emax = -1, nowned = 0;
+    for (int64_t k = 0; k < ncell_loc; ++k) {
+        const int64_t c = order[(size_t)k];
+        NPG_REQUIRE(k == 0 || gid[c] > gid[order[(size_t)k - 1]], "npg_locator_create_cells: global cell id %lld given twice", (long long)gid[c]);
+        NPG_REQUIRE(engine_cell[c] >= -1, "npg_locator_create_cells: engine_cell must be an index or -1");
+        NPG_REQUIRE(!owned[c] || engine_cell[c] >= 0, "npg_locator_create_cells: an owned cell needs its index in the engine");
+        for (int j = 0; j < 12; ++j) geo[(size_t)k * 12 + j] = geo12[(size_t)c * 12 + j];
+        eng[(size_t)k] = owned[c] ? engine_cell[c] : -1;      // `owned` folded into the sign: the kernels read one number
+        if (owned[c]) emax = std::max<int64_t>(emax, engine_cell[c]), ++nowned;
+    }
+    NPG_HIP(hipSetDevice(ctx->device));
+    BinTables bt;
+    const char *err = build_bins_cells(geo.data(), eng.data(), ncell_loc, box6, nbins, bt);
+    NPG_REQUIRE(!err, "%s", err);
+    npg_locator *loc = new npg_locator();
+    loc->ctx = ctx;
+    loc->part = true;
+    loc->ncell = emax + 1, loc->nrec = ncell_loc, loc->nowned = nowned;
+    return locator_upload(loc, bt, out);
+}
+
+static int locator_upload(npg_locator *loc, const BinTables &bt, npg_locator **out) {
     loc->grid = bt.grid;
     loc->nentries = (int64_t)bt.bin_cells.size();
     loc->max_per_bin = bt.max_per_bin;
@@ -258,8 +325,12 @@ NPG_API int npg_locator_find(npg_locator *loc, const npg_vec *points, int64_t n,
     NPG_REQUIRE(points->ctx == loc->ctx && out->ctx == loc->ctx, "npg_locator_find: arguments of different contexts");
     if (n == 0) return NPG_OK;
     const int64_t grid = (n + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(k_locate, dim3((unsigned)grid), dim3(kBlock), 0, loc->ctx->stream, loc->grid, loc->bin_ptr,
-                       loc->bin_cells, loc->geo, points->d, n, out->cell, out->lam);
+    if (loc->part)
+        hipLaunchKernelGGL(k_locate<true>, dim3((unsigned)grid), dim3(kBlock), 0, loc->ctx->stream, loc->grid, loc->bin_ptr,
+                           loc->bin_cells, loc->geo, points->d, n, out->cell, out->lam);
+    else
+        hipLaunchKernelGGL(k_locate<false>, dim3((unsigned)grid), dim3(kBlock), 0, loc->ctx->stream, loc->grid, loc->bin_ptr,
+                           loc->bin_cells, loc->geo, points->d, n, out->cell, out->lam);
     NPG_HIP(hipGetLastError());
     return NPG_OK;
 }
@@ -298,7 +369,8 @@ NPG_API int npg_fe_grid_integrals(npg_fe *fe, npg_locator *loc, const npg_vec *x
     NPG_REQUIRE(nx <= 65536 && ny <= 65536 && nz <= 65536, "npg_fe_grid_integrals: at most 65536 points per axis");
     NPG_REQUIRE(loc->ctx == fe->ctx && x_inv->ctx == fe->ctx && b->ctx == fe->ctx && axes->ctx == fe->ctx && col->ctx == fe->ctx &&
                     zon->ctx == fe->ctx, "npg_fe_grid_integrals: arguments of different contexts");
-    NPG_REQUIRE(loc->ncell == fe->d.ncell, "npg_fe_grid_integrals: the locator was built for another mesh");
+    NPG_REQUIRE(loc->part ? loc->ncell <= fe->d.ncell : loc->ncell == fe->d.ncell,
+                "npg_fe_grid_integrals: the locator was built for another mesh");
     NPG_REQUIRE(x_inv->n == fe->n_inv, "npg_fe_grid_integrals: the flow vector has %lld entries, expected %lld", (long long)x_inv->n,
                 (long long)fe->n_inv);
     NPG_REQUIRE(b->n == fe->n_b, "npg_fe_grid_integrals: the buoyancy vector has %lld entries, expected %lld", (long long)b->n,
@@ -330,15 +402,47 @@ NPG_API int npg_fe_grid_integrals(npg_fe *fe, npg_locator *loc, const npg_vec *x
     const FeDev &d = fe->d;
     const DevTables t{d.cu, d.cp, d.cb, d.G, d.u_diri, d.b_diri, d.ncell, d.nb};
     const dim3 grid((unsigned)(ny * nchunk)), block(kBlock);
-#define NPG_GRID_LAUNCH(NB)                                                                                                      \
-    hipLaunchKernelGGL((k_grid_integrals<NB>), grid, block, 0, st, loc->grid, loc->bin_ptr, loc->bin_cells, loc->geo, t, x_inv->d, \
-                       b->d, N2, axes->d, (int)nx, (int)ny, (int)nz, (int)nchunk, col->d, loc->grid_part)
-    if (d.nb == 10) NPG_GRID_LAUNCH(10);
-    else NPG_GRID_LAUNCH(4);
+#define NPG_GRID_LAUNCH(NB, PART)                                                                                                \
+    hipLaunchKernelGGL((k_grid_integrals<NB, PART>), grid, block, 0, st, loc->grid, loc->bin_ptr, loc->bin_cells, loc->geo, t,    \
+                       x_inv->d, b->d, N2, axes->d, (int)nx, (int)ny, (int)nz, (int)nchunk, col->d, loc->grid_part)
+    if (d.nb == 10 && !loc->part) NPG_GRID_LAUNCH(10, false);
+    else if (!loc->part) NPG_GRID_LAUNCH(4, false);
+    else if (d.nb == 10) NPG_GRID_LAUNCH(10, true);
+    else NPG_GRID_LAUNCH(4, true);
 #undef NPG_GRID_LAUNCH
     NPG_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_grid_fold, dim3((unsigned)((nzon + kBlock - 1) / kBlock)), block, 0, st, loc->grid_part, (int)nchunk, nzon,
                        zon->d);
+    NPG_HIP(hipGetLastError());
+    return NPG_OK;
+}
+
+NPG_API int npg_locator_cells(const npg_locator *loc, int64_t *nrecords, int64_t *nowned, int64_t *bytes) {
+    NPG_REQUIRE(loc, "npg_locator_cells: NULL handle");
+    if (nrecords) *nrecords = loc->nrec;
+    if (nowned) *nowned = loc->nowned;
+    if (bytes) {
+        int64_t nbin = (int64_t)loc->grid.nb[0] * loc->grid.nb[1] * loc->grid.nb[2];
+        *bytes = loc->nrec * kGeoStride * (int64_t)sizeof(double) + (nbin + 1 + loc->nentries) * (int64_t)sizeof(int32_t);
+    }
+    return NPG_OK;
+}
+
+NPG_API int npg_sample_mask(const npg_located *pts, int ncomp, npg_vec *buf) {
+    NPG_REQUIRE(pts && buf && ncomp >= 0 && ncomp <= 3, "npg_sample_mask: bad argument");
+    NPG_REQUIRE(buf->n == pts->n * (ncomp + 1) && buf->ctx == pts->ctx, "npg_sample_mask: buf must hold (ncomp + 1) n doubles");
+    if (pts->n == 0) return NPG_OK;
+    hipLaunchKernelGGL(k_sample_mask, dim3((unsigned)((pts->n + kBlock - 1) / kBlock)), dim3(kBlock), 0, pts->ctx->stream,
+                       (const int32_t *)pts->cell, pts->n, ncomp, buf->d);
+    NPG_HIP(hipGetLastError());
+    return NPG_OK;
+}
+
+NPG_API int npg_sample_unmask(int64_t n, int ncomp, npg_vec *buf) {
+    NPG_REQUIRE(buf && n >= 0 && n <= ((int64_t)1 << 32) && ncomp >= 0 && ncomp <= 3 && buf->n == n * (ncomp + 1),
+                "npg_sample_unmask: buf must hold (ncomp + 1) n doubles");
+    if (n == 0 || ncomp == 0) return NPG_OK;
+    hipLaunchKernelGGL(k_sample_unmask, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, buf->ctx->stream, n, ncomp, buf->d);
     NPG_HIP(hipGetLastError());
     return NPG_OK;
 }

@@ -27,6 +27,7 @@
 namespace npg {
 
 constexpr int kGeoStride = 16;
+constexpr int kGeoEngine = 12;          // partitioned locators: record slot 12 = the cell's index in the rank's engine, -1 = not owned
 constexpr double kInsideTol = -1e-10;   // a point belongs to the mesh when the best candidate's min lambda is >= this
 
 struct BinGrid {
@@ -44,6 +45,11 @@ NPG_HD int32_t bin_coord(const BinGrid &g, int a, double x) {
 
 // The cell of point p: among the candidates of p's bin the one with the largest min lambda, ties to the lowest cell id.
 // cell = -1 and lambda = NaN when p lies outside the bounding box or the best min lambda is below kInsideTol.
+// PART: the locator of one rank of a partitioned mesh (build_bins_cells).  Its records are the rank's owned cells and their witness
+// layer in ascending GLOBAL cell id, so the tie on the record index is the tie on the global id; the election is the same, and the
+// winner's record then gives the cell's index in the rank's engine - or -1 when the winner is not owned here ("not mine": another
+// rank reports the point), which reads like a point outside the mesh.
+template <bool PART = false>
 NPG_HD void locate_point(const BinGrid &g, const int32_t *bin_ptr, const int32_t *bin_cells, const double *geo,
                          const double p[3], int32_t *cell, double lam[4]) {
     const double nan = std::numeric_limits<double>::quiet_NaN();
@@ -73,6 +79,10 @@ NPG_UNROLL
                 bl0 = l0, bl1 = l1, bl2 = l2, bl3 = l3;
             }
         }
+    }
+    if (PART && best >= 0) {
+        best = (int32_t)geo[(size_t)best * kGeoStride + kGeoEngine];
+        if (best < 0) bl0 = bl1 = bl2 = bl3 = nan;
     }
     *cell = best;
     lam[0] = bl0, lam[1] = bl1, lam[2] = bl2, lam[3] = bl3;
@@ -218,39 +228,38 @@ struct BinTables {
     int64_t max_per_bin = 0;
 };
 
-// G: grad lambda as [ncell][12] (component 3 k + a of cell c at G[12 c + 3 k + a]); anchor: [ncell][3]; nbins_target: 0 = one
-// bin per cell.  Returns an error text or nullptr.
-inline const char *build_bins(const double *G, const double *anchor, int64_t ncell, int64_t nbins_target, BinTables &out) {
-    out.geo.assign((size_t)ncell * kGeoStride, 0.0);
-    std::vector<double> clo((size_t)ncell * 3), chi((size_t)ncell * 3);
-    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int64_t c = 0; c < ncell; ++c) {
-        double *q = &out.geo[(size_t)c * kGeoStride];
-        const double *g = G + (size_t)c * 12 + 3;       // rows G1, G2, G3
-        for (int a = 0; a < 3; ++a) q[a] = anchor[(size_t)c * 3 + a];
-        for (int k = 0; k < 9; ++k) q[3 + k] = g[k];
-        // the edge vectors v_j - x0 are the columns of inverse([G1; G2; G3])
-        const double det = g[0] * (g[4] * g[8] - g[5] * g[7]) - g[1] * (g[3] * g[8] - g[5] * g[6]) + g[2] * (g[3] * g[7] - g[4] * g[6]);
-        if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) return "npg_locator_create: a cell has singular grad_lambda";
-        const double id = 1.0 / det;
-        const double E[3][3] = {
-            {(g[4] * g[8] - g[5] * g[7]) * id, (g[2] * g[7] - g[1] * g[8]) * id, (g[1] * g[5] - g[2] * g[4]) * id},
-            {(g[5] * g[6] - g[3] * g[8]) * id, (g[0] * g[8] - g[2] * g[6]) * id, (g[2] * g[3] - g[0] * g[5]) * id},
-            {(g[3] * g[7] - g[4] * g[6]) * id, (g[1] * g[6] - g[0] * g[7]) * id, (g[0] * g[4] - g[1] * g[3]) * id}};
-        for (int a = 0; a < 3; ++a) {
-            double mn = q[a], mx = q[a];
-            for (int j = 0; j < 3; ++j) {
-                const double v = q[a] + E[a][j];
-                if (!std::isfinite(v)) return "npg_locator_create: non-finite cell geometry";
-                mn = std::min(mn, v), mx = std::max(mx, v);
-            }
-            // a point accepted at min lambda >= -1e-10 lies within 1e-10 cell extents of the cell: 1e-6 covers it and the rounding
-            // of the reconstructed vertices
-            const double pad = 1e-6 * (mx - mn);
-            clo[(size_t)c * 3 + a] = mn - pad, chi[(size_t)c * 3 + a] = mx + pad;
-            lo[a] = std::min(lo[a], mn), hi[a] = std::max(hi[a], mx);
+// One cell's record q = {x0, G1, G2, G3} from its anchor x0 and the rows g = {G1, G2, G3}, its padded bounding box clo / chi, and
+// lo / hi widened by its (unpadded) extent.  Every bounding box in this file comes from here, so a mesh has ONE box whoever asks.
+inline const char *cell_record(const double *x0, const double *g, double *q, double *clo, double *chi, double lo[3], double hi[3]) {
+    for (int a = 0; a < 3; ++a) q[a] = x0[a];
+    for (int k = 0; k < 9; ++k) q[3 + k] = g[k];
+    // the edge vectors v_j - x0 are the columns of inverse([G1; G2; G3])
+    const double det = g[0] * (g[4] * g[8] - g[5] * g[7]) - g[1] * (g[3] * g[8] - g[5] * g[6]) + g[2] * (g[3] * g[7] - g[4] * g[6]);
+    if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) return "npg_locator_create: a cell has singular grad_lambda";
+    const double id = 1.0 / det;
+    const double E[3][3] = {
+        {(g[4] * g[8] - g[5] * g[7]) * id, (g[2] * g[7] - g[1] * g[8]) * id, (g[1] * g[5] - g[2] * g[4]) * id},
+        {(g[5] * g[6] - g[3] * g[8]) * id, (g[0] * g[8] - g[2] * g[6]) * id, (g[2] * g[3] - g[0] * g[5]) * id},
+        {(g[3] * g[7] - g[4] * g[6]) * id, (g[1] * g[6] - g[0] * g[7]) * id, (g[0] * g[4] - g[1] * g[3]) * id}};
+    for (int a = 0; a < 3; ++a) {
+        double mn = q[a], mx = q[a];
+        for (int j = 0; j < 3; ++j) {
+            const double v = q[a] + E[a][j];
+            if (!std::isfinite(v)) return "npg_locator_create: non-finite cell geometry";
+            mn = std::min(mn, v), mx = std::max(mx, v);
         }
+        // a point accepted at min lambda >= -1e-10 lies within 1e-10 cell extents of the cell: 1e-6 covers it and the rounding
+        // of the reconstructed vertices
+        const double pad = 1e-6 * (mx - mn);
+        clo[a] = mn - pad, chi[a] = mx + pad;
+        lo[a] = std::min(lo[a], mn), hi[a] = std::max(hi[a], mx);
     }
+    return nullptr;
+}
+
+// The bins of ncell cells with the padded boxes clo / chi over the bounding box lo .. hi, about `target` bins in all
+inline const char *fill_bins(const double lo[3], const double hi[3], const std::vector<double> &clo, const std::vector<double> &chi,
+                             int64_t ncell, double target, BinTables &out) {
     BinGrid &gr = out.grid;
     double ext[3], vol = 1.0;
     for (int a = 0; a < 3; ++a) {
@@ -258,7 +267,6 @@ inline const char *build_bins(const double *G, const double *anchor, int64_t nce
         if (!(ext[a] > 0.0)) return "npg_locator_create: the mesh's bounding box is flat";
         vol *= ext[a];
     }
-    const double target = (double)(nbins_target > 0 ? nbins_target : ncell);
     const double s = std::cbrt(vol / target);           // cubic bins
     int64_t total = 1;
     for (int a = 0; a < 3; ++a) {
@@ -299,6 +307,52 @@ inline const char *build_bins(const double *G, const double *anchor, int64_t nce
                     out.bin_cells[(size_t)next[(size_t)(((int64_t)z * gr.nb[1] + y) * gr.nb[0] + x)]++] = (int32_t)c;
     }
     return nullptr;
+}
+
+// G: grad lambda as [ncell][12] (component 3 k + a of cell c at G[12 c + 3 k + a]); anchor: [ncell][3]; nbins_target: 0 = one
+// bin per cell.  Returns an error text or nullptr.
+inline const char *build_bins(const double *G, const double *anchor, int64_t ncell, int64_t nbins_target, BinTables &out) {
+    out.geo.assign((size_t)ncell * kGeoStride, 0.0);
+    std::vector<double> clo((size_t)ncell * 3), chi((size_t)ncell * 3);
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int64_t c = 0; c < ncell; ++c) {
+        const char *err = cell_record(anchor + (size_t)c * 3, G + (size_t)c * 12 + 3, &out.geo[(size_t)c * kGeoStride],
+                                      &clo[(size_t)c * 3], &chi[(size_t)c * 3], lo, hi);
+        if (err) return err;
+    }
+    return fill_bins(lo, hi, clo, chi, ncell, (double)(nbins_target > 0 ? nbins_target : ncell), out);
+}
+
+// The bounding box build_bins gives a mesh, {lo[3], hi[3]}, without the bins
+inline const char *mesh_box(const double *G, const double *anchor, int64_t ncell, double box[6]) {
+    double q[kGeoStride], clo[3], chi[3];
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int64_t c = 0; c < ncell; ++c) {
+        const char *err = cell_record(anchor + (size_t)c * 3, G + (size_t)c * 12 + 3, q, clo, chi, lo, hi);
+        if (err) return err;
+    }
+    for (int a = 0; a < 3; ++a) box[a] = lo[a], box[3 + a] = hi[a];
+    return nullptr;
+}
+
+// The bins of one rank of a partitioned mesh: ncell explicit records geo12 = {x0, G1, G2, G3}, given in ascending global cell id,
+// engine[c] = the cell's index in the rank's engine where the rank owns it, -1 otherwise (stored in record slot kGeoEngine), over
+// the GLOBAL bounding box `box` (mesh_box of the whole mesh): points are binned as the one-device locator bins them, and bins
+// away from the rank's cells stay empty.  nbins_target: 0 = one bin per record.
+inline const char *build_bins_cells(const double *geo12, const int32_t *engine, int64_t ncell, const double box[6],
+                                    int64_t nbins_target, BinTables &out) {
+    out.geo.assign((size_t)ncell * kGeoStride, 0.0);
+    std::vector<double> clo((size_t)ncell * 3), chi((size_t)ncell * 3);
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int64_t c = 0; c < ncell; ++c) {
+        double *q = &out.geo[(size_t)c * kGeoStride];
+        const char *err = cell_record(geo12 + (size_t)c * 12, geo12 + (size_t)c * 12 + 3, q, &clo[(size_t)c * 3], &chi[(size_t)c * 3], lo, hi);
+        if (err) return err;
+        q[kGeoEngine] = (double)engine[c];
+    }
+    for (int a = 0; a < 3; ++a)
+        if (!(lo[a] >= box[a] && hi[a] <= box[3 + a])) return "npg_locator_create_cells: a cell lies outside the bounding box given";
+    return fill_bins(box, box + 3, clo, chi, ncell, (double)(nbins_target > 0 ? nbins_target : ncell), out);
 }
 
 }  // namespace npg

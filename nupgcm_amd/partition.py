@@ -150,6 +150,15 @@ class RankLayout:
         c_b = mine_b[np.where(b_ids >= 0, b_ids, -1)].any(axis=1)
         self.cells = np.nonzero(c_inv | c_b)[0]
         self.n_cells_inv, self.n_cells_b = int(c_inv.sum()), int(c_b.sum())
+        # owner of a CELL (sampling: which rank reports a point that lies in it): the lowest rank among the owners of its free
+        # inversion and buoyancy DoFs - each of those ranks keeps the cell (it touches one of its rows), so the owner always holds the
+        # cell's tables and, after refresh_ghosts, its values.  A cell without any free DoF is given to rank 0 (see locator_cells).
+        big = np.iinfo(np.int32).max
+        o_i = np.where(inv_ids >= 0, own_inv[np.maximum(inv_ids, 0)], big).min(axis=1)
+        o_b = np.where(b_ids >= 0, own_b[np.maximum(b_ids, 0)], big).min(axis=1)
+        self.cell_owner = np.minimum(o_i, o_b)
+        self.cell_owner[self.cell_owner == big] = 0
+        self.cell_owner = self.cell_owner.astype(np.int32)
 
         def layout(ids, c_rows, owned, owner, n):
             sol = np.unique(ids[c_rows][ids[c_rows] >= 0])
@@ -193,6 +202,25 @@ class RankLayout:
         np.logical_or.at(node_bnd, inv, row_bnd)
         order = np.lexsort((owned, node_bnd[inv], cls))                       # class, then interior before boundary, then global id
         return owned[order]
+
+    def locator_cells(self, fe_data):
+        """(cells, owned): the cells of this rank's point locator, ascending global ids, and the mask of the ones it OWNS
+        (cell_owner == rank).  The others are the WITNESS layer: every cell that shares at least one geometric vertex
+        (mesh.cell_geo - where the cell lies, not the periodic master of its vertices) with an owned cell.  Witness cells carry
+        geometry only and are never evaluated; they take part in the election of a point's cell (largest min lambda, ties to the lowest
+        global id) so that every rank that could report a point sees every cell that accepts it, and a point is reported only where
+        the winner is owned - exactly once over the ranks.
+        Cells without a free DoF belong to rank 0.  No rank keeps such a cell (RankLayout.cells lists cells that touch an owned row),
+        so it could not be evaluated; the choice made here is to ASSERT that every owned cell is kept - true of every mesh of this
+        project, whose pressure space pins one vertex at most - rather than to add Dirichlet-only cells to rank 0's engine."""
+        cg = fe_data.mesh.cell_geo
+        own = self.cell_owner == self.rank
+        assert np.isin(np.nonzero(own)[0], self.cells, assume_unique=True).all(), \
+            "a cell without free DoFs is owned by rank 0 but kept by no rank: sampling cannot evaluate it"
+        touched = np.zeros(int(cg.max()) + 1, dtype=bool)
+        touched[cg[own].ravel()] = True
+        cells = np.nonzero(touched[cg].any(axis=1))[0]
+        return cells, own[cells]
 
     def ghost_nodes(self, fe_data):
         """(first local column, components) of every velocity NODE among this rank's solver ghosts whose components are all ghosts

@@ -29,23 +29,42 @@ _trapz = getattr(np, "trapezoid", None) or np.trapz
 CHUNK = 1 << 21          # points located / evaluated per call by sample_to_grid: ~150 MB of device memory at a time
 
 
-def _single_device(model):
-    if getattr(model, "partition", None) is not None or getattr(model, "comm", None) is not None \
-            or getattr(model.arch.ctx, "nranks", 1) > 1:
-        raise NotImplementedError("sampling a partitioned / distributed model is not implemented: every rank holds a part of "
-                                  "the state only; sample a single-device model (or a checkpoint loaded into one)")
+def _partitioned(model):
+    """The dispatch of every entry point: False for a single-device model, True for a mesh-partitioned one
+    (partition.PartitionedModel), whose ranks then call the entry point COLLECTIVELY - the same arguments on every rank, the same
+    complete result on every rank.  The replicated layout of distributed.py and 2-D meshes are refused."""
     if getattr(model.fe_data.mesh, "dim", 3) != 3:
         raise NotImplementedError("sampling is implemented for tetrahedral (3-D) meshes")
+    if getattr(model, "layout", None) is not None and hasattr(model.layout, "locator_cells"):
+        return True
+    if getattr(model, "partition", None) is not None or getattr(model, "comm", None) is not None \
+            or getattr(model.arch.ctx, "nranks", 1) > 1:
+        raise NotImplementedError("sampling the replicated distributed layout is not implemented: use the mesh-partitioned model "
+                                  "(partition.partitioned_model), whose ranks sample collectively, or a single-device model")
+    return False
+
+
+def _engine(model):
+    """the assembly engine whose DoF tables the samples are evaluated through: the rank's own on a partitioned model"""
+    return model.fe if _partitioned(model) else device_fe(model.arch, model.fe_data)
+
+
+def _allreduce(ctx, vec):
+    L.check(L.lib().npg_comm_allreduce_long(ctx.h, vec.h))
 
 
 class Located:
     """n located points on the device (npg_located): the cell id of each (-1 outside the mesh) and its barycentric coordinates
-    there.  The reference's evaluation `cache`."""
+    there.  The reference's evaluation `cache`.
+    On a partitioned model every rank holds its own: `cells` and `lambdas` are RANK-LOCAL (the index of the cell in the rank's
+    engine where this rank reports the point; -1 / NaN elsewhere - outside the mesh or another rank's point), `valid` is the mask
+    merged over the ranks."""
 
-    def __init__(self, ctx, n):
+    def __init__(self, ctx, n, collective=False):
         h = C.c_void_p()
         L.check(L.lib().npg_located_create(ctx.h, int(n), C.byref(h)))
         self.h, self.ctx, self.n = h, ctx, int(n)
+        self.collective, self._valid = bool(collective), None
 
     @classmethod
     def from_host(cls, ctx, cells, lambdas):
@@ -70,34 +89,61 @@ class Located:
 
     @property
     def cells(self):
+        """cell ids, -1 outside the mesh.  Partitioned model: rank-local (see the class)"""
         c = np.empty(self.n, dtype=np.int32)
         L.check(L.lib().npg_located_download(self.h, L.ptr(c), None))
         return c
 
     @property
     def lambdas(self):
+        """barycentric coordinates (n, 4), NaN outside the mesh.  Partitioned model: rank-local (see the class)"""
         lam = np.empty((self.n, 4))
         L.check(L.lib().npg_located_download(self.h, None, L.ptr(lam)))
         return lam
 
     @property
     def valid(self):
-        """mask of the points that lie in the mesh (downloaded on request)"""
-        return self.cells >= 0
+        """mask of the points that lie in the mesh (downloaded on request).  Partitioned model: the mask merged over the ranks - the
+        FIRST read is collective (every rank must make it), later reads return the kept mask"""
+        if not self.collective:
+            return self.cells >= 0
+        if self._valid is None:
+            cnt = DeviceVector(self.ctx, max(1, self.n))
+            if self.n:
+                L.check(L.lib().npg_sample_mask(self.h, 0, cnt.h))
+                _allreduce(self.ctx, cnt)
+            self._valid = cnt.to_host()[:self.n] > 0.0
+        return self._valid
 
 
 class PointLocator:
     """PointLocator(model, nbins=0): the point search of one mesh on the model's architecture.  nbins = 0 chooses about one bin
-    per cell.  `.locate(points)` -> Located."""
+    per cell.  `.locate(points)` -> Located.
+    On a partitioned model the rank's locator holds the cells it owns and their witness layer (RankLayout.locator_cells) over the
+    bounding box and the bin size of the WHOLE mesh; a point is found where the elected cell is owned by this rank, so over the
+    ranks it is found exactly once."""
 
     def __init__(self, model, nbins=0):
-        _single_device(model)
+        self.collective = _partitioned(model)
         m = model.fe_data.mesh
-        self.ctx, self.fe = model.arch.ctx, device_fe(model.arch, model.fe_data)
+        self.ctx, self.fe = model.arch.ctx, _engine(model)
         # each cell's OWN first vertex: across a periodic seam a cell lies where its geometry says, not where its vertices' masters do
         anchor = L.as_f64(m.geo_coords[m.cell_geo[:, 0]])
         h = C.c_void_p()
-        L.check(L.lib().npg_locator_create(self.fe.h, L.ptr(anchor), int(nbins), C.byref(h)))
+        if self.collective:
+            lay = model.layout
+            cells, owned = lay.locator_cells(model.fe_data)
+            pos = np.minimum(np.searchsorted(lay.cells, cells), len(lay.cells) - 1)
+            engine = np.where(lay.cells[pos] == cells, pos, -1).astype(np.int32)     # witness cells the rank does not keep: -1
+            G = L.as_f64(m.grad_lambda).reshape(m.ncell, 12)
+            geo12 = L.as_f64(np.concatenate([anchor[cells], G[cells, 3:]], axis=1))
+            box = np.zeros(6)
+            L.check(L.lib().npg_locator_box(L.ptr(G), L.ptr(anchor), int(m.ncell), L.ptr(box)))   # the box of the serial locator
+            gid, own8 = L.as_i64(cells), np.ascontiguousarray(owned, dtype=np.uint8)
+            L.check(L.lib().npg_locator_create_cells(self.ctx.h, L.ptr(geo12), L.ptr(engine), L.ptr(gid), L.ptr(own8), len(cells),
+                                                     L.ptr(box), int(nbins) or int(m.ncell), C.byref(h)))
+        else:
+            L.check(L.lib().npg_locator_create(self.fe.h, L.ptr(anchor), int(nbins), C.byref(h)))
         self.h = h
 
     def __del__(self):
@@ -113,8 +159,13 @@ class PointLocator:
         dims, box = np.zeros(3, dtype=np.int64), np.zeros(6)
         ne, mx = C.c_int64(), C.c_int64()
         L.check(L.lib().npg_locator_info(self.h, L.ptr(dims), L.ptr(box), C.byref(ne), C.byref(mx)))
-        return dict(dims=tuple(int(v) for v in dims), lo=box[:3].copy(), hi=box[3:].copy(), entries=ne.value,
-                    mean_per_bin=ne.value / float(np.prod(dims)), max_per_bin=mx.value)
+        out = dict(dims=tuple(int(v) for v in dims), lo=box[:3].copy(), hi=box[3:].copy(), entries=ne.value,
+                   mean_per_bin=ne.value / float(np.prod(dims)), max_per_bin=mx.value)
+        if self.collective:          # this rank's share: cell records held, the owned ones among them, device bytes of records and bins
+            nr, no, nb = C.c_int64(), C.c_int64(), C.c_int64()
+            L.check(L.lib().npg_locator_cells(self.h, C.byref(nr), C.byref(no), C.byref(nb)))
+            out.update(cells=nr.value, owned=no.value, witness=nr.value - no.value, bytes=nb.value)
+        return out
 
     @property
     def bounding_box(self):
@@ -123,7 +174,7 @@ class PointLocator:
 
     def locate(self, points) -> Located:
         pts = L.as_f64(points).reshape(-1, 3)
-        out = Located(self.ctx, len(pts))
+        out = Located(self.ctx, len(pts), self.collective)
         if len(pts):
             pv = DeviceVector.from_host(self.ctx, pts.ravel())
             L.check(L.lib().npg_locator_find(self.h, pv.h, len(pts), out.h))
@@ -131,7 +182,7 @@ class PointLocator:
 
 
 def locator(model) -> PointLocator:
-    """the model's point locator, built on first use"""
+    """the model's point locator, built on first use (a partitioned model: the rank's, from its layout)"""
     loc = model.__dict__.get("_point_locator")
     if loc is None:
         loc = model.__dict__["_point_locator"] = PointLocator(model)
@@ -140,12 +191,23 @@ def locator(model) -> PointLocator:
 
 def _evaluate(model, field, located: Located):
     code, nc = _FIELDS[field]
-    fe = device_fe(model.arch, model.fe_data)
+    fe = _engine(model)
     vec = model.b_vec if field in ("b", "grad_b") else model.inversion.solver.x
-    out = DeviceVector(model.arch.ctx, max(1, located.n * nc))
     if located.n == 0:
         return np.empty((0, nc) if nc > 1 else (0,))
-    L.check(L.lib().npg_fe_sample(fe.h, code, vec.h, located.h, out.h))
+    if _partitioned(model):
+        # every rank evaluates the points it reports and contributes zeros elsewhere; a count per point is summed alongside.  One
+        # contributor per point: the sum is that rank's value, exactly.  Merged on the device, downloaded once.
+        n = located.n
+        buf = DeviceVector(model.arch.ctx, n * (nc + 1))
+        out = buf.view(0, n * nc)
+        L.check(L.lib().npg_fe_sample(fe.h, code, vec.h, located.h, out.h))
+        L.check(L.lib().npg_sample_mask(located.h, nc, buf.h))
+        _allreduce(model.arch.ctx, buf)
+        L.check(L.lib().npg_sample_unmask(n, nc, buf.h))
+    else:
+        out = DeviceVector(model.arch.ctx, max(1, located.n * nc))
+        L.check(L.lib().npg_fe_sample(fe.h, code, vec.h, located.h, out.h))
     a = out.to_host()
     return a.reshape(-1, nc) if nc > 1 else a
 
@@ -154,8 +216,9 @@ def nan_eval(model, field, points, cache: Located = None, perturbation=False):
     """nan_eval(u, x) of src/plotting.jl:9-31 for the model's fields: field "u" (n, 3), "p" (n,), "b" (n,), "grad_b" (n, 3) at
     points (n, 3), NaN outside the mesh.  "b" is the full buoyancy N2 z + b' and "grad_b" its gradient (N2 added to the z
     component), as save_vtk / plot_slice show it; perturbation=True returns b' / grad b' alone.  cache: the `Located` of an earlier
-    call on the same points (returned by PointLocator.locate) - the points are then not searched again."""
-    _single_device(model)
+    call on the same points (returned by PointLocator.locate) - the points are then not searched again.
+    Collective on a partitioned model (every rank: the same points, the same complete result)."""
+    _partitioned(model)
     if field not in _FIELDS:
         raise ValueError(f"nan_eval: field must be one of {sorted(_FIELDS)}, got {field!r}")
     pts = L.as_f64(points).reshape(-1, 3)
@@ -242,8 +305,9 @@ def sample_to_grid(model, nx=256, ny=256, nz=256, fields=("u", "b"), chunk=CHUNK
     """sample_to_grid of postprocess/utils.py:48-78 without the VTK round trip: nx x ny x nz evenly spaced points over the mesh's
     bounding box, located and evaluated on the device.  The grid is worked through in chunks of `chunk` points (default 2^21), so the
     extra device memory stays near 72 bytes per chunk point (coordinates, cell ids, lambdas, one field) - about 150 MB - whatever
-    the grid; the result lives on the host."""
-    _single_device(model)
+    the grid; the result lives on the host.  On a partitioned model (collective) every chunk is merged over the ranks before the
+    next one starts: one more vector of (components + 1) doubles per chunk point, 32 bytes for u."""
+    _partitioned(model)
     loc = locator(model)
     lo, hi = loc.bounding_box
     x, y, z = (np.linspace(lo[a], hi[a], k) for a, k in enumerate((nx, ny, nz)))
@@ -384,10 +448,13 @@ class GridDiagnostics:
     box that sample_to_grid uses; an axis given explicitly (strictly increasing, at least 2 points; need not be uniform) replaces it.
     The axes are uploaded once and the output vectors are kept: `.compute()` runs one fused pass on the device
     (npg_fe_grid_integrals) and downloads 4 nx ny + 6 ny nz doubles.  Call it again after more timesteps - it is what an on_plot hook
-    calls."""
+    calls.
+    On a partitioned model `compute()` is collective: each rank integrates the grid points it owns and the 2-D integrals are summed
+    over the ranks in rank order - the same bits on every rank and every call; the counts are exact, the integrals differ from the
+    single-device ones by the re-association of each sum into per-rank partial sums."""
 
     def __init__(self, model, nx=256, ny=256, nz=256, x=None, y=None, z=None):
-        _single_device(model)
+        self.collective = _partitioned(model)
         self.model, self.loc = model, locator(model)
         lo, hi = self.loc.bounding_box
         given = (x, y, z)
@@ -395,15 +462,21 @@ class GridDiagnostics:
                                   for a, k in enumerate((nx, ny, nz)))
         self.nx, self.ny, self.nz = len(self.x), len(self.y), len(self.z)
         ctx = model.arch.ctx
-        self.fe = device_fe(model.arch, model.fe_data)
+        self.fe = _engine(model)
         self._axes = DeviceVector.from_host(ctx, np.concatenate([self.x, self.y, self.z]))
-        self._col = DeviceVector(ctx, max(1, 4 * self.nx * self.ny))
-        self._zon = DeviceVector(ctx, max(1, 6 * self.ny * self.nz))
+        ncol, nzon = max(1, 4 * self.nx * self.ny), max(1, 6 * self.ny * self.nz)
+        if self.collective:
+            self._out = DeviceVector(ctx, ncol + nzon)      # [col | zon]: one vector, so that the ranks' sum is one collective
+            self._col, self._zon = self._out.view(0, ncol), self._out.view(ncol, nzon)
+        else:
+            self._col, self._zon = DeviceVector(ctx, ncol), DeviceVector(ctx, nzon)
 
     def compute(self) -> GridIntegrals:
         m = self.model
         L.check(L.lib().npg_fe_grid_integrals(self.fe.h, self.loc.h, m.inversion.solver.x.h, m.b_vec.h, float(m.params.N2),
                                               self._axes.h, self.nx, self.ny, self.nz, self._col.h, self._zon.h))
+        if self.collective:
+            _allreduce(m.arch.ctx, self._out)               # each rank integrated the points it owns: summed in rank order
         col = self._col.to_host().reshape(4, self.nx, self.ny)
         zon = self._zon.to_host().reshape(6, self.ny, self.nz)
         return GridIntegrals(self.x, self.y, self.z, col, zon, m.params.alpha)
