@@ -97,6 +97,10 @@ struct GDev {
     // the system is distributed over several GPUs
     const double *Q1, *Q2, *QR;
     int nQ1, nQ2, nQR;
+    int onefold;          // one GPU, split mode, fast instances: the dots kernel's partial rows are summed ONCE (k_gmres_fold_first)
+                          // into the row Q1 points at, which also takes hcol1 / wnorm2 out of the orthogonalisation kernel
+    int vdots;            // ... and, with the fp32-stored basis, column j is formed where it is first read: the dots kernel of
+                          // step j computes it from wt and T[j].beta and stores it, the Arnoldi kernel's epilogue stores w only
     Snap *C, *T;
     double *c, *s, *z, *R, *hcol1, *wnorm2;
     double *hist;
@@ -385,7 +389,8 @@ __global__ void __launch_bounds__(kKB, FUSED ? 4 : 6) k_gmres_arnoldi(GDev d, in
         // (a tile has at most kTileRows <= kKB rows: one row per thread)
         static_assert(kTileRows <= kKB, "one epilogue row per thread");
         double wt_row = 0.0;
-        if (!FUSED && (int)threadIdx.x < td.nrows) wt_row = d.wt[td.r0 + threadIdx.x];
+        // (vdots: the basis column is formed by the dots kernel - neither this load nor the column's store below)
+        if (!FUSED && !d.vdots && (int)threadIdx.x < td.nrows) wt_row = d.wt[td.r0 + threadIdx.x];
         // one instantiation for both cases: without a second pass the correction loop has no trips
         if constexpr (WL != 0) {
             if (td.nw) {
@@ -416,14 +421,16 @@ __global__ void __launch_bounds__(kKB, FUSED ? 4 : 6) k_gmres_arnoldi(GDev d, in
             if (r < nr) {
                 const int row = r0 + r;
                 d.w[row] = sw[r] * inv_beta * precond_row(d, row);
-                double tv = wt_row;
-                if (ro)
-                    for (int q = 0; q < j; ++q)
-                        tv -= sh.h2[q] * (d.Vf ? (double)d.Vf[vidx(row, q, d.n, d.ldv)] : d.Vi[vidx(row, q, d.n, d.ldv)]);
-                if (d.Vf)
-                    d.Vf[vidx(row, j, d.n, d.ldv)] = (float)(tv * inv_beta);
-                else
-                    d.Vi[vidx(row, j, d.n, d.ldv)] = tv * inv_beta;
+                if (!d.vdots) {
+                    double tv = wt_row;
+                    if (ro)
+                        for (int q = 0; q < j; ++q)
+                            tv -= sh.h2[q] * (d.Vf ? (double)d.Vf[vidx(row, q, d.n, d.ldv)] : d.Vi[vidx(row, q, d.n, d.ldv)]);
+                    if (d.Vf)
+                        d.Vf[vidx(row, j, d.n, d.ldv)] = (float)(tv * inv_beta);
+                    else
+                        d.Vi[vidx(row, j, d.n, d.ldv)] = tv * inv_beta;
+                }
             }
             continue;
         }
@@ -462,8 +469,9 @@ __global__ void __launch_bounds__(kKB, FUSED ? 4 : 6) k_gmres_arnoldi(GDev d, in
 
 // ---- row-streaming kernels (split mode) -----------------------------------------------------------------------------------
 // One thread per row, consecutive lanes = consecutive rows: every basis column in use is one coalesced 8-byte stream and
-// every thread keeps 8*NG accumulators (NG = groups of eight columns, a template parameter).  On one GPU the consumer kernels reduce the partial rows themselves
-// (at most kMaxG rows); distributed runs fold them to one row first (k_reduce_rows) for the all-reduce.
+// every thread keeps 8*NG accumulators (NG = groups of eight columns, a template parameter).  On one GPU the fast instances' first-pass rows
+// are folded to one row by k_gmres_fold_first and every other consumer reduces the partial rows itself (at most kMaxG rows);
+// distributed runs fold them to one row first (k_reduce_rows) for the all-reduce.
 constexpr int kRB = 256;
 constexpr int kMaxRowsI = kMaxG / (kRB / 32);      // chunks of reduce_partials over at most kMaxG partial rows
 
@@ -523,10 +531,13 @@ __device__ __forceinline__ void load_row_pair_cols(const float *__restrict__ Vf,
 // loads row 0 instead (no lane-varying branch around the loads) and gets zero weights.  The kernels issue trip t + 1's loads
 // BEFORE trip t's arithmetic: with three waves per SIMD and one dependent round trip per loop trip the plain loop streamed at
 // 3.9 TB/s, the software-pipelined one at 5.5-6.9 TB/s (tools/rows_bench.hip, profiles/r03_rows_bench.txt).
-template <int NG>
+// VD (the dots kernel with GDev::vdots): column j does not exist yet - the trip loads the rows' wt pair instead (one more 16-byte
+// load) and the kernel forms the column's entries from it.
+template <int NG, bool VD = false>
 struct RowPair {
     float2 v[8 * NG];
     double w0, w1;
+    double2 t;            // (VD) wt of the two rows
     int64_t r0;
     bool valid, two;
     __device__ __forceinline__ void load(const GDev &d, int64_t blk, int j) {
@@ -534,29 +545,50 @@ struct RowPair {
         valid = r0 < d.n;
         two = r0 + 1 < d.n;
         const int64_t rc = valid ? r0 : 0;
-        load_row_pair_cols<NG>(d.Vf, rc, two, d.ldv, j, v);
+        load_row_pair_cols<NG>(d.Vf, rc, two, d.ldv, VD ? j - 1 : j, v);
         const double2 ww = *reinterpret_cast<const double2 *>(d.w + rc);    // (w is padded: the pair of an odd n's last row)
+        if constexpr (VD) t = *reinterpret_cast<const double2 *>(d.wt + rc);    // (so is wt)
         w0 = valid ? ww.x : 0.0;
         w1 = (valid && two) ? ww.y : 0.0;
     }
 };
 
-template <int NG, typename BT>
+// VD: this launch also FORMS column j, v_j = (float)(wt / beta) - the expression and the rounding point of the Arnoldi kernel's
+// epilogue, which then leaves the column alone (GDev::vdots) - stores it and takes its own j-th sum from the registers.
+template <int NG, typename BT, bool VD = false>
 __global__ void __launch_bounds__(kRB) k_gmres_dots_rows(GDev d, int j) {
+    static_assert(!VD || sizeof(BT) == 4, "the column is formed by the row-pair kernel of the fp32-stored basis");
     __shared__ double tmp[(kRB / 64) * kKP];
     double acc[8 * NG];
 #pragma unroll
     for (int k = 0; k < 8 * NG; ++k) acc[k] = 0.0;
     double nrm = 0.0;
-    if (d.T[j].done == 0) {
+    const Snap *Tj = d.T + j;
+    if (Tj->done == 0) {
         if constexpr (sizeof(BT) == 4) {
             const int64_t nblk = ((int64_t)d.n + 2 * kRB - 1) / (2 * kRB);
-            RowPair<NG> cur, nxt;
+            RowPair<NG, VD> cur, nxt;
             int64_t blk = blockIdx.x;
             if (blk < nblk) cur.load(d, blk, j);
+            double inv_beta = 0.0;
+            if constexpr (VD) inv_beta = 1.0 / Tj->beta;                     // (T[j]: written by the Arnoldi launch before this one)
             for (; blk < nblk; blk += gridDim.x) {
                 const bool more = blk + gridDim.x < nblk;
                 if (more) nxt.load(d, blk + gridDim.x, j);                   // in flight during this trip's arithmetic
+                if constexpr (VD) {
+                    float2 vj = make_float2((float)(cur.t.x * inv_beta), (float)(cur.t.y * inv_beta));
+                    if (cur.valid) {
+                        float *col = d.Vf + (size_t)j * (size_t)d.ldv + (size_t)cur.r0;
+                        if (cur.two)
+                            *reinterpret_cast<float2 *>(col) = vj;
+                        else
+                            *col = vj.x;
+                    }
+                    if (!cur.two) vj.y = 0.f;                                // (as load_row_pair_cols returns the other columns)
+#pragma unroll
+                    for (int k = 0; k < 8 * NG; ++k)
+                        if (k == j) cur.v[k] = vj;                           // (wave-uniform)
+                }
 #pragma unroll
                 for (int k = 0; k < 8 * NG; ++k) acc[k] += (double)cur.v[k].x * cur.w0 + (double)cur.v[k].y * cur.w1;
                 nrm += cur.w0 * cur.w0 + cur.w1 * cur.w1;
@@ -584,15 +616,20 @@ __global__ void __launch_bounds__(kRB, (NG < 4 || FAST) ? 3 : 2) k_gmres_orth_ro
     __shared__ double tmp[(kRB / 32) * kKP];
     __shared__ double red[kKP];
     const Snap T = d.T[j];
+    if (T.done != 0) {
+        // the solve has ended: nothing to reduce and nothing to stream - the partial row reads as zeros, as it always did
+        if (threadIdx.x < kKP) d.P2[(size_t)blockIdx.x * kKP + threadIdx.x] = 0.0;
+        return;
+    }
     // (fp32 basis, fast instance) the first trip's rows do not depend on h: their loads go out before the reduction below
     constexpr bool kPipe = sizeof(BT) == 4 && FAST;
     const int64_t nblk2 = ((int64_t)d.n + 2 * kRB - 1) / (2 * kRB);
     RowPair<kPipe ? NG : 1> cur;
     if constexpr (kPipe) {
-        if (T.done == 0 && (int64_t)blockIdx.x < nblk2) cur.load(d, d.rev ? nblk2 - 1 - blockIdx.x : blockIdx.x, j);
+        if ((int64_t)blockIdx.x < nblk2) cur.load(d, d.rev ? nblk2 - 1 - blockIdx.x : blockIdx.x, j);
     }
-    // h1 = the dots kernel's partial rows summed in a fixed order by every workgroup (one GPU), or the single all-reduced
-    // row (several GPUs)
+    // h1 = the dots kernel's partial rows summed in a fixed order by every workgroup (one GPU, full kernels), or a single row:
+    // the one k_gmres_fold_first summed in that same order (one GPU, fast kernels) or the all-reduced one (several GPUs)
     reduce_partials<kRB / 32, kMaxRowsI>(d.Q1, d.nQ1, kKP, tmp, red);
     // h is wave-uniform: keep it in scalar registers (the kernel needs 16 NG vector registers for v and as many for acc)
     double h[8 * NG], acc[8 * NG];
@@ -605,84 +642,82 @@ __global__ void __launch_bounds__(kRB, (NG < 4 || FAST) ? 3 : 2) k_gmres_orth_ro
         acc[k] = 0.0;
     }
     double nrm = 0.0;
-    if (T.done == 0) {
-        if (blockIdx.x == 0 && threadIdx.x < kKP) {
-            d.hcol1[j * kKP + threadIdx.x] = ((int)threadIdx.x <= j) ? red[threadIdx.x] : 0.0;
-            if (threadIdx.x == 0) d.wnorm2[j] = red[kNormSlot];
-        }
-        if constexpr (kPipe) {
-            const int64_t nblk = nblk2;
-            RowPair<NG> nxt;
-            for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-                const int64_t nb = blk + gridDim.x;
-                const bool more = nb < nblk;
-                if (more) nxt.load(d, d.rev ? nblk - 1 - nb : nb, j);        // in flight during this trip's arithmetic
-                double p0 = cur.w0, p1 = cur.w1;
-#pragma unroll
-                for (int k = 0; k < 8 * NG; ++k) {
-                    p0 -= h[k] * (double)cur.v[k].x;
-                    p1 -= h[k] * (double)cur.v[k].y;
-                }
-                if (cur.valid) {
-                    if (cur.two)
-                        *reinterpret_cast<double2 *>(d.wt + cur.r0) = make_double2(p0, p1);
-                    else
-                        d.wt[cur.r0] = p0;
-                    if (d.xg.p) {
-                        d.xg.p[d.xg.pos((int)cur.r0)] = (float)p0;
-                        if (cur.two) d.xg.p[d.xg.pos((int)cur.r0 + 1)] = (float)p1;
-                    }
-                } else {
-                    p0 = 0.0;                                               // (a clamped lane read row 0's basis entries)
-                    p1 = 0.0;
-                }
-                if (!cur.two) p1 = 0.0;
-                nrm += p0 * p0 + p1 * p1;
-                if (more) cur = nxt;
-            }
-        } else if constexpr (sizeof(BT) == 4) {       // full kernels: the second-pass sums leave no registers for a second trip
-            const int64_t nblk = ((int64_t)d.n + 2 * kRB - 1) / (2 * kRB);
-            for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-                const int64_t r0 = 2 * ((d.rev ? nblk - 1 - blk : blk) * kRB + threadIdx.x);
-                if (r0 >= d.n) continue;
-                const bool two = r0 + 1 < d.n;
-                float2 v[8 * NG];
-                load_row_pair_cols<NG>(d.Vf, r0, two, d.ldv, j, v);
-                const double2 ww = *reinterpret_cast<const double2 *>(d.w + r0);
-                double p0 = ww.x, p1 = two ? ww.y : 0.0;
-#pragma unroll
-                for (int k = 0; k < 8 * NG; ++k) {
-                    p0 -= h[k] * (double)v[k].x;
-                    p1 -= h[k] * (double)v[k].y;
-                }
-                if (two)
-                    *reinterpret_cast<double2 *>(d.wt + r0) = make_double2(p0, p1);
-                else
-                    d.wt[r0] = p0;
-                if (!FAST) {
-#pragma unroll
-                    for (int k = 0; k < 8 * NG; ++k) acc[k] += (double)v[k].x * p0 + (double)v[k].y * p1;
-                }
-                nrm += p0 * p0 + p1 * p1;
-            }
-        } else {
-        const int64_t nblk = ((int64_t)d.n + kRB - 1) / kRB;
+    if (!d.onefold && blockIdx.x == 0 && threadIdx.x < kKP) {            // (onefold: the fold kernel has stored them)
+        d.hcol1[j * kKP + threadIdx.x] = ((int)threadIdx.x <= j) ? red[threadIdx.x] : 0.0;
+        if (threadIdx.x == 0) d.wnorm2[j] = red[kNormSlot];
+    }
+    if constexpr (kPipe) {
+        const int64_t nblk = nblk2;
+        RowPair<NG> nxt;
         for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-            const int64_t row = (d.rev ? nblk - 1 - blk : blk) * kRB + threadIdx.x;
-            if (row >= d.n) continue;
-            double v[8 * NG];
-            load_row_cols<NG, BT>(basis_ptr<BT>(d), row, d.ldv, j, v);          // split mode: the basis is column-major
-            double wp = d.w[row];
+            const int64_t nb = blk + gridDim.x;
+            const bool more = nb < nblk;
+            if (more) nxt.load(d, d.rev ? nblk - 1 - nb : nb, j);        // in flight during this trip's arithmetic
+            double p0 = cur.w0, p1 = cur.w1;
 #pragma unroll
-            for (int k = 0; k < 8 * NG; ++k) wp -= h[k] * v[k];
-            d.wt[row] = wp;
+            for (int k = 0; k < 8 * NG; ++k) {
+                p0 -= h[k] * (double)cur.v[k].x;
+                p1 -= h[k] * (double)cur.v[k].y;
+            }
+            if (cur.valid) {
+                if (cur.two)
+                    *reinterpret_cast<double2 *>(d.wt + cur.r0) = make_double2(p0, p1);
+                else
+                    d.wt[cur.r0] = p0;
+                if (d.xg.p) {
+                    d.xg.p[d.xg.pos((int)cur.r0)] = (float)p0;
+                    if (cur.two) d.xg.p[d.xg.pos((int)cur.r0 + 1)] = (float)p1;
+                }
+            } else {
+                p0 = 0.0;                                               // (a clamped lane read row 0's basis entries)
+                p1 = 0.0;
+            }
+            if (!cur.two) p1 = 0.0;
+            nrm += p0 * p0 + p1 * p1;
+            if (more) cur = nxt;
+        }
+    } else if constexpr (sizeof(BT) == 4) {       // full kernels: the second-pass sums leave no registers for a second trip
+        const int64_t nblk = ((int64_t)d.n + 2 * kRB - 1) / (2 * kRB);
+        for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+            const int64_t r0 = 2 * ((d.rev ? nblk - 1 - blk : blk) * kRB + threadIdx.x);
+            if (r0 >= d.n) continue;
+            const bool two = r0 + 1 < d.n;
+            float2 v[8 * NG];
+            load_row_pair_cols<NG>(d.Vf, r0, two, d.ldv, j, v);
+            const double2 ww = *reinterpret_cast<const double2 *>(d.w + r0);
+            double p0 = ww.x, p1 = two ? ww.y : 0.0;
+#pragma unroll
+            for (int k = 0; k < 8 * NG; ++k) {
+                p0 -= h[k] * (double)v[k].x;
+                p1 -= h[k] * (double)v[k].y;
+            }
+            if (two)
+                *reinterpret_cast<double2 *>(d.wt + r0) = make_double2(p0, p1);
+            else
+                d.wt[r0] = p0;
             if (!FAST) {
 #pragma unroll
-                for (int k = 0; k < 8 * NG; ++k) acc[k] += v[k] * wp;
+                for (int k = 0; k < 8 * NG; ++k) acc[k] += (double)v[k].x * p0 + (double)v[k].y * p1;
             }
-            nrm += wp * wp;
+            nrm += p0 * p0 + p1 * p1;
         }
+    } else {
+    const int64_t nblk = ((int64_t)d.n + kRB - 1) / kRB;
+    for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+        const int64_t row = (d.rev ? nblk - 1 - blk : blk) * kRB + threadIdx.x;
+        if (row >= d.n) continue;
+        double v[8 * NG];
+        load_row_cols<NG, BT>(basis_ptr<BT>(d), row, d.ldv, j, v);          // split mode: the basis is column-major
+        double wp = d.w[row];
+#pragma unroll
+        for (int k = 0; k < 8 * NG; ++k) wp -= h[k] * v[k];
+        d.wt[row] = wp;
+        if (!FAST) {
+#pragma unroll
+            for (int k = 0; k < 8 * NG; ++k) acc[k] += v[k] * wp;
         }
+        nrm += wp * wp;
+    }
     }
     if (!FAST) {
         store_partial_row_rows<NG>(acc, nrm, tmp, d.P2);
@@ -699,6 +734,38 @@ __global__ void __launch_bounds__(kRB, (NG < 4 || FAST) ? 3 : 2) k_gmres_orth_ro
                 for (int w = 0; w < kRB / 64; ++w) t += tmp[w];
             d.P2[(size_t)blockIdx.x * kKP + threadIdx.x] = t;
         }
+    }
+}
+
+// One GPU, fast kernels: the dots kernel's GP1 partial rows summed ONCE, by one workgroup between the two row kernels, instead of
+// by every workgroup of the orthogonalisation kernel (768 x 196 KB of L2 reads and twelve dependent round trips per launch).
+// The ORDER is that of reduce_partials<kRB / 32, kMaxRowsI>: slice s of 8 adds rows s, s + 8, ... upwards from 0.0, then the 8
+// slice sums are added upwards from 0.0 - and the consumer's own pass over the one row adds exact zeros (a sum that starts at
+// +0.0 is never -0.0) - so h, ||w||^2 and everything after them keep their bits.  Every load is issued before the first add.
+__global__ void __launch_bounds__(kRB) k_gmres_fold_first(GDev d, int j, double *out) {
+    constexpr int NS = kRB / 32;
+    __shared__ double tmp[NS * kKP];
+    const int done = d.T[j].done;
+    const int k = threadIdx.x & (kKP - 1), slice = threadIdx.x >> 5;
+    const int nrows = d.GP1;                                      // (1 <= GP1 <= kMaxG = NS * kMaxRowsI)
+    double v[kMaxRowsI];
+#pragma unroll
+    for (int i = 0; i < kMaxRowsI; ++i) {
+        const int b = slice + NS * i;
+        v[i] = d.P1[(size_t)(b < nrows ? b : 0) * kKP + k];       // (clamped, not branched around: straight-line loads)
+    }
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < kMaxRowsI; ++i) s += (slice + NS * i < nrows) ? v[i] : 0.0;
+    tmp[slice * kKP + k] = s;
+    __syncthreads();
+    if (threadIdx.x < kKP && done == 0) {
+        double t = 0.0;
+#pragma unroll
+        for (int sl = 0; sl < NS; ++sl) t += tmp[sl * kKP + threadIdx.x];
+        out[threadIdx.x] = t;
+        d.hcol1[j * kKP + threadIdx.x] = ((int)threadIdx.x <= j) ? t : 0.0;
+        if (threadIdx.x == kNormSlot) d.wnorm2[j] = t;
     }
 }
 
@@ -920,7 +987,9 @@ static void launch_rows_bt(const GDev &d, int j, hipStream_t st, bool orth) {
 }
 template <int NG>
 static void launch_rows(const GDev &d, int j, hipStream_t st, bool orth) {
-    if (d.Vf)
+    if (d.Vf && d.vdots && !orth)
+        hipLaunchKernelGGL((k_gmres_dots_rows<NG, float, true>), dim3(d.GR), dim3(kRB), 0, st, d, j);
+    else if (d.Vf)
         launch_rows_bt<NG, float>(d, j, st, orth);
     else
         launch_rows_bt<NG, double>(d, j, st, orth);
@@ -1047,6 +1116,7 @@ static int launch_cycle_L(const GDev &d, hipStream_t st, hipEvent_t *pev, npg_gm
             launch_arnoldi_split<L>(d, std::min(d.G1, std::max(1, a_nt)), j, 0, a_nt, st, pev ? pev[2 * j] : nullptr,
                                     pev ? pev[2 * j + 1] : nullptr);
             launch_rows_kernel(d, j, st, false);
+            if (d.onefold) hipLaunchKernelGGL(k_gmres_fold_first, dim3(1), dim3(kRB), 0, st, d, j, const_cast<double *>(d.Q1));
         } else {
             if (pev) hipEventRecord(pev[2 * j], st);
             hipLaunchKernelGGL((k_gmres_arnoldi<L, true>), dim3(d.G1), dim3(kKB), 0, st, d, j, 0, d.ntiles);
@@ -1331,6 +1401,12 @@ NPG_API int npg_gmres_solve(npg_gmres *ws, const npg_csr *A_in, int precond_kind
             d.wpre = pre_env;
         }
     }
+    // One GPU, split organisation, fast kernels: the first-pass sums are folded once and the basis column is formed by the dots
+    // kernel (NPG_GMRES_ONEFOLD=0: every orthogonalisation workgroup folds them, the Arnoldi epilogue stores the column).  Same
+    // sums in the same order, same expression for the column: the switch changes no bit of any result.
+    const char *onefold_env = getenv("NPG_GMRES_ONEFOLD");
+    d.onefold = (!dist && d.split && d.fast && !(onefold_env && atoi(onefold_env) == 0)) ? 1 : 0;
+    d.vdots = (d.onefold && d.Vf) ? 1 : 0;
     if (dist) {
         d.Q1 = ws->Rg;
         d.Q2 = ws->Rg + kKP;
@@ -1343,6 +1419,10 @@ NPG_API int npg_gmres_solve(npg_gmres *ws, const npg_csr *A_in, int precond_kind
         d.nQ1 = d.GP1;
         d.nQ2 = d.GP2;
         d.nQR = d.G1;
+        if (d.onefold) {            // (slot 0 of the all-reduced rows is free on one GPU)
+            d.Q1 = ws->Rg;
+            d.nQ1 = 1;
+        }
     }
     d.C = ws->C;
     d.T = ws->T;
