@@ -42,6 +42,7 @@ typedef struct npg_index npg_index;
 typedef struct npg_fgmres npg_fgmres;
 typedef struct npg_locator npg_locator;
 typedef struct npg_located npg_located;
+typedef struct npg_integrals npg_integrals;
 
 /* ---- context: replaces the implicit CUDA.jl device/stream (ext/nuPGCMCUDAExt.jl:8-16) ------------------------- */
 int npg_ctx_create(int device, npg_ctx **out);
@@ -532,6 +533,24 @@ int npg_sample_unmask(int64_t n, int ncomp, npg_vec *buf);
  * order per entry, the same bits on every call.  The locator keeps the working memory (ceil(nx / 16) partial zon arrays). */
 int npg_fe_grid_integrals(npg_fe *fe, npg_locator *loc, const npg_vec *x_inv, const npg_vec *b, double N2, const npg_vec *axes,
                           int64_t nx, int64_t ny, int64_t nz, npg_vec *col, npg_vec *zon);
+
+/* ---- quadrature integrals of the state over the mesh (new work: the reference logs maxima only) ------------------------------
+ * The exact integrals of the finite-element fields with the engine's own rule, NPG_NINT channels (csrc/integrals_core.h):
+ *    0  1 (volume; area on the embedded 2-D meshes)     1  b'               2  b'^2
+ *    3  (u_x^2 + u_y^2) / 2                             4  u_z^2 / 2        5  u_z b'
+ *    6  nu grad u : grad u  (0 without a nu table)      7  2 nu sigma : sigma, sigma = (grad u + grad u') / 2 (full_stress = 1; else 0)
+ *    8  z b'                                            9  u . grad b'     10  u_z
+ *   11  kappa_h (d_x b'^2 + d_y b'^2) + kappa_v d_z b'^2                   12  kappa_v d_z b'      13  kappa_v      14  (div u)^2
+ * RAW integrals: the model's prefactors (alpha^2 eps^2, 1 / alpha, N2) are the caller's.  Always fp64 - npg_fe_set_precision does
+ * not apply.  Dirichlet nodes count with their values.  No atomics, a grid that depends on the cell count alone, one summation order:
+ * the same bits on every call.  The handle owns the partial sums, the z table and the mask; the engine must outlive it. */
+#define NPG_NINT 15
+/* cell_z[ncell][4]: z of each cell's OWN vertices (Mesh.geo_coords[Mesh.cell_geo], as the locator's anchor);
+   cell_mask[ncell] or NULL: 1 = this cell counts (a rank's owned cells) */
+int npg_integrals_create(npg_fe *fe, const double *cell_z, const uint8_t *cell_mask, npg_integrals **out);
+int npg_integrals_destroy(npg_integrals *I);
+/* out: NPG_NINT doubles on the device. x_inv = [u; p], b = buoyancy vector. */
+int npg_integrals_compute(npg_integrals *I, const npg_vec *x_inv, const npg_vec *b, int full_stress, npg_vec *out);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (new work: the reference is single-device) ----------------- */
 #define NPG_UNIQUE_ID_BYTES 128

@@ -9,6 +9,7 @@ from .evolution import EvolutionToolkit, collect_evolution_LHS, evolution_parame
 from .fe import DoFHandler, FEData, Mesh, Spaces, get_n_dofs
 from .inputs import (ConvectionParameterization, EddyParameterization, Forcings, Parameters, SurfaceDirichletBC,
                      SurfaceFluxBC)
+from .integrals import BudgetRecorder, Budgets, MeshIntegrals
 from .inversion import InversionToolkit, build_A_inversion, build_B_inversion, build_b_inversion
 from .io import save_checkpoint, save_state, save_vtk, set_out_dir, set_state_from_file
 from .iterative_solvers import CgWorkspace, Diagonal, GmresWorkspace, IterativeSolverToolkit, MgsGmresWorkspace, iterative_solve

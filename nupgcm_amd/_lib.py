@@ -158,6 +158,7 @@ def _declare(L, partial=False):
         "npg_located_create": [P, I64, PP], "npg_located_destroy": [P], "npg_located_upload": [P, VP, VP],
         "npg_located_download": [P, VP, VP], "npg_locator_find": [P, P, I64, P], "npg_fe_sample": [P, C.c_int, P, P, P],
         "npg_fe_grid_integrals": [P, P, P, P, D, P, I64, I64, I64, P, P],
+        "npg_integrals_create": [P, VP, VP, PP], "npg_integrals_destroy": [P], "npg_integrals_compute": [P, P, P, C.c_int, P],
         "npg_comm_unique_id": [VP], "npg_comm_init": [P, VP, C.c_int, C.c_int],
         "npg_comm_allreduce_sum": [P, C.POINTER(D), C.c_int], "npg_comm_info": [P, C.c_char_p, C.c_size_t], "npg_comm_disable_peer": [P], "npg_comm_allreduce_vec": [P, P],
         "npg_comm_allgather_segments": [P, P, C.c_int, VP, VP, VP, VP, P],
@@ -211,4 +212,5 @@ NPG_PC_BLOCKDIAG, NPG_PC_MG, NPG_PC_DENSE = 1, 2, 3
 NPG_BDF1, NPG_BDF2 = 1, 2
 NPG_FE_FP64, NPG_FE_FP32 = 0, 1
 NPG_SAMPLE_U, NPG_SAMPLE_P, NPG_SAMPLE_B, NPG_SAMPLE_GRAD_B = 1, 2, 3, 4
+NPG_NINT = 15
 NPG_MAT_M, NPG_MAT_KH, NPG_MAT_KV, NPG_MAT_A, NPG_MAT_B = 1, 2, 3, 4, 5

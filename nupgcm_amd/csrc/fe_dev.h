@@ -1,5 +1,5 @@
 // The element engine's device tables and handle, shared by the translation units that read them (fe.hip: assembly; sample.hip:
-// point evaluation of the state).
+// point evaluation of the state; integrals.hip: quadrature integrals of the state), and the shape tables they stage in LDS.
 #pragma once
 #include "common.h"
 
@@ -17,6 +17,38 @@ struct FeDev {
     const double *u_diri, *b_diri;
     const double *nu, *kh, *kv, *f;   // [nq][ncell] or null
 };
+
+constexpr int kMaxQ = 16;
+
+// R = the arithmetic type of the element-LOCAL work (shape tables, geometry, nodal values, the integrand at a quadrature
+// point): double, or float for the mixed mode of BASELINE.json configs[4] ("fp32 assembly / fp64 solve").  Whatever R is,
+// sums over quadrature points, over the cells of a row and everything downstream (CSR values, right-hand sides, solvers)
+// are fp64, and all HBM tables stay fp64 (converted on load).
+template <typename R>
+struct FeTablesT {
+    R qw[kMaxQ];
+    R N2[kMaxQ * 10];
+    R dN2[kMaxQ * 40];
+    R Nb[kMaxQ * 10];
+    R dNb[kMaxQ * 40];
+    R N1[kMaxQ * 4];
+};
+using FeTables = FeTablesT<double>;
+
+template <typename R>
+__device__ __forceinline__ void stage_tables(const FeDev &d, FeTablesT<R> &t) {
+    for (int i = threadIdx.x; i < d.nq; i += blockDim.x) t.qw[i] = (R)d.qw[i];
+    for (int i = threadIdx.x; i < d.nq * 10; i += blockDim.x) t.N2[i] = (R)d.N2[i];
+    for (int i = threadIdx.x; i < d.nq * 40; i += blockDim.x) t.dN2[i] = (R)d.dN2[i];
+    for (int i = threadIdx.x; i < d.nq * d.nb; i += blockDim.x) t.Nb[i] = (R)d.Nb[i];
+    for (int i = threadIdx.x; i < d.nq * d.nb * 4; i += blockDim.x) t.dNb[i] = (R)d.dNb[i];
+    for (int i = threadIdx.x; i < d.nq * 4; i += blockDim.x) t.N1[i] = (R)d.N1[i];
+    __syncthreads();
+}
+
+__device__ __forceinline__ double field_val(const double *x, const double *diri, int32_t idx) {
+    return idx >= 0 ? x[idx] : diri[-1 - idx];
+}
 
 }  // namespace npg
 

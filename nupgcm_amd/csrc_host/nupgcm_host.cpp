@@ -1300,3 +1300,83 @@ NPG_API int npg_fe_grid_integrals(npg_fe *fe, npg_locator *loc, const npg_vec *x
         }
     return NPG_OK;
 }
+
+// ---- quadrature integrals of the state over the mesh (csrc/integrals.hip on the host): the per-cell arithmetic is the SAME code
+// (csrc/integrals_core.h).  Fixed chunks of kIntChunk cells give one partial row each, folded in chunk order: the sums do not depend
+// on the number of threads. -----------------------------------------------------------------------------------------------------------
+#include "../csrc/integrals_core.h"
+static_assert(NPG_NINT == npg::kNInt, "NPG_NINT of the header and kNInt of integrals_core.h must agree");
+
+struct npg_integrals {
+    npg_fe *fe = nullptr;
+    std::vector<double> cz;          // [ncell][4]
+    std::vector<uint8_t> mask;       // [ncell] or empty
+    std::vector<double> part;        // [nchunk][NPG_NINT]
+};
+namespace {
+struct HostShape {       // the engine's shape tables as cell_integrals reads them
+    const double *qw, *N2, *dN2, *Nb, *dNb, *N1;
+};
+struct HostCells {       // and its cell tables ([cell][component])
+    const npg_fe *fe;
+    const double *cz;
+    bool has_nu, has_kh, has_kv;
+    double G(int k, int64_t c) const { return fe->G[(size_t)c * 12 + k]; }
+    double wdet(int64_t c) const { return fe->wdet[(size_t)c]; }
+    double z(int i, int64_t c) const { return cz[(size_t)c * 4 + i]; }
+    double u(const double *x, int l, int64_t c) const { return fval(x, fe->u_diri, fe->cu[(size_t)c * 30 + l]); }
+    double b(const double *x, int i, int64_t c) const { return fval(x, fe->b_diri, fe->cb[(size_t)c * fe->nb + i]); }
+    double nu(int q, int64_t c) const { return fe->coef[0][(size_t)c * fe->nq + q]; }
+    double kh(int q, int64_t c) const { return fe->coef[1][(size_t)c * fe->nq + q]; }
+    double kv(int q, int64_t c) const { return fe->coef[2][(size_t)c * fe->nq + q]; }
+};
+}  // namespace
+
+NPG_API int npg_integrals_create(npg_fe *fe, const double *cell_z, const uint8_t *cell_mask, npg_integrals **out) {
+    REQUIRE(fe && out, "npg_integrals_create: NULL argument");
+    REQUIRE(cell_z, "npg_integrals_create: cell_z is NULL");
+    const int64_t nc = fe->ncell;
+    for (int64_t k = 0; k < nc * 4; ++k)
+        REQUIRE(std::isfinite(cell_z[k]), "npg_integrals_create: cell_z[%lld][%d] is not finite", (long long)(k / 4), (int)(k % 4));
+    npg_integrals *I = new npg_integrals();
+    I->fe = fe;
+    I->cz.assign(cell_z, cell_z + nc * 4);
+    if (cell_mask) I->mask.assign(cell_mask, cell_mask + nc);
+    I->part.assign((size_t)((nc + npg::kIntChunk - 1) / npg::kIntChunk) * NPG_NINT, 0.0);
+    *out = I;
+    return NPG_OK;
+}
+NPG_API int npg_integrals_destroy(npg_integrals *I) {
+    delete I;
+    return NPG_OK;
+}
+NPG_API int npg_integrals_compute(npg_integrals *I, const npg_vec *x_inv, const npg_vec *b, int full_stress, npg_vec *out) {
+    REQUIRE(I && x_inv && b && out, "npg_integrals_compute: NULL argument");
+    const npg_fe *fe = I->fe;
+    REQUIRE(x_inv->n == fe->n_inv, "npg_integrals_compute: the flow vector has %lld entries, expected %lld", (long long)x_inv->n,
+            (long long)fe->n_inv);
+    REQUIRE(b->n == fe->n_b, "npg_integrals_compute: the buoyancy vector has %lld entries, expected %lld", (long long)b->n, (long long)fe->n_b);
+    REQUIRE(out->n >= NPG_NINT, "npg_integrals_compute: out holds %lld doubles, needs NPG_NINT = %d", (long long)out->n, NPG_NINT);
+    REQUIRE(full_stress == 0 || full_stress == 1, "npg_integrals_compute: full_stress must be 0 or 1, got %d", full_stress);
+    const int64_t nc = fe->ncell, nchunk = (nc + npg::kIntChunk - 1) / npg::kIntChunk;
+    const HostShape s{fe->qw.data(), fe->N2.data(), fe->dN2.data(), fe->Nb.data(), fe->dNb.data(), fe->N1.data()};
+    const HostCells t{fe, I->cz.data(), !fe->coef[0].empty(), !fe->coef[1].empty(), !fe->coef[2].empty()};
+    const uint8_t *mask = I->mask.empty() ? nullptr : I->mask.data();
+#pragma omp parallel for schedule(static)
+    for (int64_t k = 0; k < nchunk; ++k) {
+        double acc[NPG_NINT];
+        for (int a = 0; a < NPG_NINT; ++a) acc[a] = 0.0;
+        for (int64_t c = k * npg::kIntChunk; c < std::min(nc, (k + 1) * npg::kIntChunk); ++c) {
+            if (mask && !mask[c]) continue;
+            if (fe->nb == 10) npg::cell_integrals<10>(s, t, fe->nq, x_inv->d, b->d, c, full_stress != 0, acc);
+            else npg::cell_integrals<4>(s, t, fe->nq, x_inv->d, b->d, c, full_stress != 0, acc);
+        }
+        for (int a = 0; a < NPG_NINT; ++a) I->part[(size_t)k * NPG_NINT + a] = acc[a];
+    }
+    for (int a = 0; a < NPG_NINT; ++a) {
+        double sum = 0.0;
+        for (int64_t k = 0; k < nchunk; ++k) sum += I->part[(size_t)k * NPG_NINT + a];
+        out->d[a] = sum;
+    }
+    return NPG_OK;
+}

@@ -1,0 +1,74 @@
+"""Mesh integrals of a mesh-partitioned model (nupgcm_amd.integrals on a partition.PartitionedModel): 2 and 3 ranks on
+one GPU, peer-window and shared-memory transports, bowl3D h = 0.1 and the small channel basin, against the one-device models in this
+process.  As in tests/test_gpu_dist_sampling.py the models are not stepped: one synthetic global state is uploaded to the one-device
+model and, slice by slice, to every rank.  Each configuration is launched once, in fresh child processes, under its own time limit;
+a failed launch fails its test and nothing is started after it in that test."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import nupgcm_amd as npg
+from nupgcm_amd import workloads
+
+from . import dist_integrals_worker as W
+from . import integrals_ref as ir
+from .dist_sampling_worker import MESH, synthetic_state
+from .test_gpu_distributed import _free_port
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+EPS = np.finfo(np.float64).eps
+
+
+def _launch(world, transport, out, timeout=300):
+    env = dict(os.environ, NPG_COMM_TRANSPORT=transport, NPG_FORCE_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2",
+               NPG_PEER_TIMEOUT_S="60")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
+           "--master-port", str(_free_port()), os.path.join(HERE, "dist_integrals_worker.py"), out]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)          # one attempt: no retry
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    ranks = [dict(np.load(f"{out}.rank{k}.npz")) for k in range(world)]
+    assert all(str(z["transport"]) == transport for z in ranks)
+    return ranks
+
+
+@pytest.fixture(scope="module")
+def serial():
+    """tag -> (one-device model with the synthetic state, its channels, S_abs of the restatement, nq)"""
+    arch = npg.GPU()
+    out = {}
+    for tag, model in (("bowl", workloads.example_model(arch, MESH)),
+                       ("channel", workloads.channel_basin_model(arch, mesh_model=W.channel_mesh_model()))):
+        xg, bg = synthetic_state(model.fe_data)
+        model.inversion.solver.x.upload(xg)
+        model.b_vec.upload(bg)
+        f = model.forcings
+        un, bn = ir.nodal_values(model)
+        terms, _, sabs = ir.restate(model.fe_data, un, bn, f.nu, f.kappa_h, f.kappa_v, bool(callable(f.nu) or f.eddy_param.is_on))
+        out[tag] = (model, npg.MeshIntegrals(model).compute_raw(), sabs, terms.shape[2])
+    return out
+
+
+@pytest.mark.parametrize("world,transport", [(2, "peer"), (3, "shm")])
+def test_partitioned_integrals_equal_the_one_device_model(serial, tmp_path, world, transport):
+    ranks = _launch(world, transport, str(tmp_path / f"w{world}_{transport}"))
+    for tag, (model, ref, sabs, nq) in serial.items():
+        nc = model.fe_data.mesh.ncell
+        z = ranks[0]
+        for other in ranks[1:]:                                              # every rank returns the same bits
+            assert np.array_equal(other[f"{tag}_raw1"], z[f"{tag}_raw1"]), tag
+        for r in ranks:                                                      # two calls give identical bits
+            assert np.array_equal(r[f"{tag}_raw1"], r[f"{tag}_raw2"]), tag
+        counted = [int(r[f"{tag}_counted"]) for r in ranks]
+        assert sum(counted) == nc and min(counted) > 0, (tag, counted, nc)   # every cell exactly once
+        got = z[f"{tag}_raw1"]
+        assert abs(got[0] - ref[0]) <= nc * EPS * ref[0], (tag, got[0], ref[0])
+        bound = ir.summation_bound(nc, nq, sabs)
+        err = np.abs(got - ref)
+        print(f"{world} ranks {transport} {tag} (cells per rank {counted}): " +
+              ", ".join(f"ch{k} {err[k]:.1e}/{bound[k]:.1e}" for k in range(ir.NINT)))
+        assert (err <= bound).all(), (tag, err, bound)
+        assert np.abs(ref[[0, 2, 3, 4, 6, 14]]).min() > 0                    # the synthetic state exercises the flow channels
