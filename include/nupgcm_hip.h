@@ -43,6 +43,7 @@ typedef struct npg_fgmres npg_fgmres;
 typedef struct npg_locator npg_locator;
 typedef struct npg_located npg_located;
 typedef struct npg_integrals npg_integrals;
+typedef struct npg_particles npg_particles;
 
 /* ---- context: replaces the implicit CUDA.jl device/stream (ext/nuPGCMCUDAExt.jl:8-16) ------------------------- */
 int npg_ctx_create(int device, npg_ctx **out);
@@ -551,6 +552,34 @@ int npg_integrals_create(npg_fe *fe, const double *cell_z, const uint8_t *cell_m
 int npg_integrals_destroy(npg_integrals *I);
 /* out: NPG_NINT doubles on the device. x_inv = [u; p], b = buoyancy vector. */
 int npg_integrals_compute(npg_integrals *I, const npg_vec *x_inv, const npg_vec *b, int full_stress, npg_vec *out);
+
+/* ---- Lagrangian particles advected through the device-resident flow (new work: offline tracking needs u saved every step) -----
+ * n particles on the device: position [n][3], the cell each was last located in, status (0 alive, 1 lost), wind [n][3] and t_lost.
+ * npg_particles_advance carries every live particle through nsub classical RK4 steps of dx/dt = u(x, t), h = dt / nsub, in ONE kernel
+ * (csrc/particles_core.h): per stage locate -> evaluate u (closed-form P2 through the DoF tables, as npg_fe_sample(NPG_SAMPLE_U)) ->
+ * next stage point; the remembered cell is accepted without reading the bins when the point's min lambda there is >= 1e-8, otherwise
+ * the full election of npg_locator_find runs - either way the cell and lambda of npg_locator_find, bit for bit.
+ * Velocity in time: u = (1 - s) u(x_a) + s u(x_b), s = s0 + (s1 - s0) (tau / dt), tau = the time since the start of the call; x_a and
+ * x_b the same vector (the same device memory): frozen flow, one evaluation, s unused.  Model time is the particles' clock.
+ * Periodic axes (npg_particles_set_period): L[a] > 0 = the period of axis a, 0 = not periodic; the lower bound is the locator's box.
+ * Stage points are wrapped into [lo, lo + L) for their location only, the stored position after the step; wind counts the crossings:
+ * the unwrapped position is x + wind L.
+ * Leaving the mesh: a step with a stage point or an end point outside the mesh is not taken - the particle keeps its position of the
+ * start of that step, status = 1, t_lost = the time at the start of that step, and no later call moves it.  A seed that is NaN or
+ * outside the mesh is lost at the start of the first call.  No reflection, no projection onto the boundary.
+ * Always fp64.  Validation (NPG_EINVAL + message) happens before anything is launched.  A partitioned locator
+ * (npg_locator_create_cells) is refused: migration between ranks is not implemented; an embedded 2-D engine has no locator. */
+int npg_particles_create(npg_ctx *ctx, int64_t n, npg_particles **out);       /* n = 0 is legal; positions 0, t = 0 until set */
+int npg_particles_destroy(npg_particles *P);
+/* xyz[n][3] (host) at time t0; resets status, wind, t_lost (NaN) and the remembered cells */
+int npg_particles_set(npg_particles *P, const double *xyz, double t0);
+int npg_particles_set_period(npg_particles *P, const double *L3);
+int npg_particles_advance(npg_particles *P, npg_fe *fe, npg_locator *loc, const npg_vec *x_a, const npg_vec *x_b, double s0, double s1,
+                          double dt, int64_t nsub);
+/* host copies: xyz[n][3], cell[n], status[n], wind[n][3] (int32), t_lost[n] (NaN while alive); any may be NULL */
+int npg_particles_download(const npg_particles *P, double *xyz, int32_t *cell, int32_t *status, int32_t *wind, double *t_lost);
+/* device copy of the positions into a vector of 3 n doubles: what npg_locator_find / npg_fe_sample take (b along a path) */
+int npg_particles_positions(const npg_particles *P, npg_vec *out);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (new work: the reference is single-device) ----------------- */
 #define NPG_UNIQUE_ID_BYTES 128

@@ -159,6 +159,9 @@ def _declare(L, partial=False):
         "npg_located_download": [P, VP, VP], "npg_locator_find": [P, P, I64, P], "npg_fe_sample": [P, C.c_int, P, P, P],
         "npg_fe_grid_integrals": [P, P, P, P, D, P, I64, I64, I64, P, P],
         "npg_integrals_create": [P, VP, VP, PP], "npg_integrals_destroy": [P], "npg_integrals_compute": [P, P, P, C.c_int, P],
+        "npg_particles_create": [P, I64, PP], "npg_particles_destroy": [P], "npg_particles_set": [P, VP, D],
+        "npg_particles_set_period": [P, VP], "npg_particles_advance": [P, P, P, P, P, D, D, D, I64],
+        "npg_particles_download": [P, VP, VP, VP, VP, VP], "npg_particles_positions": [P, P],
         "npg_comm_unique_id": [VP], "npg_comm_init": [P, VP, C.c_int, C.c_int],
         "npg_comm_allreduce_sum": [P, C.POINTER(D), C.c_int], "npg_comm_info": [P, C.c_char_p, C.c_size_t], "npg_comm_disable_peer": [P], "npg_comm_allreduce_vec": [P, P],
         "npg_comm_allgather_segments": [P, P, C.c_int, VP, VP, VP, VP, P],

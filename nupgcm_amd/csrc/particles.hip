@@ -1,0 +1,176 @@
+// Lagrangian particles advected through the device-resident flow (npg_particles_advance): where a water parcel goes,
+// answered while the velocity is still in HBM instead of from velocities saved every timestep.
+//   k_particles_advance<BLEND>   one lane per particle, nsub classical RK4 steps per launch (particles_core.h: locate -> evaluate ->
+//                                next stage).  Position, cell, lambda, wind and status live in registers across the substeps and are
+//                                written once at the end; the cell remembered from the last location is tried first, so a particle
+//                                that stays in its cell reads one 128-byte record per stage and never the bins.  BLEND: the velocity
+//                                is (1 - s) u_a + s u_b, the two vectors evaluated one after the other from the same lambda;
+//                                BLEND = false (the same vector twice): one evaluation.  The period is a runtime branch.
+// No LDS, no scratch, no atomics: a particle is one lane's own, so the result does not depend on the order or the number of particles.
+// Always fp64 (npg_fe_set_precision does not apply).
+#include <cmath>
+
+#include "common.h"
+#include "fe_dev.h"
+#include "particles_core.h"
+#include "sample_dev.h"
+
+namespace npg {
+
+template <bool BLEND>
+__global__ void __launch_bounds__(kBlock) k_particles_advance(ParticleMesh m, DevTables t, const double *__restrict__ xa,
+                                                              const double *__restrict__ xb, ParticleCall call, int64_t nsub,
+                                                              int64_t n, double *__restrict__ xyz, int32_t *__restrict__ cell,
+                                                              int32_t *__restrict__ status, int32_t *__restrict__ wind,
+                                                              double *__restrict__ t_lost) {
+    const int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x;
+    if (i >= n) return;
+    if (status[i] != 0) return;              // lost: nothing moves it
+    ParticleState p;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) p.x[a] = xyz[3 * i + a], p.wind[a] = wind[3 * i + a];
+    p.c = cell[i];
+    const int64_t done = particle_advance<BLEND>(m, t, xa, xb, call, nsub, p);
+    if (done < nsub) {
+        status[i] = 1;
+        t_lost[i] = done > 0 ? call.t + (double)done * call.h : call.t;
+        if (done < 0) return;                // lost where the call found it: the seed stays as it was given
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) xyz[3 * i + a] = p.x[a], wind[3 * i + a] = p.wind[a];
+    cell[i] = p.c;
+}
+
+}  // namespace npg
+
+using namespace npg;
+
+struct npg_particles {
+    npg_ctx *ctx = nullptr;
+    int64_t n = 0;
+    double t = 0.0;              // the time the particles are at
+    double L[3] = {0.0, 0.0, 0.0};
+    double *xyz = nullptr;       // [n][3]
+    double *t_lost = nullptr;    // [n], NaN while alive
+    int32_t *cell = nullptr;     // [n] the remembered cell, -1 = none
+    int32_t *status = nullptr;   // [n] 0 alive, 1 lost
+    int32_t *wind = nullptr;     // [n][3]
+};
+
+NPG_API int npg_particles_destroy(npg_particles *P) {
+    if (!P) return NPG_OK;
+    hipStreamSynchronize(P->ctx->stream);
+    hipFree(P->xyz);
+    hipFree(P->t_lost);
+    hipFree(P->cell);
+    hipFree(P->status);
+    hipFree(P->wind);
+    delete P;
+    return NPG_OK;
+}
+
+NPG_API int npg_particles_create(npg_ctx *ctx, int64_t n, npg_particles **out) {
+    NPG_REQUIRE(ctx && out, "npg_particles_create: NULL argument");
+    NPG_REQUIRE(n >= 0 && n <= ((int64_t)1 << 32), "npg_particles_create: 0 .. 2^32 particles, got %lld", (long long)n);
+    NPG_HIP(hipSetDevice(ctx->device));
+    npg_particles *P = new npg_particles();
+    P->ctx = ctx;
+    P->n = n;
+    const size_t m = std::max<size_t>(1, (size_t)n);
+    hipError_t e = hipMalloc((void **)&P->xyz, m * 3 * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void **)&P->t_lost, m * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void **)&P->cell, m * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&P->status, m * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&P->wind, m * 3 * sizeof(int32_t));
+    if (e != hipSuccess) {
+        npg_particles_destroy(P);
+        NPG_HIP(e);
+    }
+    *out = P;
+    const std::vector<double> zero(m * 3, 0.0);
+    return npg_particles_set(P, zero.data(), 0.0);
+}
+
+NPG_API int npg_particles_set(npg_particles *P, const double *xyz, double t0) {
+    NPG_REQUIRE(P && (P->n == 0 || xyz), "npg_particles_set: NULL argument");
+    NPG_REQUIRE(std::isfinite(t0), "npg_particles_set: t0 is not finite");
+    NPG_HIP(hipSetDevice(P->ctx->device));
+    NPG_HIP(hipStreamSynchronize(P->ctx->stream));
+    const size_t n = (size_t)P->n;
+    P->t = t0;
+    if (n == 0) return NPG_OK;
+    const std::vector<double> nan(n, std::numeric_limits<double>::quiet_NaN());
+    NPG_HIP(hipMemcpy(P->xyz, xyz, n * 3 * sizeof(double), hipMemcpyHostToDevice));
+    NPG_HIP(hipMemcpy(P->t_lost, nan.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    NPG_HIP(hipMemset(P->cell, 0xff, n * sizeof(int32_t)));          // -1
+    NPG_HIP(hipMemset(P->status, 0, n * sizeof(int32_t)));
+    NPG_HIP(hipMemset(P->wind, 0, n * 3 * sizeof(int32_t)));
+    NPG_HIP(hipDeviceSynchronize());
+    return NPG_OK;
+}
+
+NPG_API int npg_particles_set_period(npg_particles *P, const double *L) {
+    NPG_REQUIRE(P && L, "npg_particles_set_period: NULL argument");
+    for (int a = 0; a < 3; ++a)
+        NPG_REQUIRE(std::isfinite(L[a]) && L[a] >= 0.0, "npg_particles_set_period: L[%d] = %g must be finite and >= 0 (0 = not periodic)", a, L[a]);
+    for (int a = 0; a < 3; ++a) P->L[a] = L[a];
+    return NPG_OK;
+}
+
+NPG_API int npg_particles_advance(npg_particles *P, npg_fe *fe, npg_locator *loc, const npg_vec *x_a, const npg_vec *x_b, double s0,
+                                  double s1, double dt, int64_t nsub) {
+    NPG_REQUIRE(P && fe && loc && x_a && x_b, "npg_particles_advance: NULL argument");
+    NPG_REQUIRE(fe->ctx == P->ctx && loc->ctx == P->ctx && x_a->ctx == P->ctx && x_b->ctx == P->ctx,
+                "npg_particles_advance: arguments of different contexts");
+    NPG_REQUIRE(!loc->part, "npg_particles_advance: a partitioned locator (npg_locator_create_cells) is refused - a particle that "
+                "leaves the rank's cells would have to be handed to another rank, which is not implemented");
+    NPG_REQUIRE(loc->ncell == fe->d.ncell, "npg_particles_advance: the locator was built for another mesh (an embedded 2-D engine "
+                "has no locator: particles need a tetrahedral mesh)");
+    NPG_REQUIRE(x_a->n == fe->n_inv && x_b->n == fe->n_inv, "npg_particles_advance: the flow vectors have %lld and %lld entries, expected %lld",
+                (long long)x_a->n, (long long)x_b->n, (long long)fe->n_inv);
+    const char *err = check_particle_call(s0, s1, dt, nsub);
+    NPG_REQUIRE(!err, "npg_particles_advance: %s", err);
+    const ParticleCall call = make_particle_call(P->t, s0, s1, dt, nsub);
+    if (P->n == 0) {
+        P->t += dt;
+        return NPG_OK;
+    }
+    NPG_HIP(hipSetDevice(P->ctx->device));
+    const FeDev &d = fe->d;
+    const DevTables t{d.cu, d.cp, d.cb, d.G, d.u_diri, d.b_diri, d.ncell, d.nb};
+    const ParticleMesh m{loc->grid, loc->bin_ptr, loc->bin_cells, loc->geo, {P->L[0], P->L[1], P->L[2]}};
+    const dim3 grid((unsigned)((P->n + kBlock - 1) / kBlock)), block(kBlock);
+    hipStream_t st = P->ctx->stream;
+    if (x_a->d != x_b->d)
+        hipLaunchKernelGGL(k_particles_advance<true>, grid, block, 0, st, m, t, x_a->d, x_b->d, call, nsub, P->n, P->xyz, P->cell,
+                           P->status, P->wind, P->t_lost);
+    else
+        hipLaunchKernelGGL(k_particles_advance<false>, grid, block, 0, st, m, t, x_a->d, x_a->d, call, nsub, P->n, P->xyz, P->cell,
+                           P->status, P->wind, P->t_lost);
+    NPG_HIP(hipGetLastError());
+    P->t += dt;
+    return NPG_OK;
+}
+
+NPG_API int npg_particles_download(const npg_particles *P, double *xyz, int32_t *cell, int32_t *status, int32_t *wind, double *t_lost) {
+    NPG_REQUIRE(P, "npg_particles_download: NULL handle");
+    NPG_HIP(hipSetDevice(P->ctx->device));
+    NPG_HIP(hipStreamSynchronize(P->ctx->stream));
+    const size_t n = (size_t)P->n;
+    if (n == 0) return NPG_OK;
+    if (xyz) NPG_HIP(hipMemcpy(xyz, P->xyz, n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (cell) NPG_HIP(hipMemcpy(cell, P->cell, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (status) NPG_HIP(hipMemcpy(status, P->status, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (wind) NPG_HIP(hipMemcpy(wind, P->wind, n * 3 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (t_lost) NPG_HIP(hipMemcpy(t_lost, P->t_lost, n * sizeof(double), hipMemcpyDeviceToHost));
+    return NPG_OK;
+}
+
+NPG_API int npg_particles_positions(const npg_particles *P, npg_vec *out) {
+    NPG_REQUIRE(P && out, "npg_particles_positions: NULL argument");
+    NPG_REQUIRE(out->ctx == P->ctx && out->n == 3 * P->n, "npg_particles_positions: out must hold 3 n = %lld doubles of the particles' context",
+                (long long)(3 * P->n));
+    if (P->n == 0) return NPG_OK;
+    NPG_HIP(hipMemcpyAsync(out->d, P->xyz, (size_t)P->n * 3 * sizeof(double), hipMemcpyDeviceToDevice, P->ctx->stream));
+    return NPG_OK;
+}

@@ -1380,3 +1380,104 @@ NPG_API int npg_integrals_compute(npg_integrals *I, const npg_vec *x_inv, const 
     }
     return NPG_OK;
 }
+
+// ---- Lagrangian particles in the flow (csrc/particles.hip on the host): the RK4 step, the remembered cell, the periodic wrap and the
+// rule for leaving the mesh are the SAME code (csrc/particles_core.h), looped over the particles with OpenMP -------------------------
+#include "../csrc/particles_core.h"
+
+struct npg_particles {
+    npg_ctx *ctx = nullptr;
+    int64_t n = 0;
+    double t = 0.0;
+    double L[3] = {0.0, 0.0, 0.0};
+    std::vector<double> xyz, t_lost;
+    std::vector<int32_t> cell, status, wind;
+};
+
+NPG_API int npg_particles_create(npg_ctx *ctx, int64_t n, npg_particles **out) {
+    REQUIRE(ctx && out, "npg_particles_create: NULL argument");
+    REQUIRE(n >= 0 && n <= ((int64_t)1 << 32), "npg_particles_create: 0 .. 2^32 particles, got %lld", (long long)n);
+    npg_particles *P = new npg_particles();
+    P->ctx = ctx;
+    P->n = n;
+    P->xyz.assign((size_t)n * 3, 0.0);
+    P->t_lost.assign((size_t)n, NAN);
+    P->cell.assign((size_t)n, -1);
+    P->status.assign((size_t)n, 0);
+    P->wind.assign((size_t)n * 3, 0);
+    *out = P;
+    return NPG_OK;
+}
+NPG_API int npg_particles_destroy(npg_particles *P) {
+    delete P;
+    return NPG_OK;
+}
+NPG_API int npg_particles_set(npg_particles *P, const double *xyz, double t0) {
+    REQUIRE(P && (P->n == 0 || xyz), "npg_particles_set: NULL argument");
+    REQUIRE(std::isfinite(t0), "npg_particles_set: t0 is not finite");
+    P->t = t0;
+    if (P->n) std::copy(xyz, xyz + 3 * P->n, P->xyz.begin());
+    std::fill(P->t_lost.begin(), P->t_lost.end(), NAN);
+    std::fill(P->cell.begin(), P->cell.end(), -1);
+    std::fill(P->status.begin(), P->status.end(), 0);
+    std::fill(P->wind.begin(), P->wind.end(), 0);
+    return NPG_OK;
+}
+NPG_API int npg_particles_set_period(npg_particles *P, const double *L) {
+    REQUIRE(P && L, "npg_particles_set_period: NULL argument");
+    for (int a = 0; a < 3; ++a)
+        REQUIRE(std::isfinite(L[a]) && L[a] >= 0.0, "npg_particles_set_period: L[%d] = %g must be finite and >= 0 (0 = not periodic)", a, L[a]);
+    for (int a = 0; a < 3; ++a) P->L[a] = L[a];
+    return NPG_OK;
+}
+NPG_API int npg_particles_advance(npg_particles *P, npg_fe *fe, npg_locator *loc, const npg_vec *x_a, const npg_vec *x_b, double s0,
+                                  double s1, double dt, int64_t nsub) {
+    REQUIRE(P && fe && loc && x_a && x_b, "npg_particles_advance: NULL argument");
+    REQUIRE(fe->ctx == P->ctx && loc->ctx == P->ctx && x_a->ctx == P->ctx && x_b->ctx == P->ctx,
+            "npg_particles_advance: arguments of different contexts");
+    REQUIRE(loc->ncell == fe->ncell, "npg_particles_advance: the locator was built for another mesh (an embedded 2-D engine has no "
+            "locator: particles need a tetrahedral mesh)");
+    REQUIRE(x_a->n == fe->n_inv && x_b->n == fe->n_inv, "npg_particles_advance: the flow vectors have %lld and %lld entries, expected %lld",
+            (long long)x_a->n, (long long)x_b->n, (long long)fe->n_inv);
+    const char *err = npg::check_particle_call(s0, s1, dt, nsub);
+    REQUIRE(!err, "npg_particles_advance: %s", err);
+    const npg::ParticleCall call = npg::make_particle_call(P->t, s0, s1, dt, nsub);
+    const HostTables t{fe, fe->u_diri.data(), fe->b_diri.data(), fe->nb};
+    const npg::BinTables &bt = loc->t;
+    const npg::ParticleMesh m{bt.grid, bt.bin_ptr.data(), bt.bin_cells.data(), bt.geo.data(), {P->L[0], P->L[1], P->L[2]}};
+    const bool blend = x_a->d != x_b->d;
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < P->n; ++i) {
+        if (P->status[(size_t)i] != 0) continue;         // lost: nothing moves it
+        npg::ParticleState p;
+        for (int a = 0; a < 3; ++a) p.x[a] = P->xyz[(size_t)3 * i + a], p.wind[a] = P->wind[(size_t)3 * i + a];
+        p.c = P->cell[(size_t)i];
+        const int64_t done = blend ? npg::particle_advance<true>(m, t, x_a->d, x_b->d, call, nsub, p)
+                                   : npg::particle_advance<false>(m, t, x_a->d, x_a->d, call, nsub, p);
+        if (done < nsub) {
+            P->status[(size_t)i] = 1;
+            P->t_lost[(size_t)i] = done > 0 ? call.t + (double)done * call.h : call.t;
+            if (done < 0) continue;                      // lost where the call found it: the seed stays as it was given
+        }
+        for (int a = 0; a < 3; ++a) P->xyz[(size_t)3 * i + a] = p.x[a], P->wind[(size_t)3 * i + a] = p.wind[a];
+        P->cell[(size_t)i] = p.c;
+    }
+    P->t += dt;
+    return NPG_OK;
+}
+NPG_API int npg_particles_download(const npg_particles *P, double *xyz, int32_t *cell, int32_t *status, int32_t *wind, double *t_lost) {
+    REQUIRE(P, "npg_particles_download: NULL handle");
+    if (xyz) std::copy(P->xyz.begin(), P->xyz.end(), xyz);
+    if (cell) std::copy(P->cell.begin(), P->cell.end(), cell);
+    if (status) std::copy(P->status.begin(), P->status.end(), status);
+    if (wind) std::copy(P->wind.begin(), P->wind.end(), wind);
+    if (t_lost) std::copy(P->t_lost.begin(), P->t_lost.end(), t_lost);
+    return NPG_OK;
+}
+NPG_API int npg_particles_positions(const npg_particles *P, npg_vec *out) {
+    REQUIRE(P && out, "npg_particles_positions: NULL argument");
+    REQUIRE(out->ctx == P->ctx && out->n == 3 * P->n, "npg_particles_positions: out must hold 3 n = %lld doubles of the particles' context",
+            (long long)(3 * P->n));
+    std::copy(P->xyz.begin(), P->xyz.end(), out->d);
+    return NPG_OK;
+}
