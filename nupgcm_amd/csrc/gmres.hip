@@ -101,6 +101,9 @@ struct GDev {
                           // into the row Q1 points at, which also takes hcol1 / wnorm2 out of the orthogonalisation kernel
     int vdots;            // ... and, with the fp32-stored basis, column j is formed where it is first read: the dots kernel of
                           // step j computes it from wt and T[j].beta and stores it, the Arnoldi kernel's epilogue stores w only
+    int fusedrows;        // ... and steps of up to kFusedMaxCols columns run dots, fold and update as ONE resident launch
+                          // (k_gmres_rows_fused), which keeps a thread's last trips on chip across a grid-wide hand-off
+    struct RowsHandOff *ho;   // that hand-off's counters, generation and status word (monotonic: nothing is reset between launches)
     Snap *C, *T;
     double *c, *s, *z, *R, *hcol1, *wnorm2;
     double *hist;
@@ -769,6 +772,339 @@ __global__ void __launch_bounds__(kRB) k_gmres_fold_first(GDev d, int j, double 
     }
 }
 
+// ---- one resident launch for the Gram-Schmidt sums, their fold and the update (one GPU, fast kernels, fp32-stored basis) ----
+// k_gmres_rows_fused does, for a step of at most kFusedMaxCols columns, the work of k_gmres_dots_rows<., float, true>,
+// k_gmres_fold_first and k_gmres_orth_rows<., true, float> - same grid, same rows per thread, same partial rows, same orders of
+// summation, so no bit of any result changes - and keeps what the update would read a second time on chip:
+//   phase 1  the dots pass.  A thread's trips rotate through B register buffers (trip t lives in buffer t % B; trip t + B - 1 is
+//            requested before trip t's arithmetic), so when the pass ends the registers still hold the thread's LAST B trips - the
+//            basis entries, the freshly formed v_j among them, and the w pair.  The (up to) L trips before those are copied to
+//            LDS as they leave their buffer.
+//   hand-off the workgroup stores its partial row write-through and takes a ticket on the counter of its shard (blockIdx % 8).
+//            The last arriver of shard s adds the rows s, s + 8, ... upwards from 0.0 - slice s of reduce_partials<kRB / 32,
+//            kMaxRowsI> - and takes a ticket on the top counter; the last of those adds the eight slice sums upwards from 0.0,
+//            stores the folded row, hcol1[j] and wnorm2[j], and publishes the generation.  One lane per workgroup polls it.
+//   phase 2  the update, trips in ascending order: the early ones are read again from memory, then those in LDS, then the registers.
+// Counters and generation only ever grow (a launch reads the generation E it starts from; its targets are (E + 1) x the number of
+// arrivals), so a replayed graph needs no memset node.  Every workgroup must be resident: the host launches this kernel only on a
+// grid the occupancy query admits (rows_fused_blocks_per_cu).  The poll is bounded by the wall clock: on expiry the workgroup sets
+// the status word and leaves; a launch that finds it set does nothing; npg_gmres_solve reports it as an error.
+constexpr int kFusedMaxCols = 16;   // (an instance for 20 columns with two register buffers spills: 168 registers + 164 B of scratch)
+constexpr int kHoLine = 16;                      // 8-byte words per 128-byte line: every polled word has a line of its own
+constexpr int kHoShards = kRB / 32;              // = the slices of reduce_partials<kRB / 32, kMaxRowsI>
+struct RowsHandOff {
+    unsigned long long gen[kHoLine];
+    unsigned long long top[kHoLine];
+    unsigned long long shard[kHoShards][kHoLine];
+    unsigned long long status[kHoLine];
+    double slice[kHoShards][kKP];
+};
+constexpr long long kHandOffTicks = 200000000;   // wall_clock64() counts at 100 MHz: two seconds, against a launch of ~50 us
+
+// register buffers B and LDS trips L of the instance for C columns: B (2C + 8) + 2C registers in phase 1, L (8C + 16) bytes of LDS
+// per thread (three workgroups per CU: 168 registers and ~53 KB)
+template <int C> struct FusedGeom { static constexpr int B = C <= 8 ? 4 : C <= 12 ? 3 : 2, L = C <= 8 ? 2 : 1; };
+static_assert(kFusedMaxCols % 4 == 0, "instances come in steps of four columns");
+
+#define NPG_LD_AGENT(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define NPG_ST_AGENT(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+
+template <int C>
+struct RowTrip {
+    float2 v[C];
+    double w0, w1;
+    // the loads of RowPair<., VD>::load, for C columns (VD: t = wt of the two rows, column j is not read)
+    template <bool VD>
+    __device__ __forceinline__ void load(const GDev &d, int64_t blk, int j, double2 &t) {
+        const int64_t r0 = 2 * (blk * kRB + threadIdx.x);
+        const bool valid = r0 < d.n, two = r0 + 1 < d.n;
+        const int64_t rc = valid ? r0 : 0;
+        const int jl = VD ? j - 1 : j;
+#pragma unroll
+        for (int k = 0; k < C; ++k) {
+            float2 f = make_float2(0.f, 0.f);
+            if (k <= jl) f = *reinterpret_cast<const float2 *>(d.Vf + (size_t)k * (size_t)d.ldv + (size_t)rc);
+            if (!two) f.y = 0.f;
+            v[k] = f;
+        }
+        const double2 ww = *reinterpret_cast<const double2 *>(d.w + rc);
+        if constexpr (VD) t = *reinterpret_cast<const double2 *>(d.wt + rc);
+        w0 = valid ? ww.x : 0.0;
+        w1 = (valid && two) ? ww.y : 0.0;
+    }
+};
+
+template <int C>
+__global__ void __launch_bounds__(kRB, 3) k_gmres_rows_fused(GDev d, int j) {
+    constexpr int B = FusedGeom<C>::B, L = FusedGeom<C>::L;
+    static_assert(kMaxG == kHoShards * kMaxRowsI && kMaxRowsI % kHoShards == 0, "a shard is one slice of the fold");
+    __shared__ float2 lds_v[L * C * kRB];
+    __shared__ double lds_w[L * 2 * kRB];
+    __shared__ double tmp[(kRB / 32) * kKP];
+    __shared__ double red[kKP];
+    __shared__ int sh_role, sh_ok;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const Snap *Tj = d.T + j;
+    if (Tj->done != 0) {
+        // the solve has ended: both partial rows read as zeros, as the separate kernels leave them, and nobody waits
+        if (tid < kKP) {
+            d.P1[(size_t)blockIdx.x * kKP + tid] = 0.0;
+            d.P2[(size_t)blockIdx.x * kKP + tid] = 0.0;
+        }
+        return;
+    }
+    RowsHandOff *ho = d.ho;
+    if (NPG_LD_AGENT(&ho->status[0]) != 0) return;            // an earlier hand-off gave up: the host is about to report it
+    unsigned long long E = 0;
+    if (tid == 0) E = NPG_LD_AGENT(&ho->gen[0]);                // hand-offs completed so far (nobody adds to it before every
+                                                                // workgroup of this launch has arrived, i.e. has read it)
+    const int G = gridDim.x;
+    const int64_t nblk = ((int64_t)d.n + 2 * kRB - 1) / (2 * kRB);
+    const int nt = (int64_t)blockIdx.x < nblk ? (int)((nblk - 1 - blockIdx.x) / G) + 1 : 0;      // this workgroup's trips
+    const int nreg = nt < B ? nt : B;                          // trips [nt - nreg, nt) end the pass in registers,
+    const int nlds = nt - nreg < L ? nt - nreg : L;            // [ne, ne + nlds) in LDS,
+    const int ne = nt - nreg - nlds;                           // [0, ne) are read again
+    auto blk_of = [&](int t) { return (int64_t)blockIdx.x + (int64_t)t * G; };
+
+    // ---- phase 1: v_j, the sums and ||w||^2 ----
+    RowTrip<C> buf[B];
+    double2 unused;
+    double nrm = 0.0;
+    {
+        double acc[C];
+#pragma unroll
+        for (int k = 0; k < C; ++k) acc[k] = 0.0;
+        double2 tq[B];
+        const double inv_beta = 1.0 / Tj->beta;                // (T[j]: written by the Arnoldi launch before this one)
+#pragma unroll
+        for (int s = 0; s < B - 1; ++s)
+            if (s < nt) buf[s].template load<true>(d, blk_of(s), j, tq[s]);
+        for (int base = 0; base < nt; base += B) {
+#pragma unroll
+            for (int s = 0; s < B; ++s) {
+                const int t = base + s;
+                if (t < nt) {
+                    const int sp = (s + B - 1) % B;            // the buffer of trip t - 1, whose arithmetic is done
+                    if (t + B - 1 < nt) {
+                        if (t - 1 >= ne) {                     // (then t - 1 < ne + nlds: trip t - 1 is not among the last B)
+                            const int sl = t - 1 - ne;
+#pragma unroll
+                            for (int k = 0; k < C; ++k) lds_v[(sl * C + k) * kRB + tid] = buf[sp].v[k];
+                            lds_w[(sl * 2 + 0) * kRB + tid] = buf[sp].w0;
+                            lds_w[(sl * 2 + 1) * kRB + tid] = buf[sp].w1;
+                        }
+                        buf[sp].template load<true>(d, blk_of(t + B - 1), j, tq[sp]);      // in flight during this trip's arithmetic
+                    }
+                    RowTrip<C> &cur = buf[s];
+                    const int64_t r0 = 2 * (blk_of(t) * kRB + tid);
+                    const bool valid = r0 < d.n, two = r0 + 1 < d.n;
+                    float2 vj = make_float2((float)(tq[s].x * inv_beta), (float)(tq[s].y * inv_beta));
+                    if (valid) {
+                        float *col = d.Vf + (size_t)j * (size_t)d.ldv + (size_t)r0;
+                        if (two)
+                            *reinterpret_cast<float2 *>(col) = vj;
+                        else
+                            *col = vj.x;
+                    }
+                    if (!two) vj.y = 0.f;
+#pragma unroll
+                    for (int k = 0; k < C; ++k)
+                        if (k == j) cur.v[k] = vj;             // (wave-uniform)
+#pragma unroll
+                    for (int k = 0; k < C; ++k) acc[k] += (double)cur.v[k].x * cur.w0 + (double)cur.v[k].y * cur.w1;
+                    nrm += cur.w0 * cur.w0 + cur.w1 * cur.w1;
+                }
+            }
+        }
+        // the partial row of store_partial_row_rows (columns >= C sum to 0.0 there too), stored write-through
+        __syncthreads();
+        if (lane < kKP) tmp[wave * kKP + lane] = 0.0;
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < C; ++k) {
+            const double s = group_sum_dpp<64>(acc[k]);
+            if (lane == 0) tmp[wave * kKP + k] = s;
+        }
+        const double sn = group_sum_dpp<64>(nrm);
+        if (lane == 0) tmp[wave * kKP + kNormSlot] = sn;
+        __syncthreads();
+        if (tid < kKP) {
+            double s = 0.0;
+#pragma unroll
+            for (int w = 0; w < kRB / 64; ++w) s += tmp[w * kKP + tid];
+            NPG_ST_AGENT(d.P1 + (size_t)blockIdx.x * kKP + tid, s);
+        }
+    }
+
+    // ---- hand-off ----
+    // (the rows are stored by wave 0, which also signals: its own wait is all the ordering the ticket needs)
+    const int shard = blockIdx.x % kHoShards;
+    const int cnt = (G - shard + kHoShards - 1) / kHoShards;   // workgroups (= partial rows) of this shard
+    const int nsh = G < kHoShards ? G : kHoShards;             // shards that have any
+    if (wave == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (tid == 0) {
+        const unsigned long long old = __hip_atomic_fetch_add(&ho->shard[shard][0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        sh_role = (old + 1 == (E + 1) * (unsigned long long)cnt) ? 1 : 0;
+    }
+    __syncthreads();
+    if (sh_role == 1) {
+        // last arriver of the shard: slice `shard` of the fold.  Thread (i, k) loads rows shard + 8 (8 m + i), m = 0 .. 11, all at
+        // once; the 96 adds are made in row order by the threads k of the first group, eight rows per round through LDS
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        constexpr int M = kMaxRowsI / kHoShards;
+        const int k = tid & (kKP - 1), i = tid >> 5;
+        double v[M];
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            const int q = m * kHoShards + i;
+            const unsigned long long bits = NPG_LD_AGENT(reinterpret_cast<const unsigned long long *>(d.P1) +
+                                                         (size_t)(q < cnt ? shard + kHoShards * q : shard) * kKP + k);
+            v[m] = q < cnt ? __longlong_as_double(bits) : 0.0;
+        }
+        double s = 0.0;
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            __syncthreads();
+            tmp[i * kKP + k] = v[m];
+            __syncthreads();
+            if (tid < kKP) {
+#pragma unroll
+                for (int ii = 0; ii < kHoShards; ++ii) s += tmp[ii * kKP + tid];
+            }
+        }
+        if (tid < kKP) NPG_ST_AGENT(&ho->slice[shard][tid], s);
+        if (wave == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (tid == 0) {
+            const unsigned long long old = __hip_atomic_fetch_add(&ho->top[0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (old + 1 == (E + 1) * (unsigned long long)nsh) sh_role = 2;
+        }
+        __syncthreads();
+        if (sh_role == 2) {
+            // last arriver of all: the eight slice sums upwards from 0.0, then the generation
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            if (tid < kKP) {
+                double sv[kHoShards];
+#pragma unroll
+                for (int sl = 0; sl < kHoShards; ++sl) {
+                    const unsigned long long bits = NPG_LD_AGENT(reinterpret_cast<const unsigned long long *>(&ho->slice[sl][tid]));
+                    sv[sl] = sl < nsh ? __longlong_as_double(bits) : 0.0;
+                }
+                double tsum = 0.0;
+#pragma unroll
+                for (int sl = 0; sl < kHoShards; ++sl) tsum += sv[sl];
+                NPG_ST_AGENT(const_cast<double *>(d.Q1) + tid, tsum);
+                d.hcol1[j * kKP + tid] = (tid <= j) ? tsum : 0.0;
+                if (tid == kNormSlot) d.wnorm2[j] = tsum;
+            }
+            if (wave == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (tid == 0) NPG_ST_AGENT(&ho->gen[0], E + 1);
+        }
+    }
+    // the first early trip's rows do not depend on h: their loads go out before the wait
+    RowTrip<C> early;
+    if (ne > 0) early.template load<false>(d, blk_of(0), j, unused);
+    if (tid == 0) {
+        int ok = 1;
+        const long long t0 = wall_clock64();
+        while (NPG_LD_AGENT(&ho->gen[0]) < E + 1) {
+            __builtin_amdgcn_s_sleep(8);
+            if (wall_clock64() - t0 > kHandOffTicks) {
+                NPG_ST_AGENT(&ho->status[0], 1ull);
+                ok = 0;
+                break;
+            }
+        }
+        sh_ok = ok;
+    }
+    if (wave == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
+    if (!sh_ok) return;                                        // gave up: no update, the status word says so
+    if (tid < kKP) {
+        const unsigned long long bits = NPG_LD_AGENT(reinterpret_cast<const unsigned long long *>(d.Q1) + tid);
+        red[tid] = __longlong_as_double(bits);
+    }
+    __syncthreads();
+
+    // ---- phase 2: wt = w - V h, the gather copy and ||wt||^2 ----
+    double h[C];
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+        const double hv = (k <= j) ? red[k] : 0.0;
+        const unsigned long long b = __double_as_longlong(hv);
+        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b), hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
+        h[k] = __longlong_as_double(((unsigned long long)hi << 32) | lo);
+    }
+    nrm = 0.0;
+    auto update = [&](const RowTrip<C> &cur, int t) {
+        const int64_t r0 = 2 * (blk_of(t) * kRB + tid);
+        const bool valid = r0 < d.n, two = r0 + 1 < d.n;
+        double p0 = cur.w0, p1 = cur.w1;
+#pragma unroll
+        for (int k = 0; k < C; ++k) {
+            // (opaque to the optimiser: it would otherwise keep phase 1's widened copies of the kept entries alive across the
+            //  hand-off, twice the registers)
+            float vx = cur.v[k].x, vy = cur.v[k].y;
+            asm("" : "+v"(vx), "+v"(vy));
+            p0 -= h[k] * (double)vx;
+            p1 -= h[k] * (double)vy;
+        }
+        if (valid) {
+            if (two)
+                *reinterpret_cast<double2 *>(d.wt + r0) = make_double2(p0, p1);
+            else
+                d.wt[r0] = p0;
+            if (d.xg.p) {
+                d.xg.p[d.xg.pos((int)r0)] = (float)p0;
+                if (two) d.xg.p[d.xg.pos((int)r0 + 1)] = (float)p1;
+            }
+        } else {
+            p0 = 0.0;                                           // (a clamped lane read row 0's basis entries)
+            p1 = 0.0;
+        }
+        if (!two) p1 = 0.0;
+        nrm += p0 * p0 + p1 * p1;
+    };
+    for (int t = 0; t < ne; ++t) {
+        update(early, t);                                       // (one buffer: the registers hold the last trips)
+        if (t + 1 < ne) early.template load<false>(d, blk_of(t + 1), j, unused);
+    }
+#pragma unroll
+    for (int sl = 0; sl < L; ++sl) {
+        if (sl < nlds) {
+#pragma unroll
+            for (int k = 0; k < C; ++k) early.v[k] = lds_v[(sl * C + k) * kRB + tid];
+            early.w0 = lds_w[(sl * 2 + 0) * kRB + tid];
+            early.w1 = lds_w[(sl * 2 + 1) * kRB + tid];
+            update(early, ne + sl);
+        }
+    }
+    {
+        const int tr = nt - nreg, rot = tr % B;                // the oldest trip in registers and its buffer
+#pragma unroll
+        for (int ro = 0; ro < B; ++ro) {
+            if (ro == rot) {
+#pragma unroll
+                for (int r = 0; r < B; ++r)
+                    if (r < nreg) update(buf[(ro + r) % B], tr + r);
+            }
+        }
+    }
+    // the exactly summed norm only: one wave reduction, zeros in the h2 slots
+    const double sn2 = group_sum_dpp<64>(nrm);
+    __syncthreads();
+    if (lane == 0) tmp[wave] = sn2;
+    __syncthreads();
+    if (tid < kKP) {
+        double tt = 0.0;
+        if (tid == kNormSlot)
+            for (int w = 0; w < kRB / 64; ++w) tt += tmp[w];
+        d.P2[(size_t)blockIdx.x * kKP + tid] = tt;
+    }
+}
+
 // ---- K2 ---------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kKB, 6) k_gmres_orth(GDev d, int j) {
     __shared__ KShared sh;
@@ -920,7 +1256,7 @@ __global__ void __launch_bounds__(1024) k_reduce_rows(const double *__restrict__
 using namespace npg;
 
 // npg_gmres_last_config: entries of the report, in this order (nupgcm_amd/iterative_solvers.py names them)
-constexpr int kCfgLen = 17;
+constexpr int kCfgLen = 18;
 
 struct npg_gmres {
     npg_ctx *ctx = nullptr;
@@ -964,6 +1300,10 @@ struct npg_gmres {
     npg_halo *halo = nullptr;
     double *Rg = nullptr;         // 3 x 32 doubles: all-reduced rows (distributed mode)
     int64_t n_ghost = 0;
+    RowsHandOff *ho = nullptr;    // hand-off state of k_gmres_rows_fused (allocated and zeroed on first use)
+    unsigned long long *h_ho = nullptr;   // pinned, two slots: its status word as each cycle left it
+    int fused_blocks = -1;        // workgroups of that kernel per CU (rows_fused_blocks_per_cu), -1: not asked yet
+    bool fused_off = false;       // a hand-off has timed out: the workspace keeps to the separate launches
     int32_t cfg[kCfgLen] = {};    // the kernel instances the last solve launched (npg_gmres_last_config)
     bool have_cfg = false;
 };
@@ -1002,6 +1342,32 @@ static void launch_rows_kernel(const GDev &d, int j, hipStream_t st, bool orth) 
         case 3: launch_rows<3>(d, j, st, orth); break;
         default: launch_rows<4>(d, j, st, orth); break;
     }
+}
+
+static void launch_rows_fused(const GDev &d, int j, hipStream_t st) {
+    switch ((j + 4) / 4) {       // instances for 4, 8, ... kFusedMaxCols columns
+        case 1: hipLaunchKernelGGL(k_gmres_rows_fused<4>, dim3(d.GR), dim3(kRB), 0, st, d, j); break;
+        case 2: hipLaunchKernelGGL(k_gmres_rows_fused<8>, dim3(d.GR), dim3(kRB), 0, st, d, j); break;
+        case 3: hipLaunchKernelGGL(k_gmres_rows_fused<12>, dim3(d.GR), dim3(kRB), 0, st, d, j); break;
+        default: hipLaunchKernelGGL(k_gmres_rows_fused<16>, dim3(d.GR), dim3(kRB), 0, st, d, j); break;
+    }
+}
+// Workgroups of k_gmres_rows_fused that one CU holds at a time, over the instances: the occupancy query's answer, corrected as it
+// has to be for 256-thread workgroups on gfx950 - min(API, 8, floor(800 / (ceil(sgpr / 16) 16 + 16))) - with the largest scalar
+// register count a kernel can have (every instance is reported at 106, profiles/gmres_fusedrows_ab.txt), so the bound errs low.  0: unknown.
+template <int C>
+static int rows_fused_blocks() {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_gmres_rows_fused<C>, kRB, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    return nb;
+}
+static int rows_fused_blocks_per_cu() {
+    constexpr int kSgprMax = 112;
+    const int api = std::min({rows_fused_blocks<4>(), rows_fused_blocks<8>(), rows_fused_blocks<12>(), rows_fused_blocks<16>()});
+    return std::min({api, 8, 800 / ((kSgprMax + 15) / 16 * 16 + 16)});
 }
 
 // the Arnoldi kernel instance for this matrix / input form: tiles [t0, t1) on `grid` workgroups
@@ -1115,6 +1481,10 @@ static int launch_cycle_L(const GDev &d, hipStream_t st, hipEvent_t *pev, npg_gm
         if (d.split) {
             launch_arnoldi_split<L>(d, std::min(d.G1, std::max(1, a_nt)), j, 0, a_nt, st, pev ? pev[2 * j] : nullptr,
                                     pev ? pev[2 * j + 1] : nullptr);
+            if (d.fusedrows && j < kFusedMaxCols) {
+                launch_rows_fused(d, j, st);     // sums, fold and update in one resident launch
+                continue;
+            }
             launch_rows_kernel(d, j, st, false);
             if (d.onefold) hipLaunchKernelGGL(k_gmres_fold_first, dim3(1), dim3(kRB), 0, st, d, j, const_cast<double *>(d.Q1));
         } else {
@@ -1216,11 +1586,12 @@ NPG_API int npg_gmres_destroy(npg_gmres *ws) {
     }
     for (hipEvent_t e : ws->pev) hipEventDestroy(e);
     void *ptrs[] = {ws->Vi, ws->w, ws->wt, ws->P1, ws->P2, ws->PR, ws->C, ws->T, ws->c, ws->s,
-                    ws->z, ws->R, ws->hcol1, ws->wnorm2, ws->hist, ws->prm, ws->Rg, ws->xg};
+                    ws->z, ws->R, ws->hcol1, ws->wnorm2, ws->hist, ws->prm, ws->Rg, ws->xg, ws->ho};
     for (void *p : ptrs)
         if (p) hipFree(p);
     if (ws->h_C) hipHostFree(ws->h_C);
     if (ws->h_prm) hipHostFree(ws->h_prm);
+    if (ws->h_ho) hipHostFree(ws->h_ho);
     delete ws;
     return NPG_OK;
 }
@@ -1407,6 +1778,25 @@ NPG_API int npg_gmres_solve(npg_gmres *ws, const npg_csr *A_in, int precond_kind
     const char *onefold_env = getenv("NPG_GMRES_ONEFOLD");
     d.onefold = (!dist && d.split && d.fast && !(onefold_env && atoi(onefold_env) == 0)) ? 1 : 0;
     d.vdots = (d.onefold && d.Vf) ? 1 : 0;
+    // ... and, with the fp32-stored basis, the three row launches of a step as one resident launch (k_gmres_rows_fused;
+    // NPG_GMRES_FUSEDROWS=0: the separate launches).  It is the onefold arrangement in one kernel, so it selects that arrangement
+    // for the cycle's other steps too; NPG_GMRES_ONEFOLD=0 chooses among the separate launches, i.e. with NPG_GMRES_FUSEDROWS=0 or
+    // where the fused kernel does not apply.  Only on a grid that is resident as a whole: the hand-off waits for every workgroup.
+    const char *fusedrows_env = getenv("NPG_GMRES_FUSEDROWS");
+    if (!dist && d.split && d.fast && d.Vf && !d.rev && !ws->fused_off && !(fusedrows_env && atoi(fusedrows_env) == 0)) {
+        if (ws->fused_blocks < 0) ws->fused_blocks = rows_fused_blocks_per_cu();
+        if (d.GR <= ctx->num_cu * ws->fused_blocks) {
+            if (!ws->ho) {
+                NPG_HIP(hipMalloc((void **)&ws->ho, sizeof(RowsHandOff)));
+                NPG_HIP(hipMemsetAsync(ws->ho, 0, sizeof(RowsHandOff), st));
+                NPG_HIP(hipHostMalloc((void **)&ws->h_ho, 2 * sizeof(unsigned long long), hipHostMallocDefault));
+                ws->h_ho[0] = ws->h_ho[1] = 0;
+            }
+            d.fusedrows = 1;
+            d.ho = ws->ho;
+            d.onefold = d.vdots = 1;
+        }
+    }
     if (dist) {
         d.Q1 = ws->Rg;
         d.Q2 = ws->Rg + kKP;
@@ -1489,6 +1879,7 @@ NPG_API int npg_gmres_solve(npg_gmres *ws, const npg_csr *A_in, int precond_kind
                 return rcg;
             }
             NPG_HIP(hipMemcpyAsync(ws->h_C + k, ws->C, sizeof(Snap), hipMemcpyDeviceToHost, st));
+            if (d.fusedrows) NPG_HIP(hipMemcpyAsync(ws->h_ho + k, d.ho->status, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
             NPG_HIP(hipStreamEndCapture(st, &ws->graph[k]));
             NPG_HIP(hipGraphInstantiate(&ws->exec[k], ws->graph[k], nullptr, nullptr, 0));
         }
@@ -1523,6 +1914,7 @@ NPG_API int npg_gmres_solve(npg_gmres *ws, const npg_csr *A_in, int precond_kind
             int rcc = launch_cycle(d, A->lanes, st, nullptr, ws, dist != nullptr);
             if (rcc) return rcc;
             NPG_HIP(hipMemcpyAsync(ws->h_C + slot, ws->C, sizeof(Snap), hipMemcpyDeviceToHost, st));
+            if (d.fusedrows) NPG_HIP(hipMemcpyAsync(ws->h_ho + slot, d.ho->status, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         } else {
             NPG_HIP(hipGraphLaunch(ws->exec[slot], st));
         }
@@ -1530,6 +1922,18 @@ NPG_API int npg_gmres_solve(npg_gmres *ws, const npg_csr *A_in, int precond_kind
         t_launch += std::chrono::duration<double>(std::chrono::steady_clock::now() - l0).count();
         ++n_launch;
         return NPG_OK;
+    };
+    // A hand-off of k_gmres_rows_fused that ran out of time has set the status word: that launch and every later one skipped the
+    // update, so the iterate is not to be trusted.  Report it, re-zero the hand-off state and keep to the separate launches.
+    auto fused_gave_up = [&]() -> int {
+        hipStreamSynchronize(st);
+        hipMemset(ws->ho, 0, sizeof(RowsHandOff));
+        ws->h_ho[0] = ws->h_ho[1] = 0;
+        ws->fused_off = true;
+        ws->have_graph = false;
+        npg::set_error("npg_gmres_solve: the grid-wide hand-off of the fused row kernel timed out (a workgroup was not resident); "
+                       "the iterate is not valid - this workspace uses the separate row launches from now on");
+        return NPG_EHIP;
     };
     if (!ws->profile) {
         // cycle c+1 is enqueued before the host reads the outcome of cycle c: the device never idles waiting for the
@@ -1545,6 +1949,7 @@ NPG_API int npg_gmres_solve(npg_gmres *ws, const npg_csr *A_in, int precond_kind
             }
             NPG_HIP(hipEventSynchronize(ws->ev[cur]));
             last = ws->h_C[cur];
+            if (d.fusedrows && ws->h_ho[cur] != 0) return fused_gave_up();
             if (last.done == 5) {
                 // distributed: ||w||^2 - ||h||^2 met cancellation and the device interrupted the pass before that column.
                 // Carry on from the current iterate with explicitly reduced norms (a second all-reduce per step), for
@@ -1577,11 +1982,11 @@ NPG_API int npg_gmres_solve(npg_gmres *ws, const npg_csr *A_in, int precond_kind
         if (trace)
             fprintf(stderr,
                     "[npg gmres] %s: %lld cycle launches, %.1f us host time per launch, %d iterations, %.1f us wall per "
-                    "iteration, %d second GS passes\n",
+                    "iteration, %d second GS passes, fused rows %d (row grid %d, %d workgroups per CU admitted)\n",
                     eager ? "eager" : "graph", (long long)n_launch, 1e6 * t_launch / (double)n_launch, last.iter,
                     1e6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() /
                         std::max(1, last.iter),
-                    last.nreorth);
+                    last.nreorth, d.fusedrows, d.GR, ws->fused_blocks);
     } else {
         if (ws->pev.empty()) {
             ws->pev.resize(2 * ws->mem);
@@ -1591,7 +1996,9 @@ NPG_API int npg_gmres_solve(npg_gmres *ws, const npg_csr *A_in, int precond_kind
             int rcp = launch_cycle(d, A->lanes, st, ws->pev.data(), ws, dist != nullptr);
             if (rcp) return rcp;
             NPG_HIP(hipMemcpyAsync(ws->h_C, ws->C, sizeof(Snap), hipMemcpyDeviceToHost, st));
+            if (d.fusedrows) NPG_HIP(hipMemcpyAsync(ws->h_ho, d.ho->status, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
             NPG_HIP(hipStreamSynchronize(st));
+            if (d.fusedrows && ws->h_ho[0] != 0) return fused_gave_up();
             last = ws->h_C[0];
             if (last.done == 5) {           // see the pipelined loop: explicit norms from here on
                 d.pyth = 0;
@@ -1623,7 +2030,7 @@ NPG_API int npg_gmres_solve(npg_gmres *ws, const npg_csr *A_in, int precond_kind
         const int32_t cfg[kCfgLen] = {d.split, d.Vf ? 32 : 64, d.fast, d.xg.p ? (d.xg.nbr == 0 ? 2 : 1) : 0, d.wt_ptr ? 1 : 0,
                                       d.wt_ptr ? d.wl : 0, d.wt_ptr ? d.word : 0, A->lanes, A->pk9 ? 1 : 0, dist ? 1 : 0, d.pyth,
                                       a_nt, d.split ? std::min(d.G1, std::max(1, a_nt)) : d.G1, d.split ? d.GR : d.G2, d.n, d.mem,
-                                      d.lazy2};
+                                      d.lazy2, d.fusedrows};
         memcpy(ws->cfg, cfg, sizeof cfg);
         ws->have_cfg = true;
     }

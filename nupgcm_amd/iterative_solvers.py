@@ -91,7 +91,7 @@ class GmresWorkspace(_Workspace):
         return buf[:max(k, 0)]
 
     CONFIG_KEYS = ("split", "basis", "fast", "xg", "windowed", "wl", "word", "L", "pk9", "distributed", "pyth", "tiles",
-                   "grid", "row_grid", "n", "memory", "lazy2")
+                   "grid", "row_grid", "n", "memory", "lazy2", "fusedrows")
 
     def last_config(self):
         """the kernel instances the last solve launched (npg_gmres_last_config): dict over CONFIG_KEYS - split organisation, stored
