@@ -338,7 +338,7 @@ int npg_precond_mg_set_cycle(npg_precond *pc, int gamma);
  * SpMV) stay fp64.  npg_precond_mg_update_level rebuilds the copies. */
 int npg_precond_mg_set_mixed(npg_precond *pc, int on);
 /* NPG_PC_DENSE: A^-1 as n^2 doubles in HBM (2 GB at 16 k unknowns, 8 GB at 31 k: what 288 GB buy) - densified, factorised
- * and inverted once by rocSOLVER (getrf + getri, set-up), applied per solve by a hand-written split-column GEMV at HBM speed.
+ * and inverted once by rocSOLVER (getrf + getrs against the identity, set-up), applied per solve by a hand-written split-column GEMV at HBM speed.
  * For the reference's small meshes, where the scalar-preconditioned GMRES is bound by kernel latency (19 us x 600 iterations),
  * this is the device counterpart of its CPU() path's `lu(A)` + `ldiv!` (src/inversion.jl:55-58, src/iterative_solvers.jl:42-47);
  * behind flexible GMRES it needs 1-2 iterations.  A must be plain CSR.  Call again to follow a re-assembled A. */

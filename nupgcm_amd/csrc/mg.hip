@@ -104,6 +104,11 @@ __global__ void k_densify(const int64_t *__restrict__ rowptr, const int32_t *__r
         for (int64_t k = rowptr[r]; k < rowptr[r + 1]; ++k) dA[r + (int64_t)col[k] * n] = val[k];
 }
 
+// M (column-major n x n, zero-filled) <- I
+__global__ void k_unit_diagonal(double *__restrict__ M, int64_t n) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) M[i + i * n] = 1.0;
+}
+
 // part[s][i] = sum over the s-th chunk of columns j of M[i + j n] x[j]: thread = row i, consecutive lanes read consecutive
 // doubles of one column (coalesced), eight columns in flight per thread; blockIdx.y = chunk
 constexpr int kGemvChunkCols = 512;
@@ -463,14 +468,15 @@ static int dense_apply(npg_precond *pc, const double *r, double *z, double a, do
     return NPG_OK;
 }
 
-// A^-1 of a plain-CSR matrix as a dense fp64 array in HBM: densify, LU with partial pivoting and inversion by rocSOLVER
-// (set-up; n^2 doubles - 2 GB at 16 k unknowns, 8 GB at 31 k), applied per solve by the hand-written GEMV above
-static int dense_build(npg_precond *pc, const npg_csr *A, bool fp32, bool fp16 = false) {
+// A^-1 of a plain-CSR matrix as a dense fp64 array in HBM: densify, LU with partial pivoting and the solve against the identity
+// by rocSOLVER (set-up; n^2 doubles - 2 GB at 16 k unknowns, 8 GB at 31 k - and as many again while it runs), applied per solve
+// by the hand-written GEMV above
+static int dense_build_raw(npg_precond *pc, const npg_csr *A, bool fp32, bool fp16) {
     NPG_REQUIRE(A && A->m == A->n && A->nnode() == 0, "dense inverse: a square plain-CSR matrix is required");
     const int64_t n = A->m;
-    // (46 340 = floor(sqrt(2^31)): rocSOLVER's getrf / getri address the n x n array with 32-bit element offsets - at 58 295 unknowns,
+    // (46 340 = floor(sqrt(2^31)): rocSOLVER's getrf addresses the n x n array with 32-bit element offsets - at 58 295 unknowns,
     //  the channel basin's coarsest level, they fault; round 5, profiles/r05_coarse_viscosity.txt)
-    NPG_REQUIRE(n > 0 && n <= 46340, "dense inverse: %lld unknowns (limit 46 340: rocSOLVER's getrf / getri index the n x n array with 32-bit offsets)",
+    NPG_REQUIRE(n > 0 && n <= 46340, "dense inverse: %lld unknowns (limit 46 340: rocSOLVER's getrf / getrs index the n x n array with 32-bit offsets)",
                 (long long)n);
     hipStream_t st = pc->ctx->stream;
     DenseInv &d = pc->dense;
@@ -503,12 +509,28 @@ static int dense_build(npg_precond *pc, const npg_csr *A, bool fp32, bool fp16 =
     NPG_HIP(hipStreamSynchronize(st));
     rocblas_status s2 = rocblas_status_success;
     if (s1 == rocblas_status_success && i1 == 0) {
-        s2 = rocsolver_dgetri(h, (rocblas_int)n, d.M, (rocblas_int)n, ipiv, info);
-        NPG_HIP(hipMemcpyAsync(&i2, info, sizeof i2, hipMemcpyDeviceToHost, st));
-        NPG_HIP(hipStreamSynchronize(st));
+        // A^-1 = the solution of L U X = P I by getrs, not getri: rocSOLVER 3.32's dgetri returned a wrong inverse at n = 255 and
+        // n = 511 (the first (n + 1) / 2 columns, |A X - I| = 1, info = 0; right at 256, 257, 512, 513 -
+        // profiles/dense_inverse_getri.txt, tests/test_gpu_dense_inverse.py).  The factors stay in d.M until the solve is
+        // done: 2 n^2 doubles at the peak.
+        double *X = nullptr;
+        NPG_HIP(hipMalloc((void **)&X, (size_t)n * n * sizeof(double)));
+        hipError_t e = hipMemsetAsync(X, 0, (size_t)n * n * sizeof(double), st);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_unit_diagonal, dim3(grid_for(n)), dim3(kBlock), 0, st, X, n);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) {
+            s2 = rocsolver_dgetrs(h, rocblas_operation_none, (rocblas_int)n, (rocblas_int)n, d.M, (rocblas_int)n, ipiv, X, (rocblas_int)n);
+            e = hipStreamSynchronize(st);
+        }
+        i2 = 0;                               // (getrs reports through its status alone)
+        if (e == hipSuccess && s2 == rocblas_status_success) std::swap(d.M, X);
+        hipFree(X);                           // the factors - or, after a failure, the unfinished inverse
+        NPG_HIP(e);
     }
     NPG_REQUIRE(s1 == rocblas_status_success && i1 == 0 && s2 == rocblas_status_success && i2 == 0,
-                "dense inverse: rocSOLVER getrf/getri failed (status %d/%d, info %d/%d: the matrix is singular to working "
+                "dense inverse: rocSOLVER getrf/getrs failed (status %d/%d, info %d/%d: the matrix is singular to working "
                 "precision, or out of memory)", (int)s1, (int)s2, (int)i1, (int)i2);
     if (fp16) {
         d.ldf = (n + 7) / 8 * 8;
@@ -589,11 +611,20 @@ static int dense_build(npg_precond *pc, const npg_csr *A, bool fp32, bool fp16 =
     return NPG_OK;
 }
 
+// ... and a build that failed leaves no inverse behind: not the factors, not a half-written array - an application afterwards
+// is refused ("has not been set") instead of multiplying by them
+static int dense_build(npg_precond *pc, const npg_csr *A, bool fp32, bool fp16 = false) {
+    const int rc = dense_build_raw(pc, A, fp32, fp16);
+    if (rc) dense_free(pc->dense);
+    return rc;
+}
+
 NPG_API int npg_precond_dense_set(npg_precond *pc, const npg_csr *A, int fp32_storage) {
     NPG_REQUIRE(pc && pc->kind == NPG_PC_DENSE, "npg_precond_dense_set: not a dense-inverse preconditioner");
     int rc = dense_build(pc, A, fp32_storage != 0);
     if (rc) return rc;
     pc->n = A->m;
+    pc->cycle_bytes = 0;       // counted again by the next application: the storage may have changed
     return NPG_OK;
 }
 
@@ -991,7 +1022,12 @@ static int precond_apply_raw(npg_precond *pc, const double *r, double *z) {
     ++pc->applications;
     if (pc->kind == NPG_PC_DENSE) {
         NPG_REQUIRE(pc->dense.M || pc->dense.Mf, "npg_precond_apply: the dense inverse has not been set");
-        return dense_apply(pc, r, z, 1.0, 0.0);
+        int64_t count = 0;
+        if (pc->cycle_bytes == 0) byte_sink = &count;
+        const int rcd = dense_apply(pc, r, z, 1.0, 0.0);
+        byte_sink = nullptr;
+        if (count) pc->cycle_bytes = count;
+        return rcd;
     }
     if (pc->kind == NPG_PC_MG) {
         NPG_REQUIRE(pc->L.back().A, "npg_precond_apply: multigrid levels are not all set");

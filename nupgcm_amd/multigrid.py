@@ -555,7 +555,7 @@ class MultigridPreconditioner(GeneralPreconditioner):
         return self
 
     def _refresh_coarse_dense(self):
-        """the coarsest level's dense inverse after a re-assembly: rebuilt (getrf + getri of the level's matrix) - or, with
+        """the coarsest level's dense inverse after a re-assembly: rebuilt (getrf + getrs against the identity, of the level's matrix) - or, with
         dense_refresh_every = k > 1 (NPG_MG_DENSE_REFRESH_EVERY), only at every k-th refresh: in between the cycle keeps the inverse
         of the previous operator as its coarse solve (an approximate one: the smoother's operators and the level matrices above
         are current), which a coarsest level of several 1e4 unknowns needs - its inversion takes seconds"""

@@ -50,6 +50,26 @@ def vcycle(levels, lev, b, omega=2.5, jw=0.7, sweeps=3, nu1=2, nu2=2, coarse=20)
     return smooth(l, x, b, nu2, omega, jw, sweeps)
 
 
+def cycle(levels, lev, b, x=None, gamma=1, coarse_solve=None, omega=2.5, jw=0.7, sweeps=3, nu1=2, nu2=2, coarse=20):
+    """mg_cycle restated: gamma = 1 the V-cycle, gamma = 2 the W-cycle - the coarse problem of every level is visited gamma
+    times, each visit continuing from the previous visit's iterate.  x: the incoming iterate (None: zero).  Level 0 takes `coarse`
+    smoothing steps from the incoming iterate or, given coarse_solve (r -> A0^-1 r), x + coarse_solve(b - A0 x)."""
+    l = levels[lev]
+    params = dict(omega=omega, jw=jw, sweeps=sweeps, nu1=nu1, nu2=nu2, coarse=coarse)
+    x = np.zeros_like(b) if x is None else x
+    if lev == 0:
+        if coarse_solve is not None:
+            return x + coarse_solve(b - l.A @ x)
+        return smooth(l, x, b, coarse, omega, jw, sweeps)
+    x = smooth(l, x, b, nu1, omega, jw, sweeps)
+    bc = l.P.T @ (b - l.A @ x)
+    xc = None
+    for _ in range(gamma):
+        xc = cycle(levels, lev - 1, bc, xc, gamma, coarse_solve, **params)
+    x = x + l.P @ xc
+    return smooth(l, x, b, nu2, omega, jw, sweeps)
+
+
 def fgmres(A, b, M, x0=None, m=20, scale=1.0, atol=1e-6, rtol=1e-6, itmax=0):
     """right-preconditioned restarted FGMRES(m); stop when scale ||r|| <= atol + rtol scale ||r0||.
     Returns x, dict(niter, residuals (scaled estimates), solved)."""
