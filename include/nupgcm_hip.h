@@ -115,7 +115,13 @@ int npg_csr_combine(npg_csr *out, double a, const npg_csr *X, double b, const np
  * Five (four) 12-byte CSR entries and five (four) 8-byte gathers become one 20-byte record {c, K, C} and one gather of the
  * node's contiguous components.  The structure is verified entry by entry (relative tolerance rtol); *blocked = 0 and the
  * matrix is untouched if it does not hold (e.g. function-valued nu).  A node-blocked matrix can be multiplied and solved
- * with, but not downloaded, cloned or re-assembled. */
+ * with, but not downloaded, cloned or re-assembled.
+ * Failure paths: whenever the call does not end with *blocked = 1 the handle is the plain matrix it was, bit for bit (it
+ * still downloads, clones and multiplies).  That covers (a) a structure that does not hold, (b) a record form that does not
+ * fit - the rows of one node exceed an SpMV tile (about 1 900 neighbours of a three-component node): *blocked = 0, NPG_OK,
+ * and npg_last_error() names the limit - and (c) an error on the way (out of memory), which is returned.  A matrix that fits
+ * the ordinary tiles but not a windowed one - a node beyond a window's caps, or a tile of nodes without any entry in the block
+ * columns - is node-blocked without a windowed tile set (npg_csr_window_info: 0 tiles). */
 int npg_csr_block_nodes(npg_csr *A, int64_t n_full, int64_t n_surf, double rtol, int *blocked);
 /* (round 5; multi-GPU) Ghost NODES of a rank's row block - the matrix's columns [m, n) are the rank's ghosts: node g's (x, y[, z])
  * components are the ghost columns [first_col[g], first_col[g] + ncomp[g]), ncomp = 3 or 2.  Call before npg_csr_block_nodes:
@@ -132,7 +138,7 @@ int npg_csr_set_ghost_nodes(npg_csr *A, int64_t n_nodes, const int32_t *first_co
  * go on taking and returning vectors in the caller's order (right-hand side, warm start / solution and a vector preconditioner
  * are gathered / scattered on the device, four vector passes per solve), so npg_vec_upload_perm / npg_vec_download_perm with
  * the caller's own permutations stay what they were.  Other solvers refuse such a matrix.  *blocked = 0 and the matrix
- * untouched if the structure does not hold. */
+ * untouched, in the caller's order, on every failure path of npg_csr_block_nodes. */
 int npg_csr_block_nodes_dofs(npg_csr *A, const int64_t *node_of_dof, const int32_t *comp_of_dof, double rtol, int *blocked);
 /* the two-component special case: npg_csr_block_nodes(A, 0, npairs, ...) */
 int npg_csr_pair_xy(npg_csr *A, int64_t npairs, double rtol, int *paired);

@@ -323,7 +323,7 @@ static int build_window_tiles_scaled(npg_csr *A, const std::vector<int32_t> &pco
             d.nw = (int32_t)tw.size();
             d.voff = (int32_t)vlist.size();
             d.nv = (int32_t)tv.size();
-            NPG_REQUIRE(d.nw > 0, "build_window_tiles: a block tile without column nodes");
+            if (d.nw == 0) return NPG_OK;        // a tile of nodes without any entry in the block columns: no windowed set
             wlist.insert(wlist.end(), tw.begin(), tw.end());
             vlist.insert(vlist.end(), tv.begin(), tv.end());
             blk.push_back(d);
@@ -405,6 +405,7 @@ static int build_window_tiles_scaled(npg_csr *A, const std::vector<int32_t> &pco
         }
         int64_t r = 0;
         bool ok = true;
+        const size_t wlist_blk = wlist.size();
         while (r < nbehind && ok) {
             const int32_t T = (int32_t)(blk.size() + rowt.size());
             tw.clear();
@@ -456,7 +457,10 @@ static int build_window_tiles_scaled(npg_csr *A, const std::vector<int32_t> &pco
             rghost.push_back(tw.back() >= nnode);
             r = re;
         }
-        if (!ok) rowt.clear();
+        if (!ok) {          // (ordinary tiles for these rows: the lists of the row tiles made so far go with them)
+            rowt.clear();
+            wlist.resize(wlist_blk);
+        }
     }
     vlist.push_back((int32_t)nbr);           // sentinel: a tile without such columns still reads one entry at its offset
     NPG_REQUIRE(wlist.size() < (size_t)INT32_MAX && vlist.size() < (size_t)INT32_MAX, "build_window_tiles: window lists exceed int32 offsets");
@@ -801,7 +805,8 @@ using namespace npg;
 
 // Store the velocity block of A_inversion node by node (see spmv_device.h): one record {c, K, C} per coupled node pair.
 // The structure is verified entry by entry on the host (K_xx = K_yy = K_zz, C_xy = -C_yx within rtol * row scale, nothing
-// else in the block); if anything does not match the matrix is left untouched and *blocked = 0.
+// else in the block); if anything does not match the matrix is left untouched and *blocked = 0.  The same when the record
+// form does not fit its tiles or cannot be allocated: the plain arrays are kept until the new form stands (see the swap below).
 NPG_API int npg_csr_block_nodes(npg_csr *A, int64_t nfull, int64_t nsurf, double rtol, int *blocked) {
     NPG_REQUIRE(A && blocked && nfull >= 0 && nsurf >= 0, "npg_csr_block_nodes: bad argument");
     const int64_t nf3 = 3 * nfull, nbr = nf3 + 2 * nsurf, nnode = nfull + nsurf;
@@ -945,68 +950,119 @@ NPG_API int npg_csr_block_nodes(npg_csr *A, int64_t nfull, int64_t nsurf, double
         }
         nrp[r + 1] = (int64_t)ncol.size();
     }
-    // swap the device arrays; a clone shares rowptr / col / tiles with its pattern owner and must detach from them
-    if (A->owns_pattern) {
-        NPG_HIP(hipFree(A->col));
-        NPG_HIP(hipFree(A->rowptr));
-        if (A->tile_ptr) NPG_HIP(hipFree(A->tile_ptr));
-    }
-    NPG_HIP(hipFree(A->val));
+    // Swap the device arrays.  The plain arrays are set aside, not freed, until the record form and its tiles stand: the fit
+    // checks of build_tiles / build_window_tiles need the new form in the handle, and when one of them (or an allocation) fails
+    // the handle gets its plain arrays back - a matrix that was not converted is the caller's matrix, bit for bit.
+    // (A clone shares rowptr / col / tiles with its pattern owner and detaches from them.)
+    int64_t *const old_rowptr = A->rowptr;
+    int32_t *const old_col = A->col;
+    double *const old_val = A->val;
+    TileDesc *const old_tile_ptr = A->tile_ptr;
+    const bool old_owns = A->owns_pattern;
+    const int32_t old_ntiles = A->ntiles, old_interior = A->ntiles_interior, old_lanes = A->lanes, old_lanes_default = A->lanes_default;
+    const int64_t old_rnnz = A->rnnz;
+    std::vector<int64_t> old_h_rowptr = A->h_rowptr;
+    std::vector<TileDesc> old_h_tiles = A->h_tiles;
     A->col = nullptr;
     A->val = nullptr;
     A->rowptr = nullptr;
     A->tile_ptr = nullptr;
     A->owns_pattern = true;
-    NPG_HIP(hipMalloc((void **)&A->rowptr, nrp.size() * sizeof(int64_t)));
-    NPG_HIP(hipMalloc((void **)&A->col, std::max<size_t>(1, ncol.size()) * sizeof(int32_t)));
-    NPG_HIP(hipMalloc((void **)&A->val, std::max<size_t>(1, nval.size()) * sizeof(double)));
-    NPG_HIP(hipMalloc((void **)&A->prow, prow.size() * sizeof(int64_t)));
-    NPG_HIP(hipMalloc((void **)&A->pcol, std::max<size_t>(1, pcol.size()) * sizeof(int32_t)));
-    NPG_HIP(hipMalloc((void **)&A->pkc, std::max<size_t>(2, pkc.size()) * sizeof(double)));
-    NPG_HIP(hipMemcpy(A->rowptr, nrp.data(), nrp.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-    if (!ncol.empty()) {
-        NPG_HIP(hipMemcpy(A->col, ncol.data(), ncol.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        NPG_HIP(hipMemcpy(A->val, nval.data(), nval.size() * sizeof(double), hipMemcpyHostToDevice));
+    bool no_fit = false;        // build_tiles: the rows of one node do not fit one tile
+    auto convert = [&]() -> int {
+        NPG_HIP(hipMalloc((void **)&A->rowptr, nrp.size() * sizeof(int64_t)));
+        NPG_HIP(hipMalloc((void **)&A->col, std::max<size_t>(1, ncol.size()) * sizeof(int32_t)));
+        NPG_HIP(hipMalloc((void **)&A->val, std::max<size_t>(1, nval.size()) * sizeof(double)));
+        NPG_HIP(hipMalloc((void **)&A->prow, prow.size() * sizeof(int64_t)));
+        NPG_HIP(hipMalloc((void **)&A->pcol, std::max<size_t>(1, pcol.size()) * sizeof(int32_t)));
+        NPG_HIP(hipMalloc((void **)&A->pkc, std::max<size_t>(2, pkc.size()) * sizeof(double)));
+        NPG_HIP(hipMemcpy(A->rowptr, nrp.data(), nrp.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        if (!ncol.empty()) {
+            NPG_HIP(hipMemcpy(A->col, ncol.data(), ncol.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+            NPG_HIP(hipMemcpy(A->val, nval.data(), nval.size() * sizeof(double), hipMemcpyHostToDevice));
+        }
+        NPG_HIP(hipMemcpy(A->prow, prow.data(), prow.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        if (!pcol.empty()) {
+            NPG_HIP(hipMemcpy(A->pcol, pcol.data(), pcol.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+            NPG_HIP(hipMemcpy(A->pkc, pkc.data(), pkc.size() * sizeof(double), hipMemcpyHostToDevice));
+        }
+        if (colrec) {
+            const size_t ng = gcolv.size();
+            NPG_HIP(hipMalloc((void **)&A->grow, growv.size() * sizeof(int64_t)));
+            NPG_HIP(hipMalloc((void **)&A->gcol, ng * sizeof(int32_t)));
+            NPG_HIP(hipMalloc((void **)&A->gval, 3 * ng * sizeof(double)));
+            NPG_HIP(hipMemcpy(A->grow, growv.data(), growv.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+            NPG_HIP(hipMemcpy(A->gcol, gcolv.data(), ng * sizeof(int32_t), hipMemcpyHostToDevice));
+            NPG_HIP(hipMemcpy(A->gval, gxy.data(), 2 * ng * sizeof(double), hipMemcpyHostToDevice));
+            NPG_HIP(hipMemcpy(A->gval + 2 * ng, gzv.data(), ng * sizeof(double), hipMemcpyHostToDevice));
+            A->ngrec = (int64_t)ng;
+            A->h_grow = std::move(growv);
+        }
+        if (coupling && !dcol.empty()) {
+            const size_t nd = dcol.size();
+            NPG_HIP(hipMalloc((void **)&A->drow, drow.size() * sizeof(int64_t)));
+            NPG_HIP(hipMalloc((void **)&A->dcol, nd * sizeof(int32_t)));
+            NPG_HIP(hipMalloc((void **)&A->dval, 3 * nd * sizeof(double)));
+            NPG_HIP(hipMemcpy(A->drow, drow.data(), drow.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+            NPG_HIP(hipMemcpy(A->dcol, dcol.data(), nd * sizeof(int32_t), hipMemcpyHostToDevice));
+            NPG_HIP(hipMemcpy(A->dval, dxy.data(), 2 * nd * sizeof(double), hipMemcpyHostToDevice));
+            NPG_HIP(hipMemcpy(A->dval + 2 * nd, dz.data(), nd * sizeof(double), hipMemcpyHostToDevice));
+            A->ndrec = (int64_t)nd;
+            A->ndrec_real = ndrec_real;
+            A->h_drow = std::move(drow);
+        }
+        A->h_rowptr = std::move(nrp);
+        A->h_prow = std::move(prow);
+        A->rnnz = (int64_t)ncol.size();
+        A->nfull = (int32_t)nfull;
+        A->nsurf = (int32_t)nsurf;
+        A->nrec_real = nrec_real;
+        int rc = build_tiles(A);
+        if (rc) {
+            no_fit = rc == NPG_EINVAL;
+            return rc;
+        }
+        if (want_win && colrec) return build_window_tiles(A, pcol, gcolv, dcol, pkc, dxy, gxy, gzv, dz, ncol, nval);
+        return NPG_OK;
+    };
+    const int rc = convert();
+    if (rc != NPG_OK) {
+        // back to the plain matrix: drop whatever of the record form exists, put the arrays that were set aside back
+        free_window_tiles(A);
+        for (void *p : {(void *)A->rowptr, (void *)A->col, (void *)A->val, (void *)A->tile_ptr, (void *)A->prow, (void *)A->pcol, (void *)A->pkc,
+                        (void *)A->grow, (void *)A->gcol, (void *)A->gval, (void *)A->drow, (void *)A->dcol, (void *)A->dval})
+            if (p) hipFree(p);
+        A->prow = A->grow = A->drow = nullptr;
+        A->pcol = A->gcol = A->dcol = nullptr;
+        A->pkc = A->gval = A->dval = nullptr;
+        A->ngrec = A->ndrec = A->ndrec_real = A->nrec_real = 0;
+        A->h_prow.clear();
+        A->h_grow.clear();
+        A->h_drow.clear();
+        A->nfull = A->nsurf = 0;
+        A->rowptr = old_rowptr;
+        A->col = old_col;
+        A->val = old_val;
+        A->tile_ptr = old_tile_ptr;
+        A->owns_pattern = old_owns;
+        A->ntiles = old_ntiles;
+        A->ntiles_interior = old_interior;
+        A->lanes = old_lanes;
+        A->lanes_default = old_lanes_default;
+        A->rnnz = old_rnnz;
+        A->h_rowptr = std::move(old_h_rowptr);
+        A->h_tiles = std::move(old_h_tiles);
+        A->gen++;
+        // the rows of one node do not fit one tile: like a structure that does not hold, no error - *blocked = 0 and
+        // npg_last_error says so; anything else (out of memory, window lists beyond int32 offsets) is returned
+        return no_fit ? NPG_OK : rc;
     }
-    NPG_HIP(hipMemcpy(A->prow, prow.data(), prow.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-    if (!pcol.empty()) {
-        NPG_HIP(hipMemcpy(A->pcol, pcol.data(), pcol.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        NPG_HIP(hipMemcpy(A->pkc, pkc.data(), pkc.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (old_owns) {
+        hipFree(old_col);
+        hipFree(old_rowptr);
+        if (old_tile_ptr) hipFree(old_tile_ptr);
     }
-    if (colrec) {
-        const size_t ng = gcolv.size();
-        NPG_HIP(hipMalloc((void **)&A->grow, growv.size() * sizeof(int64_t)));
-        NPG_HIP(hipMalloc((void **)&A->gcol, ng * sizeof(int32_t)));
-        NPG_HIP(hipMalloc((void **)&A->gval, 3 * ng * sizeof(double)));
-        NPG_HIP(hipMemcpy(A->grow, growv.data(), growv.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        NPG_HIP(hipMemcpy(A->gcol, gcolv.data(), ng * sizeof(int32_t), hipMemcpyHostToDevice));
-        NPG_HIP(hipMemcpy(A->gval, gxy.data(), 2 * ng * sizeof(double), hipMemcpyHostToDevice));
-        NPG_HIP(hipMemcpy(A->gval + 2 * ng, gzv.data(), ng * sizeof(double), hipMemcpyHostToDevice));
-        A->ngrec = (int64_t)ng;
-        A->h_grow = std::move(growv);
-    }
-    if (coupling && !dcol.empty()) {
-        const size_t nd = dcol.size();
-        NPG_HIP(hipMalloc((void **)&A->drow, drow.size() * sizeof(int64_t)));
-        NPG_HIP(hipMalloc((void **)&A->dcol, nd * sizeof(int32_t)));
-        NPG_HIP(hipMalloc((void **)&A->dval, 3 * nd * sizeof(double)));
-        NPG_HIP(hipMemcpy(A->drow, drow.data(), drow.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        NPG_HIP(hipMemcpy(A->dcol, dcol.data(), nd * sizeof(int32_t), hipMemcpyHostToDevice));
-        NPG_HIP(hipMemcpy(A->dval, dxy.data(), 2 * nd * sizeof(double), hipMemcpyHostToDevice));
-        NPG_HIP(hipMemcpy(A->dval + 2 * nd, dz.data(), nd * sizeof(double), hipMemcpyHostToDevice));
-        A->ndrec = (int64_t)nd;
-        A->ndrec_real = ndrec_real;
-        A->h_drow = std::move(drow);
-    }
-    A->h_rowptr = std::move(nrp);
-    A->h_prow = std::move(prow);
-    A->rnnz = (int64_t)ncol.size();
-    A->nfull = (int32_t)nfull;
-    A->nsurf = (int32_t)nsurf;
-    A->nrec_real = nrec_real;
-    int rc = build_tiles(A);
-    if (rc) return rc;
-    if (want_win && colrec && (rc = build_window_tiles(A, pcol, gcolv, dcol, pkc, dxy, gxy, gzv, dz, ncol, nval))) return rc;
+    hipFree(old_val);
     *blocked = 1;
     return NPG_OK;
 }
