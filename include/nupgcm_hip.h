@@ -43,6 +43,7 @@ typedef struct npg_fgmres npg_fgmres;
 typedef struct npg_locator npg_locator;
 typedef struct npg_located npg_located;
 typedef struct npg_integrals npg_integrals;
+typedef struct npg_classes npg_classes;
 typedef struct npg_particles npg_particles;
 
 /* ---- context: replaces the implicit CUDA.jl device/stream (ext/nuPGCMCUDAExt.jl:8-16) ------------------------- */
@@ -558,6 +559,37 @@ int npg_integrals_create(npg_fe *fe, const double *cell_z, const uint8_t *cell_m
 int npg_integrals_destroy(npg_integrals *I);
 /* out: NPG_NINT doubles on the device. x_inv = [u; p], b = buoyancy vector. */
 int npg_integrals_compute(npg_integrals *I, const npg_vec *x_inv, const npg_vec *b, int full_stress, npg_vec *out);
+
+/* ---- the state binned into (latitude band, buoyancy class) (new work: the reference overlays isopycnals on a z-coordinate psi) --
+ * A joint table [ny + 1][nb + 1][NPG_NCLS] over the cells of the mesh (csrc/classes_core.h).
+ * Sample rule - NOT the engine's quadrature (Keast's rule has a negative weight): ns barycentric points rule_lam[ns][4] with weights
+ * rule_w[ns], every weight > 0, sum = 1 (checked to 1e-12, as every lam row).  A sample of cell c carries the measure
+ * w[s] wdet(c) sum_q qw[q] (the last factor from the engine's own table).  Exact for functions linear in the cell, otherwise a
+ * positive Riemann sum.  At a sample, all from one lambda (closed-form P2 / P1 shape functions, Dirichlet nodes count):
+ *    y = sum lambda_i y_i, z = sum lambda_i z_i (the cell's own vertices),  B = N2 z + b',  u,  grad B = grad b' + N2 e_z.
+ * Bins: b_edges[nb], y_edges[ny] finite and strictly increasing, nb >= 0, ny >= 0.  Class = the number of b_edges <= B
+ * (searchsorted(b_edges, B, side = "right"), 0 .. nb); band = the same of y_edges and y: the end bins are open, every finite sample is
+ * counted exactly once.  A sample whose B or y is not finite goes to no bin and is counted in `dropped`.
+ * Channels (term = measure x integrand; RAW integrals, prefactors are the caller's):
+ *    0  1 (volume census)       1  u_x       2  u_y (residual overturning)       3  u_z
+ *    4  z                       5  B         6  d_z B                            7  u . grad B
+ * The same bits on every call, whatever the arrival order: pass 1 sums S_c = sum |term_c| (fixed order, as npg_integrals_compute) and
+ * counts the dropped samples; with frexp(S_c) = (m, e) the channel's scale is 2^(61 - e) (1 when S_c = 0); pass 2 adds
+ * llrint(term scale_c) as signed 64-bit integers with relaxed device-scope atomics (integer addition is associative); pass 3 divides
+ * by the scale.  Quantisation: at most half a unit per sample, n_bin 2^-61 S_c per bin.  A channel whose S_c is not finite comes back
+ * NaN.  Always fp64.  Validation (NPG_EINVAL + message) happens before anything is launched.  A mask that leaves no cell gives a zero
+ * table.  The handle owns the integer table (zeroed at the start of every compute, on the stream), the partial rows, the rule and the
+ * edges; the engine must outlive it. */
+#define NPG_NCLS 8
+/* cell_y / cell_z [ncell][4]: y and z of each cell's OWN vertices; cell_mask[ncell] or NULL: 1 = this cell counts;
+   1 <= ns <= 4096; (ny + 1)(nb + 1) <= 2^22 */
+int npg_classes_create(npg_fe *fe, const double *cell_y, const double *cell_z, const uint8_t *cell_mask, const double *rule_lam,
+                       const double *rule_w, int ns, const double *y_edges, int64_t ny, const double *b_edges, int64_t nb,
+                       npg_classes **out);
+/* table: (ny + 1)(nb + 1) NPG_NCLS doubles, entry ((band (nb + 1)) + class) NPG_NCLS + channel; info: >= 1 + NPG_NCLS doubles:
+   dropped, S_c.  N2 = 0 bins the perturbation b'. */
+int npg_classes_compute(npg_classes *K, const npg_vec *x_inv, const npg_vec *b, double N2, npg_vec *table, npg_vec *info);
+int npg_classes_destroy(npg_classes *K);
 
 /* ---- Lagrangian particles advected through the device-resident flow (new work: offline tracking needs u saved every step) -----
  * n particles on the device: position [n][3], the cell each was last located in, status (0 alive, 1 lost), wind [n][3] and t_lost.

@@ -1381,6 +1381,164 @@ NPG_API int npg_integrals_compute(npg_integrals *I, const npg_vec *x_inv, const 
     return NPG_OK;
 }
 
+// ---- the state binned into (latitude band, buoyancy class) (csrc/classes.hip on the host): the per-sample arithmetic and the edge
+// search are the SAME code (csrc/classes_core.h).  Pass 1 in fixed chunks of kClsChunk cells, folded in chunk order; pass 2 adds the
+// quantised terms as 64-bit integers (relaxed atomics on one table, a run of samples in one bin added up first): integer addition is
+// associative, so the table does not depend on the number of threads. ------------------------------------------------------------------
+#include "../csrc/classes_core.h"
+static_assert(NPG_NCLS == npg::kNCls, "NPG_NCLS of the header and kNCls of classes_core.h must agree");
+
+struct npg_classes {
+    npg_fe *fe = nullptr;
+    std::vector<double> cy, cz;      // [ncell][4]
+    std::vector<uint8_t> mask;       // [ncell] or empty
+    std::vector<double> lam, wq;     // [ns][4], [ns] (= w[s] qsum)
+    std::vector<double> y_edges, b_edges;
+    std::vector<double> part;        // [nchunk][kClsInfo]
+    std::vector<int64_t> itab;       // [(ny + 1)(nb + 1)][NPG_NCLS]
+    int64_t nbins = 0;
+};
+namespace {
+struct HostClsCells {    // the engine's cell tables as class_cell_load reads them ([cell][component])
+    const npg_fe *fe;
+    const double *cy, *cz;
+    double G(int k, int64_t c) const { return fe->G[(size_t)c * 12 + k]; }
+    double wdet(int64_t c) const { return fe->wdet[(size_t)c]; }
+    double y(int i, int64_t c) const { return cy[(size_t)c * 4 + i]; }
+    double z(int i, int64_t c) const { return cz[(size_t)c * 4 + i]; }
+    double u(const double *x, int l, int64_t c) const { return fval(x, fe->u_diri, fe->cu[(size_t)c * 30 + l]); }
+    double b(const double *x, int i, int64_t c) const { return fval(x, fe->b_diri, fe->cb[(size_t)c * fe->nb + i]); }
+};
+inline void classes_flush(int64_t *itab, int64_t bin, const int64_t run[NPG_NCLS]) {
+    for (int k = 0; k < NPG_NCLS; ++k)
+        if (run[k] != 0) __atomic_fetch_add(&itab[bin * NPG_NCLS + k], run[k], __ATOMIC_RELAXED);
+}
+// PASS 1: acc += {|term|, dropped} of cell c; PASS 2: the cell's quantised terms into itab, run by run
+template <int NB, int PASS>
+inline void classes_cell(const npg_classes *K, const HostClsCells &t, const double *xu, const double *xb, double N2, int64_t c, double *acc,
+                         const double *scale, int64_t *itab) {
+    npg::ClassCell<NB> n;
+    npg::class_cell_load<NB>(t, xu, xb, c, n);
+    const int ns = (int)K->wq.size();
+    const int64_t ny = (int64_t)K->y_edges.size(), nb = (int64_t)K->b_edges.size();
+    int64_t run[NPG_NCLS] = {0, 0, 0, 0, 0, 0, 0, 0}, cur = -1;
+    for (int s = 0; s < ns; ++s) {
+        double term[NPG_NCLS];
+        int64_t band = 0, cls = 0;
+        const bool ok = npg::class_sample<NB, PASS == 2>(n, &K->lam[(size_t)4 * s], K->wq[(size_t)s], N2, K->y_edges.data(), ny,
+                                                         K->b_edges.data(), nb, &band, &cls, term);
+        if (PASS == 1) {
+            if (ok) for (int k = 0; k < NPG_NCLS; ++k) acc[k] += std::fabs(term[k]);
+            else acc[NPG_NCLS] += 1.0;
+        } else if (ok) {
+            const int64_t bin = band * (nb + 1) + cls;
+            if (bin != cur) {
+                if (cur >= 0) classes_flush(itab, cur, run);
+                cur = bin;
+                for (int k = 0; k < NPG_NCLS; ++k) run[k] = 0;
+            }
+            for (int k = 0; k < NPG_NCLS; ++k) run[k] += npg::class_quantise(term[k], scale[k]);
+        }
+    }
+    if (PASS == 2 && cur >= 0) classes_flush(itab, cur, run);
+}
+}  // namespace
+
+NPG_API int npg_classes_create(npg_fe *fe, const double *cell_y, const double *cell_z, const uint8_t *cell_mask, const double *rule_lam,
+                               const double *rule_w, int ns, const double *y_edges, int64_t ny, const double *b_edges, int64_t nb,
+                               npg_classes **out) {
+    REQUIRE(fe && out, "npg_classes_create: NULL argument");
+    REQUIRE(cell_y && cell_z, "npg_classes_create: cell_y or cell_z is NULL");
+    REQUIRE(ns >= 1 && ns <= npg::kClsMaxSamples, "npg_classes_create: 1 .. %d samples per cell, got %d", npg::kClsMaxSamples, ns);
+    REQUIRE(rule_lam && rule_w, "npg_classes_create: rule_lam or rule_w is NULL");
+    REQUIRE(ny >= 0 && nb >= 0 && (ny == 0 || y_edges) && (nb == 0 || b_edges), "npg_classes_create: edges missing or a negative count");
+    REQUIRE(ny < npg::kClsMaxBins && nb < npg::kClsMaxBins && (ny + 1) * (nb + 1) <= npg::kClsMaxBins,
+            "npg_classes_create: ny = %lld and nb = %lld give more than 2^22 bins (ny + 1)(nb + 1)", (long long)ny, (long long)nb);
+    const char *err = npg::check_edges(y_edges, ny);
+    REQUIRE(!err, "npg_classes_create: y_edges %s", err);
+    err = npg::check_edges(b_edges, nb);
+    REQUIRE(!err, "npg_classes_create: b_edges %s", err);
+    double wsum = 0.0;
+    for (int s = 0; s < ns; ++s) {
+        REQUIRE(rule_w[s] > 0.0 && std::isfinite(rule_w[s]), "npg_classes_create: weight %d of the rule is not > 0", s);
+        wsum += rule_w[s];
+        const double *l = rule_lam + 4 * s;
+        REQUIRE(std::fabs((l[0] + l[1]) + (l[2] + l[3]) - 1.0) <= 1e-12, "npg_classes_create: lam row %d of the rule does not sum to 1", s);
+    }
+    REQUIRE(std::fabs(wsum - 1.0) <= 1e-12, "npg_classes_create: the weights of the rule sum to %.17g, not 1", wsum);
+    const int64_t nc = fe->ncell;
+    for (int64_t k = 0; k < nc * 4; ++k) {
+        REQUIRE(std::isfinite(cell_y[k]), "npg_classes_create: cell_y[%lld][%d] is not finite", (long long)(k / 4), (int)(k % 4));
+        REQUIRE(std::isfinite(cell_z[k]), "npg_classes_create: cell_z[%lld][%d] is not finite", (long long)(k / 4), (int)(k % 4));
+    }
+    double qsum = 0.0;                       // the measure of a sample is w[s] wdet qsum, qsum from the engine's own weights
+    for (double w : fe->qw) qsum += w;
+    npg_classes *K = new npg_classes();
+    K->fe = fe;
+    K->cy.assign(cell_y, cell_y + nc * 4);
+    K->cz.assign(cell_z, cell_z + nc * 4);
+    if (cell_mask) K->mask.assign(cell_mask, cell_mask + nc);
+    K->lam.assign(rule_lam, rule_lam + (size_t)4 * ns);
+    K->wq.resize((size_t)ns);
+    for (int s = 0; s < ns; ++s) K->wq[(size_t)s] = rule_w[s] * qsum;
+    if (ny) K->y_edges.assign(y_edges, y_edges + ny);
+    if (nb) K->b_edges.assign(b_edges, b_edges + nb);
+    K->nbins = (ny + 1) * (nb + 1);
+    K->part.assign((size_t)((nc + npg::kClsChunk - 1) / npg::kClsChunk) * npg::kClsInfo, 0.0);
+    K->itab.assign((size_t)K->nbins * NPG_NCLS, 0);
+    *out = K;
+    return NPG_OK;
+}
+NPG_API int npg_classes_destroy(npg_classes *K) {
+    delete K;
+    return NPG_OK;
+}
+NPG_API int npg_classes_compute(npg_classes *K, const npg_vec *x_inv, const npg_vec *b, double N2, npg_vec *table, npg_vec *info) {
+    REQUIRE(K && x_inv && b && table && info, "npg_classes_compute: NULL argument");
+    const npg_fe *fe = K->fe;
+    REQUIRE(x_inv->n == fe->n_inv, "npg_classes_compute: the flow vector has %lld entries, expected %lld", (long long)x_inv->n,
+            (long long)fe->n_inv);
+    REQUIRE(b->n == fe->n_b, "npg_classes_compute: the buoyancy vector has %lld entries, expected %lld", (long long)b->n, (long long)fe->n_b);
+    REQUIRE(table->n >= K->nbins * NPG_NCLS, "npg_classes_compute: table holds %lld doubles, needs (ny + 1)(nb + 1) NPG_NCLS = %lld",
+            (long long)table->n, (long long)(K->nbins * NPG_NCLS));
+    REQUIRE(info->n >= 1 + NPG_NCLS, "npg_classes_compute: info holds %lld doubles, needs 1 + NPG_NCLS = %d", (long long)info->n, 1 + NPG_NCLS);
+    REQUIRE(std::isfinite(N2), "npg_classes_compute: N2 is not finite");
+    const int64_t nc = fe->ncell, nchunk = (nc + npg::kClsChunk - 1) / npg::kClsChunk, nent = K->nbins * NPG_NCLS;
+    const HostClsCells t{fe, K->cy.data(), K->cz.data()};
+    const uint8_t *mask = K->mask.empty() ? nullptr : K->mask.data();
+    const double *xu = x_inv->d, *xb = b->d;
+    int64_t *itab = K->itab.data();
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < nent; ++i) itab[i] = 0;
+#pragma omp parallel for schedule(static)
+    for (int64_t k = 0; k < nchunk; ++k) {
+        double acc[npg::kClsInfo];
+        for (int a = 0; a < npg::kClsInfo; ++a) acc[a] = 0.0;
+        for (int64_t c = k * npg::kClsChunk; c < std::min(nc, (k + 1) * npg::kClsChunk); ++c) {
+            if (mask && !mask[c]) continue;
+            if (fe->nb == 10) classes_cell<10, 1>(K, t, xu, xb, N2, c, acc, nullptr, nullptr);
+            else classes_cell<4, 1>(K, t, xu, xb, N2, c, acc, nullptr, nullptr);
+        }
+        for (int a = 0; a < npg::kClsInfo; ++a) K->part[(size_t)k * npg::kClsInfo + a] = acc[a];
+    }
+    double scale[NPG_NCLS];
+    for (int a = 0; a < npg::kClsInfo; ++a) {
+        double sum = 0.0;
+        for (int64_t k = 0; k < nchunk; ++k) sum += K->part[(size_t)k * npg::kClsInfo + a];
+        if (a < NPG_NCLS) info->d[1 + a] = sum, scale[a] = npg::class_scale(sum);
+        else info->d[0] = sum;
+    }
+#pragma omp parallel for schedule(static)
+    for (int64_t c = 0; c < nc; ++c) {
+        if (mask && !mask[c]) continue;
+        if (fe->nb == 10) classes_cell<10, 2>(K, t, xu, xb, N2, c, nullptr, scale, itab);
+        else classes_cell<4, 2>(K, t, xu, xb, N2, c, nullptr, scale, itab);
+    }
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < nent; ++i) table->d[i] = (double)itab[i] / scale[i % NPG_NCLS];
+    return NPG_OK;
+}
+
 // ---- Lagrangian particles in the flow (csrc/particles.hip on the host): the RK4 step, the remembered cell, the periodic wrap and the
 // rule for leaving the mesh are the SAME code (csrc/particles_core.h), looped over the particles with OpenMP -------------------------
 #include "../csrc/particles_core.h"

@@ -1,0 +1,91 @@
+"""The flow binned into (latitude band, buoyancy class) (nupgcm_amd.watermass) on the CPU() architecture -
+libnupgcm_host.so runs the same per-sample arithmetic and the same edge search as the device kernels (csrc/classes_core.h) - against the
+numpy restatement of tests/watermass_ref.py, exact identities against MeshIntegrals, ties at an edge, the table shapes, bit-identical
+repeat calls, dropped samples, refusals and the recorder.  No GPU."""
+import pytest
+
+import nupgcm_amd as npg
+from tests import integrals_ref as ir
+from tests import sampling_ref as sr
+from tests import watermass_ref as wr
+
+
+@pytest.fixture(scope="module")
+def arch():
+    return npg.CPU()
+
+
+@pytest.fixture(scope="module")
+def flux_model(arch):
+    return sr.bowl_model(arch, "bowl_surface_flux", nsteps=3)
+
+
+@pytest.fixture(scope="module")
+def mix_model(arch):
+    """N2 = 1 / alpha and Dirichlet b: B and b' bin differently, Dirichlet nodes count"""
+    return sr.bowl_model(arch, "bowl_mixing", nsteps=3)
+
+
+@pytest.fixture(scope="module")
+def p1_model(arch):
+    return sr.bowl_model(arch, "bowl_mixing", b_order=1, nsteps=3)
+
+
+def channel(arch):
+    """the small channel basin (periodic seam) with a random flow and its own buoyancy"""
+    model = sr.channel_model(arch)
+    b = model.b_vec.to_host()
+    ir.random_state(model)
+    model.b_vec.upload(b)
+    return model
+
+
+def test_both_libraries_export_the_classes_entry_points():
+    wr.check_exports()
+
+
+def test_table_against_the_restatement_bowl_p2(mix_model):
+    wr.check_table(mix_model, "bowl P2")
+
+
+def test_table_against_the_restatement_bowl_p1(p1_model):
+    wr.check_table(p1_model, "bowl P1")
+
+
+def test_table_against_the_restatement_channel_basin(arch):
+    wr.check_table(channel(arch), "channel basin")
+
+
+def test_table_against_the_restatement_embedded_2d(arch):
+    wr.check_table(ir.bowl2d_model(arch), "bowl 2-D")
+
+
+def test_identities_against_the_mesh_integrals(mix_model, p1_model):
+    wr.check_identities(mix_model, "bowl P2")
+    wr.check_identities(p1_model, "bowl P1", p1=True)
+
+
+def test_ties_at_an_edge(flux_model):
+    wr.check_ties(flux_model)
+
+
+def test_shapes(flux_model):
+    wr.check_shapes(flux_model, "bowl P2")
+
+
+def test_determinism_and_rezeroing(flux_model):
+    wr.check_determinism(flux_model)
+
+
+def test_dropped_samples(flux_model, p1_model):
+    wr.check_dropped(flux_model, "bowl P2")
+    wr.check_dropped(p1_model, "bowl P1")
+
+
+def test_refusals(flux_model):
+    wr.check_refusals(flux_model)
+    wr.check_replicated_layout_refused(flux_model)
+
+
+def test_class_recorder_as_on_plot(arch, tmp_path):
+    wr.check_recorder(sr.bowl_model(arch, "bowl_surface_flux"), tmp_path)
