@@ -45,6 +45,7 @@ typedef struct npg_located npg_located;
 typedef struct npg_integrals npg_integrals;
 typedef struct npg_classes npg_classes;
 typedef struct npg_particles npg_particles;
+typedef struct npg_tracers npg_tracers;
 
 /* ---- context: replaces the implicit CUDA.jl device/stream (ext/nuPGCMCUDAExt.jl:8-16) ------------------------- */
 int npg_ctx_create(int device, npg_ctx **out);
@@ -618,6 +619,29 @@ int npg_particles_advance(npg_particles *P, npg_fe *fe, npg_locator *loc, const 
 int npg_particles_download(const npg_particles *P, double *xyz, int32_t *cell, int32_t *status, int32_t *wind, double *t_lost);
 /* device copy of the positions into a vector of 3 n doubles: what npg_locator_find / npg_fe_sample take (b along a path) */
 int npg_particles_positions(const npg_particles *P, npg_vec *out);
+
+/* ---- passive tracers carried by the flow (new work: the reference evolves b' alone) -------------------------------------------
+ * K scalars stepped with the model's own advection-diffusion operator: the same BDF scheme, the same matrix M + theta (Kh + Kv) and the
+ * same velocity extrapolation as b' (csrc/tracers_core.h).  Tracer k has nodal values c (free DoFs in the buoyancy
+ * numbering; Dirichlet nodes take the tracer's OWN values, not b_diri), a background gradient gamma (the full tracer is gamma z + c)
+ * and a uniform source.  npg_tracers_rhs writes, for every tracer and every row i,
+ *    y_k[i] = int ( c1 c + c2 c_prev - cdt ( u~ . grad c~ + u~_z gamma_k - source_k ) ) phi_i
+ *           - int ( c_D phi_i + theta ( kappa_h grad_h c_D . grad_h phi_i + kappa_v d_z c_D d_z phi_i ) )
+ *           + theta gamma_k rhs_diff1[i] + dt flux_k[i]
+ * with the scheme constants of npg_fe_evolution_rhs, c_D = the tracer's Dirichlet part, kappa_h / kappa_v the engine's CURRENT tables
+ * (the tracers follow the convection closure), rhs_diff1 = npg_fe_assemble_rhs_diff(fe, 1.0, .), shared by all tracers.
+ * One launch evaluates u~ at the quadrature points once per cell and loops over the tracers; a second one gathers the rows in cell
+ * order: no atomics, the same bits on every call, and tracer k's output does not depend on the other tracers of the call.  The
+ * arithmetic follows npg_fe_set_precision.  The handle owns the local vectors (ntracer * nloc_b * ncell doubles); the engine must
+ * outlive it.  Validation (NPG_EINVAL + message) happens before anything is launched. */
+int npg_tracers_create(npg_fe *fe, int ntracer, npg_tracers **out);
+int npg_tracers_destroy(npg_tracers *T);
+/* diri_or_null[n_b_diri]: the tracer's values at the Dirichlet nodes in the order of npg_fe_desc.b_diri (NULL = zeros) */
+int npg_tracers_set(npg_tracers *T, int k, const double *diri_or_null, double gamma, double source);
+/* c, c_prev, flux, y: [ntracer * n_b], tracer k at k * n_b.  rhs_diff1 may be NULL only if every gamma is 0; flux may be NULL. */
+int npg_tracers_rhs(npg_tracers *T, int scheme, double dt, double theta, const npg_vec *c, const npg_vec *c_prev,
+                    const npg_vec *x_inv, const npg_vec *x_inv_prev, const npg_vec *rhs_diff1_or_null,
+                    const npg_vec *flux_or_null, npg_vec *y);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (new work: the reference is single-device) ----------------- */
 #define NPG_UNIQUE_ID_BYTES 128

@@ -20,6 +20,7 @@ from .sampling import (GridDiagnostics, GridIntegrals, GridSamples, Located, Poi
                        barotropic_streamfunction, depth, find_H, nan_eval, overturning_streamfunction, sample_profiles,
                        sample_slice, sample_to_grid, zonal_mean, zonal_width)
 from .timesteppers import BDF1, BDF2, update_dt, update_t
+from .tracers import PassiveTracers, TracerSpec
 from .watermass import BuoyancyClasses, ClassRecorder, ClassTable
 
 __all__ = [n for n in dir() if not n.startswith("_")]

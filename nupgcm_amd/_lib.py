@@ -164,6 +164,8 @@ def _declare(L, partial=False):
         "npg_particles_create": [P, I64, PP], "npg_particles_destroy": [P], "npg_particles_set": [P, VP, D],
         "npg_particles_set_period": [P, VP], "npg_particles_advance": [P, P, P, P, P, D, D, D, I64],
         "npg_particles_download": [P, VP, VP, VP, VP, VP], "npg_particles_positions": [P, P],
+        "npg_tracers_create": [P, C.c_int, PP], "npg_tracers_destroy": [P], "npg_tracers_set": [P, C.c_int, VP, D, D],
+        "npg_tracers_rhs": [P, C.c_int, D, D, P, P, P, P, P, P, P],
         "npg_comm_unique_id": [VP], "npg_comm_init": [P, VP, C.c_int, C.c_int],
         "npg_comm_allreduce_sum": [P, C.POINTER(D), C.c_int], "npg_comm_info": [P, C.c_char_p, C.c_size_t], "npg_comm_disable_peer": [P], "npg_comm_allreduce_vec": [P, P],
         "npg_comm_allgather_segments": [P, P, C.c_int, VP, VP, VP, VP, P],

@@ -501,6 +501,7 @@ NPG_API int npg_fe_create(npg_ctx *ctx, const npg_fe_desc *desc, npg_fe **out) {
     fe->ctx = ctx;
     fe->n_inv = desc->n_inv;
     fe->n_b = desc->n_b;
+    fe->n_b_diri = std::max<int64_t>(0, desc->n_b_diri);
     NPG_HIP(hipSetDevice(ctx->device));
     FeDev &d = fe->d;
     d.ncell = nc;

@@ -56,6 +56,7 @@ struct npg_fe {
     npg_ctx *ctx = nullptr;
     npg::FeDev d{};
     int64_t n_inv = 0, n_b = 0;
+    int64_t n_b_diri = 0;           // entries of the buoyancy Dirichlet value table (tracers keep one of their own per tracer)
     std::vector<void *> allocs;
     double *loc = nullptr;          // [nb][ncell]
     int64_t *gptr = nullptr;        // inverted index of the buoyancy rows (vector pass 2, matrix rows)

@@ -1639,3 +1639,113 @@ NPG_API int npg_particles_positions(const npg_particles *P, npg_vec *out) {
     std::copy(P->xyz.begin(), P->xyz.end(), out->d);
     return NPG_OK;
 }
+
+// ---- passive tracers carried by the flow (csrc/tracers.hip on the host): the per-cell arithmetic is the SAME code
+// (csrc/tracers_core.h); pass 2 walks the engine's inverted index in cell order, as gather_rows does. ----------------------------------
+#include "../csrc/tracers_core.h"
+
+struct npg_tracers {
+    npg_fe *fe = nullptr;
+    int ntracer = 0;
+    int64_t n_diri = 0;
+    std::vector<double> loc, diri, gamma, source;        // [K][ncell][nb], [K][n_diri], [K], [K]
+    std::vector<uint8_t> lift;
+};
+namespace {
+struct HostTrShape {     // the engine's shape tables as cell_tracers reads them
+    const double *qw, *N2, *Nb, *dNb;
+};
+struct HostTrCells {     // and its cell tables ([cell][component])
+    const npg_fe *fe;
+    double G(int k, int64_t c) const { return fe->G[(size_t)c * 12 + k]; }
+    double wdet(int64_t c) const { return fe->wdet[(size_t)c]; }
+    double u(const double *x, int l, int64_t c) const { return fval(x, fe->u_diri, fe->cu[(size_t)c * 30 + l]); }
+    int32_t cb(int i, int64_t c) const { return fe->cb[(size_t)c * fe->nb + i]; }
+    double kh(int q, int64_t c) const { return fe->coef[1][(size_t)c * fe->nq + q]; }
+    double kv(int q, int64_t c) const { return fe->coef[2][(size_t)c * fe->nq + q]; }
+    size_t loc(int i, int64_t c) const { return (size_t)c * fe->nb + i; }
+};
+struct HostTrVel {       // a cell's velocities at the quadrature points
+    double a[3 * npg::kTrMaxQ];
+    double &operator()(int j) { return a[j]; }
+};
+}  // namespace
+
+NPG_API int npg_tracers_create(npg_fe *fe, int ntracer, npg_tracers **out) {
+    REQUIRE(fe && out, "npg_tracers_create: NULL argument");
+    REQUIRE(ntracer >= 1, "npg_tracers_create: ntracer must be at least 1, got %d", ntracer);
+    REQUIRE(ntracer <= 65535, "npg_tracers_create: at most 65535 tracers, got %d", ntracer);
+    npg_tracers *T = new npg_tracers();
+    T->fe = fe;
+    T->ntracer = ntracer;
+    T->n_diri = (int64_t)fe->b_diri.size();              // (the engine keeps one spare zero behind its n_b_diri values)
+    T->loc.assign((size_t)ntracer * fe->ncell * fe->nb, 0.0);
+    T->diri.assign((size_t)ntracer * T->n_diri, 0.0);
+    T->gamma.assign((size_t)ntracer, 0.0);
+    T->source.assign((size_t)ntracer, 0.0);
+    T->lift.assign((size_t)ntracer, 0);
+    *out = T;
+    return NPG_OK;
+}
+NPG_API int npg_tracers_destroy(npg_tracers *T) {
+    delete T;
+    return NPG_OK;
+}
+NPG_API int npg_tracers_set(npg_tracers *T, int k, const double *diri_or_null, double gamma, double source) {
+    REQUIRE(T, "npg_tracers_set: NULL handle");
+    REQUIRE(k >= 0 && k < T->ntracer, "npg_tracers_set: tracer %d out of range (ntracer = %d)", k, T->ntracer);
+    REQUIRE(std::isfinite(gamma) && std::isfinite(source), "npg_tracers_set: gamma and source must be finite");
+    const int64_t nd = T->n_diri - 1;
+    bool any = false;
+    if (diri_or_null)
+        for (int64_t j = 0; j < nd; ++j) {
+            REQUIRE(std::isfinite(diri_or_null[j]), "npg_tracers_set: Dirichlet value %lld is not finite", (long long)j);
+            any = any || diri_or_null[j] != 0.0;
+        }
+    for (int64_t j = 0; j < nd; ++j) T->diri[(size_t)k * T->n_diri + j] = diri_or_null ? diri_or_null[j] : 0.0;
+    T->gamma[(size_t)k] = gamma;
+    T->source[(size_t)k] = source;
+    T->lift[(size_t)k] = any;
+    return NPG_OK;
+}
+NPG_API int npg_tracers_rhs(npg_tracers *T, int scheme, double dt, double theta, const npg_vec *c, const npg_vec *c_prev,
+                            const npg_vec *x_inv, const npg_vec *x_inv_prev, const npg_vec *rhs_diff1_or_null, const npg_vec *flux_or_null,
+                            npg_vec *y) {
+    REQUIRE(T, "npg_tracers_rhs: NULL handle");
+    REQUIRE(c && c_prev && x_inv && x_inv_prev && y, "npg_tracers_rhs: NULL state vector");
+    npg_fe *fe = T->fe;
+    const int K = T->ntracer;
+    const int64_t nb = fe->n_b, nc = fe->ncell;
+    REQUIRE(scheme == NPG_BDF1 || scheme == NPG_BDF2, "npg_tracers_rhs: scheme must be NPG_BDF1 or NPG_BDF2, got %d", scheme);
+    REQUIRE(c->n == K * nb && c_prev->n == K * nb, "npg_tracers_rhs: tracer vectors must have ntracer * n_b = %lld entries", (long long)(K * nb));
+    REQUIRE(y->n == K * nb, "npg_tracers_rhs: the output vector must have ntracer * n_b = %lld entries", (long long)(K * nb));
+    REQUIRE(x_inv->n == fe->n_inv && x_inv_prev->n == fe->n_inv, "npg_tracers_rhs: inversion vectors must have %lld entries",
+            (long long)fe->n_inv);
+    REQUIRE(!rhs_diff1_or_null || rhs_diff1_or_null->n == nb, "npg_tracers_rhs: rhs_diff1 must have n_b = %lld entries", (long long)nb);
+    REQUIRE(!flux_or_null || flux_or_null->n == K * nb, "npg_tracers_rhs: flux must have ntracer * n_b = %lld entries", (long long)(K * nb));
+    bool lift = false;
+    for (int k = 0; k < K; ++k) {
+        REQUIRE(T->gamma[(size_t)k] == 0.0 || rhs_diff1_or_null,
+                "npg_tracers_rhs: tracer %d has a background gradient (gamma = %g) but rhs_diff1 is NULL", k, T->gamma[(size_t)k]);
+        lift = lift || T->lift[(size_t)k];
+    }
+    REQUIRE(!lift || (!fe->coef[1].empty() && !fe->coef[2].empty()),
+            "npg_tracers_rhs: a tracer has non-zero Dirichlet values but the coefficients kappa_h / kappa_v have not been set");
+    const HostTrShape s{fe->qw.data(), fe->N2.data(), fe->Nb.data(), fe->dNb.data()};
+    const HostTrCells t{fe};
+    const npg::TracerSet ts{K, nb, T->n_diri, nc * fe->nb, c->d, c_prev->d, T->diri.data(), T->gamma.data(), T->source.data(), T->loc.data()};
+    const bool bdf2 = scheme == NPG_BDF2;
+#pragma omp parallel for schedule(static)
+    for (int64_t cell = 0; cell < nc; ++cell) {
+        HostTrVel uq;
+        if (fe->nb == 10) npg::cell_tracers<double, 10>(s, t, uq, fe->nq, bdf2, dt, theta, x_inv->d, x_inv_prev->d, ts, cell);
+        else npg::cell_tracers<double, 4>(s, t, uq, fe->nq, bdf2, dt, theta, x_inv->d, x_inv_prev->d, ts, cell);
+    }
+#pragma omp parallel for schedule(static) collapse(2)
+    for (int k = 0; k < K; ++k)
+        for (int64_t r = 0; r < nb; ++r)
+            y->d[(size_t)k * nb + r] = npg::tracer_row(fe->gptr.data(), fe->gidx.data(), T->loc.data() + (size_t)k * ts.loc_stride, r,
+                                                       theta * T->gamma[(size_t)k], dt, rhs_diff1_or_null ? rhs_diff1_or_null->d : nullptr,
+                                                       flux_or_null ? flux_or_null->d + (size_t)k * nb : nullptr);
+    return NPG_OK;
+}

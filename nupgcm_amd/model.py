@@ -67,6 +67,7 @@ class Model:
         # reference's recipe
         self.extrapolate_guess = False
         self.stats = []
+        self.tracers = None         # tracers.PassiveTracers(model, ...): run() steps them directly after evolve()
         self._prev = None
         self._u_view = inversion.solver.x.view(0, fe_data.dofs.nu)     # x[1:nu] = u (p_inversion = [p_u; nu + p_p])
 
@@ -137,6 +138,7 @@ def run(model: Model, n_info=10, n_save=float("inf"), n_plot=float("inf"), advec
     fe = model.evolution.fe
     ctx = model.arch.ctx
     comm = getattr(model, "comm", None)          # partition.PartitionedModel: host-level reductions over the ranks
+    tracers = getattr(model, "tracers", None)    # passive tracers ride on the step (tracers.PassiveTracers)
     if model._prev is None:
         # copies of previous and current u, b (src/model.jl:119-123)
         model._prev = dict(x_prev=inv_x.copy(), b_prev=b.copy(), x_curr=inv_x.copy(), b_curr=b.copy())
@@ -156,6 +158,8 @@ def run(model: Model, n_info=10, n_save=float("inf"), n_plot=float("inf"), advec
         pv["x_curr"].copy_from(inv_x)                                                           # src/model.jl:140-141
         pv["b_curr"].copy_from(b)
         evolve(model, pv["x_prev"], pv["b_prev"])                                               # src/model.jl:144
+        if tracers is not None:
+            tracers.step(model, pv["x_prev"])
         order = int(getattr(model, "extrapolate_guess", 0) or 0)
         if order >= 2 and not getattr(model, "_warned_quadratic_guess", False):
             import warnings
@@ -177,6 +181,9 @@ def run(model: Model, n_info=10, n_save=float("inf"), n_plot=float("inf"), advec
         xm, xnan = model._u_view.maxabs()
         bm, bnan = b.maxabs()
         blow = max(xm, bm) > 1e3 or xnan or bnan
+        if tracers is not None:
+            cm, cnan = tracers.maxabs()
+            blow = blow or cm > 1e3 or cnan
         if comm is not None:
             blow = comm.any(blow)                                 # every rank leaves the loop together
         if blow:
@@ -188,6 +195,8 @@ def run(model: Model, n_info=10, n_save=float("inf"), n_plot=float("inf"), advec
                 pv["x_prev2"].copy_from(pv["x_prev"])
         pv["x_prev"], pv["x_curr"] = pv["x_curr"], pv["x_prev"]                                 # src/model.jl:156-157
         pv["b_prev"], pv["b_curr"] = pv["b_curr"], pv["b_prev"]
+        if tracers is not None:
+            tracers.rotate()
         if frc.eddy_param.is_on and advection and i % 10 == 0:                                  # src/model.jl:160-170
             ep = frc.eddy_param
             fe.update_nu_eddy(ep.N2min, prm.alpha, prm.N2, b)

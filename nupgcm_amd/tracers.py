@@ -1,0 +1,176 @@
+"""Passive tracers carried by the flow (npg_tracers_rhs): ideal age, dyes, a second component with its own background
+gradient and surface flux.  The reference evolves b' alone.
+
+A tracer obeys the model's own advection-diffusion equation, stepped every timestep with the same BDF scheme, the same matrix
+A = M + theta (Kh + Kv), the same preconditioner and the same velocity extrapolation as b':
+
+    A c^{n+1} = int ( c1 c + c2 c_prev - cdt ( u~ . grad c~ + u~_z Gamma - S ) ) phi  -  Dirichlet lift  +  theta Gamma rhs_diff1  +  dt flux
+
+The full tracer is Gamma z + c.  The K right-hand sides come from ONE fused element launch that evaluates the velocity at the
+quadrature points once per cell (csrc/tracers.hip); the K solves are K warm-started CG solves on views of the stacked vectors.
+Tracers use the buoyancy's diffusivities - the engine's current kappa_h / kappa_v tables, so they follow the convection closure -
+and the buoyancy's Dirichlet tags with values of their own.  They are passive: u, p and b' do not change by a bit."""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Any
+
+import numpy as np
+
+from . import _lib as L
+from .architectures import DeviceVector
+from .evolution import evolution_parameter
+from .iterative_solvers import CgWorkspace, IterativeSolverToolkit, iterative_solve
+from .timesteppers import BDF1
+
+
+@dataclass
+class TracerSpec:
+    """name; initial (a function of x, an array in native free-DoF order as set_b takes, or None = 0); dirichlet (a number, a function
+    of x, or None = 0, on the buoyancy's Dirichlet tags); gamma (background gradient: the full tracer is gamma z + c); source (uniform);
+    flux (a number, a function of x, or None: surface flux over the mesh's surface tags, scaled as build_rhs_flux scales b's)"""
+    name: str
+    initial: Any = None
+    dirichlet: Any = None
+    gamma: float = 0.0
+    source: float = 0.0
+    flux: Any = None
+
+
+def _spec(t):
+    if isinstance(t, TracerSpec):
+        return t
+    if isinstance(t, dict):
+        return TracerSpec(**t)
+    raise TypeError(f"PassiveTracers: a tracer is a TracerSpec or a dict of its fields, got {type(t).__name__}")
+
+
+def _solve_stats(stats):
+    return dict(stats) if stats is not None else None
+
+
+class PassiveTracers:
+    """PassiveTracers(model, tracers): K tracers on the model's mesh, set as `model.tracers`; run() then steps them directly after
+    evolve().  `c`, `c_prev`, `c_curr` are stacked device vectors (tracer k at k * n_b, the buoyancy's numbering); `values(k | name)`
+    returns tracer k in native free-DoF order on the host; `stats[i]` holds the K CG statistics of step i."""
+
+    def __init__(self, model, tracers):
+        if getattr(model, "comm", None) is not None or getattr(model, "layout", None) is not None \
+                or getattr(model.arch.ctx, "nranks", 1) > 1:
+            raise NotImplementedError("PassiveTracers: distributed and mesh-partitioned models are not supported; tracers run on a "
+                                      "single-device model")
+        if model.evolution is None:
+            raise ValueError("PassiveTracers: the model has no EvolutionToolkit")
+        self.specs = [_spec(t) for t in tracers]
+        if not self.specs:
+            raise ValueError("PassiveTracers: at least one tracer is needed")
+        names = [s.name for s in self.specs]
+        if len(set(names)) != len(names):
+            raise ValueError(f"PassiveTracers: tracer names must be distinct, got {names}")
+        self.names = names
+        self.model = model
+        ev, fed = model.evolution, model.fe_data
+        self.fe = ev.fe
+        ctx = self.ctx = model.arch.ctx
+        K, nb = len(self.specs), fed.dofs.nb
+        self.ntracer, self.nb = K, nb
+        h = C.c_void_p()
+        L.check(L.lib().npg_tracers_create(self.fe.h, K, C.byref(h)))
+        self.h = h
+        s, d, t, m = fed.spaces, fed.dofs, fed.tables, fed.mesh
+        diri_nodes = np.nonzero(s.b_dof < 0)[0]                      # the order of DeviceTables.b_diri
+        xd = m.node_coords[:s.nb_nodes][diri_nodes]
+        c0 = np.zeros(K * nb)
+        flux = np.zeros(K * nb)
+        any_flux = False
+        self.gamma, self.source = np.zeros(K), np.zeros(K)
+        for k, sp in enumerate(self.specs):
+            dv = None
+            if sp.dirichlet is not None:
+                dv = np.zeros(len(t.b_diri))                         # (embedded 2-D meshes: one spare zero behind the nodes' values)
+                v = sp.dirichlet(xd) if callable(sp.dirichlet) else np.full(len(diri_nodes), float(sp.dirichlet))
+                dv[:len(diri_nodes)] = np.asarray(v, dtype=float)
+                dv = L.as_f64(dv)
+            self.gamma[k], self.source[k] = float(sp.gamma), float(sp.source)
+            L.check(L.lib().npg_tracers_set(self.h, k, None if dv is None else L.ptr(dv), self.gamma[k], self.source[k]))
+            if sp.initial is not None:
+                vals = s.interpolate_b(sp.initial) if callable(sp.initial) else np.asarray(sp.initial, dtype=float)
+                if vals.shape != (nb,):
+                    raise ValueError(f"PassiveTracers: tracer '{sp.name}': expected {nb} free values, got {vals.shape}")
+                c0[k * nb:(k + 1) * nb] = vals[d.p_b]
+            if sp.flux is not None:
+                fn = sp.flux if callable(sp.flux) else (lambda x, c=float(sp.flux): np.full(x.shape[:-1], c))
+                load = m.surface_load(lambda x: model.params.alpha * fn(x))[:s.nb_nodes]
+                pos = t.b_pos
+                f = np.zeros(nb)
+                f[pos[pos >= 0]] = load[pos >= 0]
+                flux[k * nb:(k + 1) * nb] = f
+                any_flux = True
+        self.c = DeviceVector.from_host(ctx, c0)
+        self.c_prev, self.c_curr = self.c.copy(), self.c.copy()
+        self.y = DeviceVector(ctx, K * nb)
+        self.flux = DeviceVector.from_host(ctx, flux) if any_flux else None
+        self.rhs_diff1 = self.fe.rhs_diff(1.0, DeviceVector(ctx, nb)) if np.any(self.gamma != 0.0) else None
+        # K solves with the evolution toolkit's own A and P, each with its own workspace (warm start: the workspace's x aliases the
+        # tracer's slice of c, as IterativeSolverToolkit.x aliases workspace.x)
+        self.solvers = []
+        for k in range(K):
+            ws = CgWorkspace(ctx, nb)
+            ws.x = self.c.view(k * nb, nb)
+            self.solvers.append(IterativeSolverToolkit(ev.solver.A, ev.solver.P, self.y.view(k * nb, nb), ws, ev.solver.kwargs,
+                                                       f"Tracer {names[k]}"))
+        self.stats = []
+
+    def __del__(self):
+        try:
+            if self.h:
+                L.lib().npg_tracers_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def index(self, k):
+        return self.names.index(k) if isinstance(k, str) else int(k)
+
+    def view(self, k, which="c"):
+        """tracer k's window of a stacked vector ("c", "c_prev", "c_curr", "y")"""
+        k = self.index(k)
+        return getattr(self, which).view(k * self.nb, self.nb)
+
+    def values(self, k):
+        """tracer k (index or name) on the host, free values in native order - as State.b"""
+        return self.view(k).to_host(self.model.fe_data.dofs.inv_p_b)
+
+    def rhs(self, scheme, dt, theta, x_inv, x_inv_prev, y=None):
+        """one npg_tracers_rhs call on the current c / c_prev into `y` (default: the solvers' right-hand sides)"""
+        y = self.y if y is None else y
+        L.check(L.lib().npg_tracers_rhs(self.h, int(scheme), float(dt), float(theta), self.c.h, self.c_prev.h, x_inv.h, x_inv_prev.h,
+                                        None if self.rhs_diff1 is None else self.rhs_diff1.h,
+                                        None if self.flux is None else self.flux.h, y.h))
+        return y
+
+    def step(self, model, x_inv_prev):
+        """what evolve() does for b', for every tracer: [convection closure on: rhs_diff1 from the refreshed kappa_v] -> one fused
+        right-hand-side call -> K CG solves with the evolution toolkit's A and P (already rebuilt by evolve() for this step)."""
+        ev, ts, prm = model.evolution, model.timestepper, model.params
+        self.c_curr.copy_from(self.c)                    # what run() does for b_curr before evolve()
+        if self.rhs_diff1 is not None and model.forcings.conv_param.is_on:
+            self.fe.rhs_diff(1.0, self.rhs_diff1)
+        theta = evolution_parameter(prm, ts)
+        scheme = L.NPG_BDF1 if isinstance(ts, BDF1) else L.NPG_BDF2
+        self.rhs(scheme, ts.dt, theta, model.inversion.solver.x, x_inv_prev)
+        step_stats = []
+        for s in self.solvers:
+            s.A, s.P = ev.solver.A, ev.solver.P          # (CPU(): collect_evolution_LHS replaces the factorisation object)
+            iterative_solve(s)
+            step_stats.append(_solve_stats(s.workspace.stats))
+        self.stats.append(step_stats)
+        return self
+
+    def rotate(self):
+        """the history rotation of run(): c_prev <-> c_curr"""
+        self.c_prev, self.c_curr = self.c_curr, self.c_prev
+
+    def maxabs(self):
+        return self.c.maxabs()
