@@ -34,6 +34,7 @@ typedef struct npg_vec npg_vec;
 typedef struct npg_csr npg_csr;
 typedef struct npg_gmres npg_gmres;
 typedef struct npg_cg npg_cg;
+typedef struct npg_cg_multi npg_cg_multi;
 typedef struct npg_fe npg_fe;
 typedef struct npg_halo npg_halo;
 typedef struct npg_precond npg_precond;
@@ -287,6 +288,18 @@ int npg_cg_destroy(npg_cg *ws);
 int npg_cg_solve(npg_cg *ws, const npg_csr *A, int precond_kind, double precond_scalar, const npg_vec *precond_diag,
                  const npg_vec *y, npg_vec *x, double atol, double rtol, int64_t itmax, npg_solve_stats *stats);
 int64_t npg_cg_history(npg_cg *ws, double *buf, int64_t cap);
+
+/* CG for several right-hand sides against one matrix: every column has the bits of npg_cg_solve on that column;
+ * the matrix is streamed once per iteration for up to eight columns.  y, x: stacked vectors of ncol * n (column k at k * n); x is
+ * the warm start and the result.  stats: ncol entries (may be NULL); `seconds` is the whole call's, in every entry.  A: plain CSR
+ * (no node blocks, records or internal renumbering).  Single device: there is no halo variant. */
+#define NPG_CG_MULTI_MAX 32
+int npg_cg_multi_create(npg_ctx *ctx, int64_t n, int ncol_max, npg_cg_multi **out);
+int npg_cg_multi_destroy(npg_cg_multi *ws);
+int npg_cg_multi_solve(npg_cg_multi *ws, const npg_csr *A, int precond_kind, double precond_scalar, const npg_vec *precond_diag,
+                       int ncol, const npg_vec *y, npg_vec *x, double atol, double rtol, int64_t itmax, npg_solve_stats *stats);
+/* residual history of column `col` of the last solve: returns entries written */
+int64_t npg_cg_multi_history(npg_cg_multi *ws, int col, double *buf, int64_t cap);
 
 /* ---- general preconditioners + flexible GMRES: src/preconditioners.jl:1-125 and SURVEY 8f rank 1 --------------------------
  * `P` of the IterativeSolverToolkit is a tagged union: NPG_PRECOND_NONE / _SCALAR / _DIAG are linear diagonal actions that

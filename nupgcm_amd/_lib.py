@@ -127,6 +127,8 @@ def _declare(L, partial=False):
         "npg_gmres_set_profile": [P, C.c_int], "npg_gmres_set_split": [P, C.c_int], "npg_gmres_set_basis": [P, C.c_int], "npg_gmres_set_gather": [P, C.c_int], "npg_gmres_get_profile": [P, C.POINTER(D), C.POINTER(I64)], "npg_gmres_last_config": [P, VP, C.c_int],
         "npg_cg_create": [P, I64, PP], "npg_cg_destroy": [P],
         "npg_cg_solve": [P, P, C.c_int, D, P, P, P, D, D, I64, C.POINTER(SolveStats)],
+        "npg_cg_multi_create": [P, I64, C.c_int, PP], "npg_cg_multi_destroy": [P],
+        "npg_cg_multi_solve": [P, P, C.c_int, D, P, C.c_int, P, P, D, D, I64, C.POINTER(SolveStats)],
         "npg_precond_create": [P, C.c_int, C.c_int, PP], "npg_precond_destroy": [P],
         "npg_precond_blockdiag_set": [P, C.c_int, I64, P, P, I64, D, D], "npg_precond_blockdiag_set_ilu0": [P, C.c_int, P],
         "npg_ilu0_create": [P, P, C.POINTER(P)], "npg_ilu0_destroy": [P], "npg_ilu0_refactor": [P, P], "npg_ilu0_apply": [P, P, P],
@@ -188,6 +190,9 @@ def _declare(L, partial=False):
     L.npg_gmres_history.argtypes = [P, VP, I64]
     L.npg_cg_history.restype = I64
     L.npg_cg_history.argtypes = [P, VP, I64]
+    if hasattr(L, "npg_cg_multi_history"):
+        L.npg_cg_multi_history.restype = I64
+        L.npg_cg_multi_history.argtypes = [P, C.c_int, VP, I64]
     if hasattr(L, "npg_fgmres_history"):           # (the host library has no flexible GMRES: general preconditioners are device work)
         L.npg_fgmres_history.restype = I64
         L.npg_fgmres_history.argtypes = [P, VP, I64]
@@ -221,4 +226,5 @@ NPG_FE_FP64, NPG_FE_FP32 = 0, 1
 NPG_SAMPLE_U, NPG_SAMPLE_P, NPG_SAMPLE_B, NPG_SAMPLE_GRAD_B = 1, 2, 3, 4
 NPG_NINT = 15
 NPG_NCLS = 8
+NPG_CG_MULTI_MAX = 32
 NPG_MAT_M, NPG_MAT_KH, NPG_MAT_KV, NPG_MAT_A, NPG_MAT_B = 1, 2, 3, 4, 5

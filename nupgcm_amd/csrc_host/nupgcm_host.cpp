@@ -670,6 +670,75 @@ NPG_API int npg_cg_solve(npg_cg *ws, const npg_csr *A, int precond_kind, double 
     return NPG_OK;
 }
 
+// Several right-hand sides against one matrix: the same C ABI as the device library's batched solver; here a loop over the columns
+// that runs the CG above on each column's slice, so every column has that solver's bits, statistics and history.
+struct npg_cg_multi {
+    npg_ctx *ctx = nullptr;
+    int64_t n = 0;
+    int ncol_max = 0, last_ncol = 0;
+    npg_cg *one = nullptr;
+    std::vector<std::vector<double>> hist;
+};
+NPG_API int npg_cg_multi_create(npg_ctx *ctx, int64_t n, int ncol_max, npg_cg_multi **out) {
+    REQUIRE(ctx && out && n > 0, "npg_cg_multi_create: bad argument");
+    REQUIRE(ncol_max >= 1 && ncol_max <= NPG_CG_MULTI_MAX, "npg_cg_multi_create: ncol_max = %d, need 1 <= ncol_max <= %d", ncol_max,
+            NPG_CG_MULTI_MAX);
+    npg_cg_multi *ws = new npg_cg_multi();
+    ws->ctx = ctx;
+    ws->n = n;
+    ws->ncol_max = ncol_max;
+    if (int rc = npg_cg_create(ctx, n, &ws->one)) {
+        delete ws;
+        return rc;
+    }
+    ws->hist.resize((size_t)ncol_max);
+    *out = ws;
+    return NPG_OK;
+}
+NPG_API int npg_cg_multi_destroy(npg_cg_multi *ws) {
+    if (!ws) return NPG_OK;
+    npg_cg_destroy(ws->one);
+    delete ws;
+    return NPG_OK;
+}
+NPG_API int npg_cg_multi_solve(npg_cg_multi *ws, const npg_csr *A, int precond_kind, double precond_scalar, const npg_vec *precond_diag,
+                               int ncol, const npg_vec *y, npg_vec *x, double atol, double rtol, int64_t itmax, npg_solve_stats *stats) {
+    REQUIRE(ws && A && y && x, "npg_cg_multi_solve: NULL argument");
+    REQUIRE(ncol >= 1 && ncol <= ws->ncol_max, "npg_cg_multi_solve: ncol = %d, the workspace holds 1 .. %d columns", ncol, ws->ncol_max);
+    REQUIRE(A->ctx == ws->ctx && y->ctx == ws->ctx && x->ctx == ws->ctx &&
+                (precond_kind != NPG_PRECOND_DIAG || !precond_diag || precond_diag->ctx == ws->ctx),
+            "npg_cg_multi_solve: the workspace, the matrix and the vectors must belong to one context");
+    REQUIRE(A->m == ws->n && A->n == ws->n && y->n == (int64_t)ncol * ws->n && x->n == (int64_t)ncol * ws->n,
+            "npg_cg_multi_solve: workspace is for n=%lld and %d columns want vectors of %lld, but A is %lldx%lld, y has %lld, x has %lld",
+            (long long)ws->n, ncol, (long long)ncol * (long long)ws->n, (long long)A->m, (long long)A->n, (long long)y->n, (long long)x->n);
+    REQUIRE(precond_kind == NPG_PRECOND_NONE || precond_kind == NPG_PRECOND_SCALAR ||
+                (precond_kind == NPG_PRECOND_DIAG && precond_diag && precond_diag->n == ws->n),
+            "npg_cg_multi_solve: bad preconditioner");
+    const auto t0 = std::chrono::steady_clock::now();
+    ws->last_ncol = ncol;
+    for (int k = 0; k < ncol; ++k) {
+        npg_vec yk, xk;
+        yk.ctx = xk.ctx = ws->ctx;
+        yk.n = xk.n = ws->n;
+        yk.owns = xk.owns = false;
+        yk.d = y->d + (size_t)k * (size_t)ws->n;
+        xk.d = x->d + (size_t)k * (size_t)ws->n;
+        if (int rc = npg_cg_solve(ws->one, A, precond_kind, precond_scalar, precond_diag, &yk, &xk, atol, rtol, itmax, stats ? stats + k : nullptr))
+            return rc;
+        ws->hist[(size_t)k] = ws->one->hist;
+    }
+    const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    for (int k = 0; stats && k < ncol; ++k) stats[k].seconds = seconds;
+    return NPG_OK;
+}
+NPG_API int64_t npg_cg_multi_history(npg_cg_multi *ws, int col, double *buf, int64_t cap) {
+    if (!ws || !buf || cap <= 0 || col < 0 || col >= ws->last_ncol) return 0;
+    const std::vector<double> &h = ws->hist[(size_t)col];
+    const int64_t k = std::min<int64_t>(cap, (int64_t)h.size());
+    memcpy(buf, h.data(), (size_t)k * sizeof(double));
+    return k;
+}
+
 // ---- element kernels ---------------------------------------------------------------------------------------------------------------------
 struct npg_fe {
     npg_ctx *ctx = nullptr;

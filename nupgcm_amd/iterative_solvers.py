@@ -284,6 +284,48 @@ class CgWorkspace(_Workspace):
         return buf[:max(k, 0)]
 
 
+class BatchedCgWorkspace(_Workspace):
+    """ncol CgWorkspaces in one (npg_cg_multi_*): `solve` runs CG on ncol right-hand sides against ONE matrix and
+    preconditioner, the matrix streamed once per iteration for up to eight columns.  Every column has the bits, the statistics and
+    the history of CgWorkspace.solve on that column.  `x` and `y` are stacked vectors (column k at k n); x is warm start and
+    result.  At most 32 columns."""
+
+    def __init__(self, ctx, n, ncol):
+        super().__init__()
+        h = C.c_void_p()
+        L.check(L.lib().npg_cg_multi_create(ctx.h, int(n), int(ncol), C.byref(h)))
+        self.h, self.ctx, self.n, self.ncol = h, ctx, int(n), int(ncol)
+        self.x = DeviceVector(ctx, self.ncol * self.n)
+
+    def __del__(self):
+        try:
+            if self.h:
+                L.lib().npg_cg_multi_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def solve(self, A: DeviceCSR, y: DeviceVector, x: DeviceVector, P, atol=1e-6, rtol=1e-6, itmax=0, ncol=None, **_ignored):
+        """one batched solve of the ncol (default: len(x) / n) columns of (y, x); returns (and keeps in `stats`) the list of their
+        stats dicts"""
+        kind, s, dh = (L.NPG_PRECOND_NONE, 0.0, None) if P is None else P.kind()
+        ncol = max(len(x) // self.n, 1) if ncol is None else int(ncol)
+        st = (L.SolveStats * max(ncol, 1))()
+        L.check(L.lib().npg_cg_multi_solve(self.h, A.h, kind, s, dh, ncol, y.h, x.h, float(atol), float(rtol), int(itmax), st))
+        self.stats = [e.as_dict() for e in st[:ncol]]
+        return self.stats
+
+    def history(self, col):
+        col = int(col)
+        buf = np.empty(int(self.stats[col]["niter"]) + 1 if self.stats else 1)
+        k = L.lib().npg_cg_multi_history(self.h, col, L.ptr(buf), buf.size)
+        return buf[:max(k, 0)]
+
+    def view(self, col):
+        """column `col` of the workspace's x"""
+        return self.x.view(int(col) * self.n, self.n)
+
+
 class IterativeSolverToolkit:
     """src/iterative_solvers.jl:1-9,26-29: {A, P, x, y, workspace, kwargs, label}; x just points to workspace.x."""
 

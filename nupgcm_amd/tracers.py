@@ -7,7 +7,9 @@ A = M + theta (Kh + Kv), the same preconditioner and the same velocity extrapola
     A c^{n+1} = int ( c1 c + c2 c_prev - cdt ( u~ . grad c~ + u~_z Gamma - S ) ) phi  -  Dirichlet lift  +  theta Gamma rhs_diff1  +  dt flux
 
 The full tracer is Gamma z + c.  The K right-hand sides come from ONE fused element launch that evaluates the velocity at the
-quadrature points once per cell (csrc/tracers.hip); the K solves are K warm-started CG solves on views of the stacked vectors.
+quadrature points once per cell (csrc/tracers.hip); the K solves are K warm-started CG solves on views of the stacked vectors, or
+(batched=True) one batched CG per group of at most 32 tracers that streams the matrix once per iteration for up to
+eight columns, with the same bits.
 Tracers use the buoyancy's diffusivities - the engine's current kappa_h / kappa_v tables, so they follow the convection closure -
 and the buoyancy's Dirichlet tags with values of their own.  They are passive: u, p and b' do not change by a bit."""
 from __future__ import annotations
@@ -21,7 +23,7 @@ import numpy as np
 from . import _lib as L
 from .architectures import DeviceVector
 from .evolution import evolution_parameter
-from .iterative_solvers import CgWorkspace, IterativeSolverToolkit, iterative_solve
+from .iterative_solvers import BatchedCgWorkspace, CgWorkspace, IterativeSolverToolkit, iterative_solve
 from .timesteppers import BDF1
 
 
@@ -53,9 +55,12 @@ def _solve_stats(stats):
 class PassiveTracers:
     """PassiveTracers(model, tracers): K tracers on the model's mesh, set as `model.tracers`; run() then steps them directly after
     evolve().  `c`, `c_prev`, `c_curr` are stacked device vectors (tracer k at k * n_b, the buoyancy's numbering); `values(k | name)`
-    returns tracer k in native free-DoF order on the host; `stats[i]` holds the K CG statistics of step i."""
+    returns tracer k in native free-DoF order on the host; `stats[i]` holds the K CG statistics of step i.
+    batched=True solves the K systems of a step with BatchedCgWorkspace (groups of at most 32 tracers); every tracer keeps the bits of
+    the per-tracer solve.  On CPU() iterative_solve takes the reference's direct-solve branches for these sizes, which have no batched
+    form: there batched=True runs the per-tracer path."""
 
-    def __init__(self, model, tracers):
+    def __init__(self, model, tracers, batched=False):
         if getattr(model, "comm", None) is not None or getattr(model, "layout", None) is not None \
                 or getattr(model.arch.ctx, "nranks", 1) > 1:
             raise NotImplementedError("PassiveTracers: distributed and mesh-partitioned models are not supported; tracers run on a "
@@ -120,6 +125,15 @@ class PassiveTracers:
             ws.x = self.c.view(k * nb, nb)
             self.solvers.append(IterativeSolverToolkit(ev.solver.A, ev.solver.P, self.y.view(k * nb, nb), ws, ev.solver.kwargs,
                                                        f"Tracer {names[k]}"))
+        # batched: one workspace per group of at most 32 tracers, its x the group's window of c (the warm start)
+        self.batched = bool(batched) and ctx.device >= 0
+        self.groups = []
+        if self.batched:
+            for k0 in range(0, K, L.NPG_CG_MULTI_MAX):
+                kc = min(L.NPG_CG_MULTI_MAX, K - k0)
+                ws = BatchedCgWorkspace(ctx, nb, kc)
+                ws.x = self.c.view(k0 * nb, kc * nb)
+                self.groups.append((k0, kc, ws, self.y.view(k0 * nb, kc * nb)))
         self.stats = []
 
     def __del__(self):
@@ -152,7 +166,8 @@ class PassiveTracers:
 
     def step(self, model, x_inv_prev):
         """what evolve() does for b', for every tracer: [convection closure on: rhs_diff1 from the refreshed kappa_v] -> one fused
-        right-hand-side call -> K CG solves with the evolution toolkit's A and P (already rebuilt by evolve() for this step)."""
+        right-hand-side call -> K CG solves with the evolution toolkit's A and P (already rebuilt by evolve() for this step) - or,
+        batched, one solve per group of at most 32 tracers."""
         ev, ts, prm = model.evolution, model.timestepper, model.params
         self.c_curr.copy_from(self.c)                    # what run() does for b_curr before evolve()
         if self.rhs_diff1 is not None and model.forcings.conv_param.is_on:
@@ -161,6 +176,11 @@ class PassiveTracers:
         scheme = L.NPG_BDF1 if isinstance(ts, BDF1) else L.NPG_BDF2
         self.rhs(scheme, ts.dt, theta, model.inversion.solver.x, x_inv_prev)
         step_stats = []
+        if self.batched:
+            for _k0, _kc, ws, yg in self.groups:
+                step_stats.extend(_solve_stats(st) for st in ws.solve(ev.solver.A, yg, ws.x, ev.solver.P, **ev.solver.kwargs))
+            self.stats.append(step_stats)
+            return self
         for s in self.solvers:
             s.A, s.P = ev.solver.A, ev.solver.P          # (CPU(): collect_evolution_LHS replaces the factorisation object)
             iterative_solve(s)
