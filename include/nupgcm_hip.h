@@ -231,7 +231,9 @@ typedef struct npg_solve_stats {
     int32_t solved;       /* workspace.stats.solved                                             */
     int32_t niter;        /* workspace.stats.niter (cumulative inner iterations)                */
     int32_t npass;        /* GMRES restart cycles started                                       */
-    int32_t status;       /* 1 solved, 2 itmax reached, 3 breakdown, 4 zero residual at start   */
+    int32_t status;       /* 1 solved, 2 itmax reached, 3 breakdown, 4 zero residual at start.  CG: 3 = the start's r'z is NaN or
+                             Inf (0 iterations), or p'Ap is not positive (zero, negative, NaN): that step is not taken, and x, niter,
+                             rnorm and the history are those of the last completed iteration; or r'z turned NaN  */
     int32_t nreorth;      /* GMRES: second Gram-Schmidt passes taken                            */
     int32_t nflagged;   /* GMRES: Arnoldi steps flagged by the device - a Pythagorean norm that lost > 4 digits (distributed), or a
                          * column that was due a second Gram-Schmidt pass while the fast kernels ran (the next solves use the

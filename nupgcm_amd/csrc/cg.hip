@@ -5,7 +5,10 @@
 // Three kernels per iteration, scalars never leave the device:
 //   CS  Ap = A p (tiled CSR SpMV), partial p'Ap
 //   CU  alpha = gamma / p'Ap ; x += alpha p ; r -= alpha Ap ; z = P r ; partial r'z
+//       p'Ap not positive (zero, negative or NaN): no step, a flag for CP
 //   CP  gamma' = r'z ; stopping test sqrt(gamma') <= atol + rtol sqrt(gamma_0) ; beta = gamma'/gamma ; p = z + beta p
+//       flag set: status 3 with the iterate, the count and the history of the last completed iteration
+// The first CP writes p = z and never reads what an earlier solve left in p.
 // State snapshots alternate between two slots so that a workgroup never reads what another workgroup of the same launch
 // writes.  The host looks at the state every `chunk` iterations only.
 #include <algorithm>
@@ -41,6 +44,7 @@ struct CDev {
     const double *Qp;     // what k_cg_update reduces: Pp on one GPU, the all-reduced row when distributed
     int nQp;
     CSnap *S;   // two slots
+    int *brk;   // 1 when the last CU refused its step (p'Ap not positive); CU writes it in every iteration, the next CP reads it
     double *hist;
     int hist_cap;
     const CParams *prm;
@@ -97,15 +101,19 @@ __global__ void __launch_bounds__(kKB) k_cg_direction(CDev d, int src, int dst, 
         CSnap s = prev;
         if (s.done == 0) {
             const double g = sh.red[0];
+            const bool refused = !s.first && d.brk[0] != 0;
             if (s.first) {
                 s.rnorm0 = sqrt(g);
                 s.rnorm = s.rnorm0;
                 s.eps = d.prm->atol + d.prm->rtol * s.rnorm0;
                 s.first = 0;
                 s.iter = 0;
-                s.done = (g == 0.0) ? 4 : (s.rnorm0 <= s.eps ? 1 : 0);
-                s.pad = 1;   // beta = 0 marker
+                // r'z that is NaN or Inf (y, x0 or the matrix hold one): breakdown, before rnorm0 <= eps = Inf can call it solved
+                s.done = !isfinite(g) ? 3 : ((g == 0.0) ? 4 : (s.rnorm0 <= s.eps ? 1 : 0));
+                s.pad = 1;   // first step: p = z
                 if (blockIdx.x == 0) d.hist[0] = s.rnorm0;
+            } else if (refused) {
+                s.done = 3;  // CU took no step: iter, rnorm, gamma and the history stay at the last completed iteration
             } else {
                 s.rnorm = sqrt(g);
                 s.iter += 1;
@@ -115,13 +123,17 @@ __global__ void __launch_bounds__(kKB) k_cg_direction(CDev d, int src, int dst, 
                 s.pad = 0;
             }
             sh.red[1] = s.pad ? 0.0 : g / prev.gamma;
-            s.gamma = g;
+            if (!refused) s.gamma = g;
         }
         sh.S = s;
         if (blockIdx.x == 0) d.S[dst] = s;
     }
     __syncthreads();
     if (sh.S.done != 0) return;
+    if (sh.S.pad) {      // first step: the old p is not read (it may hold a NaN of an earlier solve, and 0 * NaN is NaN)
+        for (int64_t row = blockIdx.x * (int64_t)kKB + threadIdx.x; row < d.n; row += (int64_t)gridDim.x * kKB) d.p[row] = d.z[row];
+        return;
+    }
     const double beta = sh.red[1];
     for (int64_t row = blockIdx.x * (int64_t)kKB + threadIdx.x; row < d.n; row += (int64_t)gridDim.x * kKB)
         d.p[row] = d.z[row] + beta * d.p[row];
@@ -158,7 +170,10 @@ __global__ void __launch_bounds__(kKB) k_cg_update(CDev d, int slot) {
     reduce_partials<kNS, kMaxI>(d.Qp, d.nQp, 1, sh.tmp, sh.red);
     if (s.done != 0) return;
     const double pAp = sh.red[0];
-    const double alpha = (pAp > 0.0) ? s.gamma / pAp : 0.0;
+    const bool refuse = !(pAp > 0.0);       // the same in every workgroup (and, distributed, on every rank: Qp is the all-reduced row)
+    if (blockIdx.x == 0 && threadIdx.x == 0) d.brk[0] = refuse ? 1 : 0;
+    if (refuse) return;
+    const double alpha = s.gamma / pAp;
     double acc[1] = {0.0};
     for (int64_t row = blockIdx.x * (int64_t)kKB + threadIdx.x; row < d.n; row += (int64_t)gridDim.x * kKB) {
         const double pv = d.p[row];
@@ -188,6 +203,7 @@ struct npg_cg {
     int64_t n = 0;
     double *r = nullptr, *z = nullptr, *p = nullptr, *Ap = nullptr, *Pg = nullptr, *Pp = nullptr;
     CSnap *S = nullptr;
+    int *brk = nullptr;
     CParams *prm = nullptr;
     double *hist = nullptr;
     int hist_cap = 0;
@@ -215,13 +231,12 @@ NPG_API int npg_cg_create(npg_ctx *ctx, int64_t n, npg_cg **out) {
     NPG_HIP(hipMalloc((void **)&ws->Pg, pb));
     NPG_HIP(hipMalloc((void **)&ws->Pp, pb));
     NPG_HIP(hipMalloc((void **)&ws->S, 2 * sizeof(CSnap)));
+    NPG_HIP(hipMalloc((void **)&ws->brk, sizeof(int)));
     NPG_HIP(hipMalloc((void **)&ws->prm, sizeof(CParams)));
     ws->hist_cap = (int)std::min<int64_t>(2 * n + 2, 1 << 22);
     NPG_HIP(hipMalloc((void **)&ws->hist, sizeof(double) * ws->hist_cap));
     NPG_HIP(hipHostMalloc((void **)&ws->h_S, 2 * sizeof(CSnap), hipHostMallocDefault));
     NPG_HIP(hipHostMalloc((void **)&ws->h_prm, sizeof(CParams), hipHostMallocDefault));
-    NPG_HIP(hipMemsetAsync(ws->p, 0, vb, ctx->stream));
-    NPG_HIP(hipStreamSynchronize(ctx->stream));
     *out = ws;
     return NPG_OK;
 }
@@ -229,7 +244,7 @@ NPG_API int npg_cg_create(npg_ctx *ctx, int64_t n, npg_cg **out) {
 NPG_API int npg_cg_destroy(npg_cg *ws) {
     if (!ws) return NPG_OK;
     hipStreamSynchronize(ws->ctx->stream);
-    void *ptrs[] = {ws->r, ws->z, ws->p, ws->Ap, ws->Pg, ws->Pp, ws->S, ws->prm, ws->hist, ws->Rg};
+    void *ptrs[] = {ws->r, ws->z, ws->p, ws->Ap, ws->Pg, ws->Pp, ws->S, ws->brk, ws->prm, ws->hist, ws->Rg};
     for (void *p : ptrs)
         if (p) hipFree(p);
     if (ws->h_S) hipHostFree(ws->h_S);
@@ -334,6 +349,7 @@ NPG_API int npg_cg_solve(npg_cg *ws, const npg_csr *A_in, int precond_kind, doub
     d.Qp = ws->halo ? ws->Rg : d.Pp;
     d.nQp = ws->halo ? 1 : d.G1;
     d.S = ws->S;
+    d.brk = ws->brk;
     d.hist = ws->hist;
     d.hist_cap = ws->hist_cap;
     d.prm = ws->prm;

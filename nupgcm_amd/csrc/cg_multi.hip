@@ -47,6 +47,7 @@ struct MDev {
     double *Pg, *Pp;
     int G1, G2;
     MSnap *S;             // [2][smax]
+    int *brk;             // [smax]: cg.hip's brk per column
     double *hist;         // [smax][hist_cap]
     int hist_cap;
     const MParams *prm;
@@ -68,6 +69,7 @@ struct MShared {
     double wsum[kMW * kPartStride];
     double beta[kMCols];
     int done[kMCols];
+    int first[kMCols];
 };
 
 __device__ __forceinline__ double cgm_precond(const MDev &d, int64_t row) {
@@ -145,7 +147,7 @@ template <int C>
 __global__ void __launch_bounds__(kMB) k_cgm_update(MDev d, int slot, int cb) {
     __shared__ MShared sh;
     reduce_partials<kMNS, kMMaxI>(d.Pp, d.G1, d.K, sh.tmp, sh.red);
-    const unsigned active = cgm_active<C>(d, slot, cb);
+    unsigned active = cgm_active<C>(d, slot, cb);
     if (active == 0) return;
     double alpha[C], acc[C];
 #pragma unroll
@@ -154,7 +156,12 @@ __global__ void __launch_bounds__(kMB) k_cgm_update(MDev d, int slot, int cb) {
         alpha[j] = 0.0;
         if ((active >> j) & 1u) {
             const double pAp = sh.red[cb + j];
-            alpha[j] = (pAp > 0.0) ? d.S[slot * d.smax + cb + j].gamma / pAp : 0.0;
+            const bool refuse = !(pAp > 0.0);       // as k_cg_update: no step for this column, a flag for k_cgm_direction
+            if (blockIdx.x == 0 && threadIdx.x == 0) d.brk[cb + j] = refuse ? 1 : 0;
+            if (refuse)
+                active &= ~(1u << j);
+            else
+                alpha[j] = d.S[slot * d.smax + cb + j].gamma / pAp;
         }
     }
     for (int64_t row = blockIdx.x * (int64_t)kMB + threadIdx.x; row < d.n; row += (int64_t)gridDim.x * kMB) {
@@ -187,6 +194,7 @@ __global__ void __launch_bounds__(kMB) k_cgm_direction(MDev d, int src, int dst,
         double beta = 0.0;
         if (s.done == 0) {
             const double g = sh.red[k];
+            const bool refused = !s.first && d.brk[k] != 0;
             double *hist = d.hist + (size_t)k * d.hist_cap;
             if (s.first) {
                 s.rnorm0 = sqrt(g);
@@ -194,9 +202,11 @@ __global__ void __launch_bounds__(kMB) k_cgm_direction(MDev d, int src, int dst,
                 s.eps = d.prm->atol + d.prm->rtol * s.rnorm0;
                 s.first = 0;
                 s.iter = 0;
-                s.done = (g == 0.0) ? 4 : (s.rnorm0 <= s.eps ? 1 : 0);
-                s.pad = 1;   // beta = 0 marker
+                s.done = !isfinite(g) ? 3 : ((g == 0.0) ? 4 : (s.rnorm0 <= s.eps ? 1 : 0));
+                s.pad = 1;   // first step: p = z
                 if (blockIdx.x == 0) hist[0] = s.rnorm0;
+            } else if (refused) {
+                s.done = 3;  // no step was taken: iter, rnorm, gamma and the history stay at the last completed iteration
             } else {
                 s.rnorm = sqrt(g);
                 s.iter += 1;
@@ -206,13 +216,14 @@ __global__ void __launch_bounds__(kMB) k_cgm_direction(MDev d, int src, int dst,
                 s.pad = 0;
             }
             beta = s.pad ? 0.0 : g / prev.gamma;
-            s.gamma = g;
+            if (!refused) s.gamma = g;
             if (blockIdx.x == 0) d.S[dst * d.smax + k] = s;
         } else if (blockIdx.x == 0 && d.S[dst * d.smax + k].done == 0) {
             d.S[dst * d.smax + k] = s;      // a finished column's state reaches the other slot once, then stays
         }
         sh.beta[k] = beta;
         sh.done[k] = s.done;
+        sh.first[k] = s.pad;
     }
     __syncthreads();
     if (d.ks != 1) {        // stacked: column by column
@@ -221,6 +232,10 @@ __global__ void __launch_bounds__(kMB) k_cgm_direction(MDev d, int src, int dst,
             const double beta = sh.beta[k];
             double *__restrict__ p = d.p + (int64_t)k * d.n;
             const double *__restrict__ z = d.z + (int64_t)k * d.n;
+            if (sh.first[k]) {      // first step: the old p is not read (cg.hip)
+                for (int64_t row = blockIdx.x * (int64_t)kMB + threadIdx.x; row < d.n; row += (int64_t)gridDim.x * kMB) p[row] = z[row];
+                continue;
+            }
             for (int64_t row = blockIdx.x * (int64_t)kMB + threadIdx.x; row < d.n; row += (int64_t)gridDim.x * kMB) p[row] = z[row] + beta * p[row];
         }
         return;
@@ -229,7 +244,7 @@ __global__ void __launch_bounds__(kMB) k_cgm_direction(MDev d, int src, int dst,
     int k = (int)((blockIdx.x * (int64_t)kMB + threadIdx.x) % d.K);
     const int dk = (int)(((int64_t)gridDim.x * kMB) % d.K);
     for (int64_t i = blockIdx.x * (int64_t)kMB + threadIdx.x; i < nk; i += (int64_t)gridDim.x * kMB) {
-        if (sh.done[k] == 0) d.p[i] = d.z[i] + sh.beta[k] * d.p[i];
+        if (sh.done[k] == 0) d.p[i] = sh.first[k] ? d.z[i] : d.z[i] + sh.beta[k] * d.p[i];
         k += dk;
         if (k >= d.K) k -= d.K;
     }
@@ -245,6 +260,7 @@ struct npg_cg_multi {
     int ncol_max = 0;
     double *r = nullptr, *z = nullptr, *p = nullptr, *Ap = nullptr, *Pg = nullptr, *Pp = nullptr;
     MSnap *S = nullptr;
+    int *brk = nullptr;
     MParams *prm = nullptr;
     double *hist = nullptr;
     int hist_cap = 0;
@@ -272,12 +288,12 @@ NPG_API int npg_cg_multi_create(npg_ctx *ctx, int64_t n, int ncol_max, npg_cg_mu
     NPG_HIP(hipMalloc((void **)&ws->Pg, pb));
     NPG_HIP(hipMalloc((void **)&ws->Pp, pb));
     NPG_HIP(hipMalloc((void **)&ws->S, 2 * (size_t)ncol_max * sizeof(MSnap)));
+    NPG_HIP(hipMalloc((void **)&ws->brk, (size_t)ncol_max * sizeof(int)));
     NPG_HIP(hipMalloc((void **)&ws->prm, sizeof(MParams)));
     ws->hist_cap = (int)std::min<int64_t>(2 * n + 2, 1 << 22);
     NPG_HIP(hipMalloc((void **)&ws->hist, sizeof(double) * (size_t)ws->hist_cap * (size_t)ncol_max));
     NPG_HIP(hipHostMalloc((void **)&ws->h_S, 2 * (size_t)ncol_max * sizeof(MSnap), hipHostMallocDefault));
     NPG_HIP(hipHostMalloc((void **)&ws->h_prm, sizeof(MParams), hipHostMallocDefault));
-    NPG_HIP(hipMemsetAsync(ws->p, 0, vb, ctx->stream));
     NPG_HIP(hipMemsetAsync(ws->Pg, 0, pb, ctx->stream));
     NPG_HIP(hipMemsetAsync(ws->Pp, 0, pb, ctx->stream));
     NPG_HIP(hipStreamSynchronize(ctx->stream));
@@ -288,7 +304,7 @@ NPG_API int npg_cg_multi_create(npg_ctx *ctx, int64_t n, int ncol_max, npg_cg_mu
 NPG_API int npg_cg_multi_destroy(npg_cg_multi *ws) {
     if (!ws) return NPG_OK;
     hipStreamSynchronize(ws->ctx->stream);
-    void *ptrs[] = {ws->r, ws->z, ws->p, ws->Ap, ws->Pg, ws->Pp, ws->S, ws->prm, ws->hist};
+    void *ptrs[] = {ws->r, ws->z, ws->p, ws->Ap, ws->Pg, ws->Pp, ws->S, ws->brk, ws->prm, ws->hist};
     for (void *p : ptrs)
         if (p) hipFree(p);
     if (ws->h_S) hipHostFree(ws->h_S);
@@ -426,6 +442,7 @@ NPG_API int npg_cg_multi_solve(npg_cg_multi *ws, const npg_csr *A, int precond_k
     d.G1 = std::max(1, std::min<int>(A->ntiles, std::min(kMMaxG, ctx->num_cu)));       // as npg_cg_solve
     d.G2 = (int)std::max<int64_t>(1, std::min<int64_t>((ws->n + kMB - 1) / kMB, d.G1));
     d.S = ws->S;
+    d.brk = ws->brk;
     d.hist = ws->hist;
     d.hist_cap = ws->hist_cap;
     d.prm = ws->prm;
@@ -439,9 +456,6 @@ NPG_API int npg_cg_multi_solve(npg_cg_multi *ws, const npg_csr *A, int precond_k
     MSnap *h_init = ws->h_S + ws->ncol_max;
     for (int k = 0; k < ncol; ++k) h_init[k] = s0;
     NPG_HIP(hipMemcpyAsync(ws->S, h_init, (size_t)ncol * sizeof(MSnap), hipMemcpyHostToDevice, ctx->stream));
-    // a column count other than the last solve's may move the columns of p: what p = z + 0 p reads at the first step must be finite
-    if (ncol != ws->last_ncol && ws->last_ncol != 0)
-        NPG_HIP(hipMemsetAsync(ws->p, 0, (size_t)ws->n * (size_t)ws->ncol_max * sizeof(double), ctx->stream));
     ws->last_ncol = ncol;
     int rc;
     switch (A->lanes) {

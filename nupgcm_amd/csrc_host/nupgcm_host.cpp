@@ -633,7 +633,8 @@ NPG_API int npg_cg_solve(npg_cg *ws, const npg_csr *A, int precond_kind, double 
     const double rnorm0 = rnorm, eps = atol + rtol * rnorm;
     ws->hist.assign(1, rnorm);
     int64_t iter = 0;
-    int status = rnorm == 0.0 ? 4 : (rnorm <= eps ? 1 : 0);
+    // r'z that is NaN or Inf: breakdown, before rnorm <= eps = Inf can call it solved (as the device library)
+    int status = !std::isfinite(gamma) ? 3 : (rnorm == 0.0 ? 4 : (rnorm <= eps ? 1 : 0));
     while (status == 0) {
         spmv_raw(A, p, Ap, 1.0, 0.0);
         const double pAp = dot_fixed(p, Ap, n);

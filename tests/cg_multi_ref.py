@@ -181,6 +181,65 @@ def check_endings(case):
     st, _ = check_special(case, Y, Xf, 1, 1)
     slow = max(st[0]["niter"], st[2]["niter"])
     assert 0 < st[1]["niter"] <= slow - 8, (st[1]["niter"], slow)       # at least two host checks (every 4 iterations) earlier
+    check_reuse_after_nonfinite(case.ctx)
+    check_curvature_column(case.ctx)
+
+
+def check_reuse_after_nonfinite(ctx):
+    """one BatchedCgWorkspace, K = 3 in every call: an ordinary solve, a NaN in column 1's y, an Inf in column 1's x0, the ordinary
+    solve again - with the bits of the first one, and every column of every call with the bits of its single solve"""
+    case = Case(ctx, tridiagonal(257), "tridiagonal n=257 reuse", ncol=3)
+    n, kw = case.n, dict(itmax=200)
+    ws = npg.BatchedCgWorkspace(ctx, n, 3)
+    Y, X0 = case.Y, case.X0
+    first = case.solve_batched(Y, X0, ws=ws, **kw)
+    assert [s["status"] for s in first[1]] == [1, 1, 1]
+    Yn, Xi = Y.copy(), X0.copy()
+    Yn[1, n // 2] = np.nan
+    Xi[1, n // 3] = np.inf
+    for Yp, Xp in ((Yn, X0), (Y, Xi)):
+        X, st, hist = case.solve_batched(Yp, Xp, ws=ws, **kw)
+        assert st[1]["status"] == 3 and st[1]["solved"] == 0 and st[1]["niter"] <= 1 and len(hist[1]) == st[1]["niter"] + 1, st[1]
+        for k in range(3):
+            compare(f"{case.label} poisoned", k, (X[k], st[k], hist[k]), case.solve_single(Yp[k], Xp[k], **kw))
+        assert st[0]["status"] == st[2]["status"] == 1
+    again = case.solve_batched(Y, X0, ws=ws, **kw)
+    print(f"cg_multi {case.label}: status {[s['status'] for s in first[1]]} before, {[s['status'] for s in again[1]]} after a NaN and an Inf")
+    for k in range(3):
+        compare(f"{case.label} again", k, (again[0][k], again[1][k], again[2][k]), (first[0][k], first[1][k], first[2][k]))
+        compare(f"{case.label} again", k, (again[0][k], again[1][k], again[2][k]), case.single(k, **kw))
+
+
+def check_curvature_column(ctx):
+    """tridiagonal(257) with A[128, 128] = -2.5, no preconditioner, itmax = 40.  Column 1 starts at 0 with y = e_128: p'Ap = -2.5 at
+    the first step, status 3 after 0 iterations with x untouched.  Columns 0 and 2 start at 0 with right-hand sides supported on rows
+    0 .. 59 and 200 .. 256: a tridiagonal Krylov space widens by one row per iteration, so within 40 iterations they never meet row
+    128 and are ordinary positive-definite solves.  Every column has the bits of its single solve."""
+    n, at = 257, 128
+    A = sp.lil_matrix(tridiagonal(n))
+    A[at, at] = -2.5
+    case = Case(ctx, A.tocsr(), "indefinite tridiagonal n=257", ncol=3, precond="none")
+    Y, X0 = np.zeros((3, n)), np.zeros((3, n))
+    Y[0, :60], Y[2, 200:] = case.Y[0, :60], case.Y[2, 200:]
+    Y[1, at] = 1.0
+    st, X = check_special(case, Y, X0, 1, 3, itmax=40)
+    assert st[1]["niter"] == 0 and st[1]["solved"] == 0 and not X[1].any()
+    assert st[0]["status"] == st[2]["status"] == 1 and 8 < st[0]["niter"] < 40 and 8 < st[2]["niter"] < 40, st
+    for k in (0, 2):                                        # and they solved their systems
+        assert np.abs(case.As @ X[k] - Y[k]).max() <= 1e-5 * np.abs(Y[k]).max()
+    # a random column meets the negative entry after a few steps: status 3 there, with the single solve's bits beside two ordinary ones
+    Yr, Xr = Y.copy(), X0.copy()
+    Yr[1], Xr[1] = case.Y[1], case.X0[1]
+    st, _ = check_special(case, Yr, Xr, 1, 3, itmax=40)
+    assert 0 < st[1]["niter"] < 40 and st[0]["status"] == st[2]["status"] == 1
+    # the all-zero matrix (stored zeros): p'Ap == 0 at the first step of every column
+    Z = sp.csr_matrix(tridiagonal(n))
+    Z.data[:] = 0.0
+    zero = Case(ctx, Z, "zero matrix n=257", ncol=3, precond="none")
+    X, st, hist = zero.solve_batched(zero.Y, zero.X0, itmax=40)
+    for k in range(3):
+        compare(zero.label, k, (X[k], st[k], hist[k]), zero.single(k, itmax=40))
+        assert st[k]["status"] == 3 and st[k]["niter"] == 0 and st[k]["solved"] == 0 and same_bits(X[k], zero.X0[k])
 
 
 def check_independence(case):
