@@ -540,4 +540,16 @@ __device__ __forceinline__ void spmv_tile(const CsrDev &A, const XF x, int r0, i
     spmv_tile<NT, L, XF, TNNZ, U2>(A, x, td, t, out);
 }
 
+// A workgroup's tiles blockIdx.x, + gridDim.x, ...: f(td) for each.  The next tile's descriptor is loaded before f runs, so that
+// load is in flight during this tile.
+template <class F>
+__device__ __forceinline__ void for_each_tile(const TileDesc *tile_ptr, int ntiles, F f) {
+    TileDesc nd = tile_ptr[blockIdx.x < (unsigned)ntiles ? blockIdx.x : 0];
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const TileDesc td = nd;
+        if (t + (int)gridDim.x < ntiles) nd = tile_ptr[t + gridDim.x];
+        f(td);
+    }
+}
+
 }  // namespace npg

@@ -1,5 +1,5 @@
 """An extended-precision CG and the checks shared by tests/test_cg_steps.py (host library) and tests/test_gpu_cg_steps.py (device):
-npg_cg_solve (csrc/cg.hip: k_cg_init / k_cg_spmv / k_cg_update / k_cg_direction) step by step against something that is not the
+npg_cg_solve (csrc/cg.hip: k_cg_init / k_cg_spmv / k_cg_update<1> / k_cg_direction) step by step against something that is not the
 project's own code.
 
 Reference: `cg_run` in numpy.longdouble (64-bit mantissa), the sparse product written out as np.add.reduceat over the CSR arrays,

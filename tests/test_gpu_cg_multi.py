@@ -1,6 +1,6 @@
-"""The batched CG on the GPU (csrc/cg_multi.hip: k_cgm_init / k_cgm_spmv / k_cgm_update / k_cgm_direction) against
-npg_cg_solve on the same context, at tolerance zero: per column the bits of x, niter, status, solved, rnorm0, rnorm and the history
-(tests/cg_multi_ref.py).
+"""The batched CG on the GPU (csrc/cg.hip: k_cgm_init / k_cgm_spmv for the products, then k_cg_update<C> / k_cg_direction, which the
+single solve runs too with one column) against npg_cg_solve (k_cg_init / k_cg_spmv for the products) on the same
+context, at tolerance zero: per column the bits of x, niter, status, solved, rnorm0, rnorm and the history (tests/cg_multi_ref.py).
 
 Which product-kernel instance each matrix runs (lanes per row from npg_csr_create's rule, asserted below; column blocks from K):
   tridiagonal n = 1, 257, 70 001 and the 7-point Laplacian + I on 20^3 ... 4 lanes

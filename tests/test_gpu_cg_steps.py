@@ -1,4 +1,4 @@
-"""npg_cg_solve on the GPU (csrc/cg.hip: k_cg_init / k_cg_spmv / k_cg_update / k_cg_direction) step by step against the longdouble
+"""npg_cg_solve on the GPU (csrc/cg.hip: k_cg_init / k_cg_spmv / k_cg_update<1> / k_cg_direction) step by step against the longdouble
 CG of tests/cg_steps_ref.py; its endings and the reuse of a workspace that has seen a NaN or an Inf, on both libraries.
 
 Every case solves with atol = rtol = 0 and itmax = k from a random non-zero x0, for k in (1, 2, 3, 4, 5, 8, 9) as far as the

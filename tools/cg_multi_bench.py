@@ -51,8 +51,7 @@ def main():
     n = A.shape[0]
     say(f"{ctx.name()}; {a.workload}: evolution matrix {n} rows, {A.nnz} entries ({A.nnz / n:.1f} per row, {12 * A.nnz / 1e6:.0f} MB of "
         f"(col, val)); P {type(P).__name__}; solver kwargs {kw}; set-up + {a.steps} steps {time.time() - t0:.1f} s; windows of {a.inner} "
-        f"solves, {a.reps} windows per figure, batched and single alternating; NPG_CGM_LAYOUT = "
-        f"{os.environ.get('NPG_CGM_LAYOUT', 'default')}, NPG_CGM_BLOCK = {os.environ.get('NPG_CGM_BLOCK', 'default')}")
+        f"solves, {a.reps} windows per figure, batched and single alternating")
     rng = np.random.default_rng(20261018)
     # the buoyancy's own last system: its right-hand side and the warm start it had (the b of the step before), so a column needs
     # the iterations a tracer needs in a model step
