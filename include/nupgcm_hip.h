@@ -607,6 +607,33 @@ int npg_classes_create(npg_fe *fe, const double *cell_y, const double *cell_z, c
 int npg_classes_compute(npg_classes *K, const npg_vec *x_inv, const npg_vec *b, double N2, npg_vec *table, npg_vec *info);
 int npg_classes_destroy(npg_classes *K);
 
+/* ---- water-mass transformation by mixing: the diffusivity-weighted table of the same handle (csrc/mixing_core.h) ----
+ * For FE fields div(kappa grad B) is a distribution, so the transformation is built from the quantity that is a function in every cell:
+ *    D(B0) = int_{B < B0} kappa_h (d_x B^2 + d_y B^2) + kappa_v (d_z B)^2 dV,      Phi(B0) = dD / dB0 >= 0,      E(B0) = dPhi / dB0
+ * Phi is the down-gradient diffusive buoyancy flux through the surface B = B0, E the diapycnal volume transport towards higher
+ * buoyancy.  Boundary terms (a surface flux) are not part of it.  Binned with the sample rule, the measure, the edges, the mask and the
+ * bin search of the handle; B = N2 z + b', grad B = grad b' + N2 e_z as in npg_classes_compute.  At a sample
+ *    kappa_h = kappa_h[cell][s] (or the scalar),
+ *    kappa_v = kappa_v0 + kappa_c (1 + tanh(-a / N2min)) / 2,   a = alpha (N2c + d_z b'),   kappa_v0 = kappa_v0[cell][s] (or the scalar):
+ * the BACKGROUND diffusivity plus the convection closure of npg_fe_update_kappa_convection evaluated from the sample's own d_z b'.
+ * N2c and alpha are the closure's, separate from the binning N2.  kappa_c = 0: closure off (tanh is not evaluated).
+ * Channels (term = measure x integrand, raw integrals), table [ny + 1][nb + 1][NPG_NMIX]:
+ *    0  1 (the census: bit-identical to channel 0 of npg_classes_compute)      4  kappa_v
+ *    1  kappa_h (d_x B^2 + d_y B^2)                                            5  kappa_h
+ *    2  kappa_v (d_z B)^2                                                      6  |grad B|^2
+ *    3  kappa_v d_z B                                                          7  kappa_v - kappa_v0 (the closure's part)
+ * The same order-independent 64-bit integer sums, scales and info vector as npg_classes_compute; both calls zero the handle's integer
+ * table on the stream at their start, so they may be interleaved on one handle.
+ * npg_classes_set_diffusivity: tables [ncell][ns] (copied) or NULL = the scalar holds everywhere; every value finite and >= 0; a
+ * second call replaces the first.  npg_classes_mixing refuses (NPG_EINVAL + message, before any launch): NULL arguments, no
+ * diffusivities set, a non-finite or negative kappa_c, alpha, N2 or N2c, kappa_c > 0 with N2min not > 0, wrong lengths, vectors of
+ * another context. */
+#define NPG_NMIX 8
+int npg_classes_set_diffusivity(npg_classes *K, const double *kappa_h /* [ncell][ns] or NULL */, double kappa_h_scalar,
+                                const double *kappa_v0 /* [ncell][ns] or NULL */, double kappa_v0_scalar);
+int npg_classes_mixing(npg_classes *K, const npg_vec *b, double N2, double kappa_c, double N2min, double alpha, double N2c,
+                       npg_vec *table, npg_vec *info);   /* table, info: as npg_classes_compute */
+
 /* ---- Lagrangian particles advected through the device-resident flow (new work: offline tracking needs u saved every step) -----
  * n particles on the device: position [n][3], the cell each was last located in, status (0 alive, 1 lost), wind [n][3] and t_lost.
  * npg_particles_advance carries every live particle through nsub classical RK4 steps of dx/dt = u(x, t), h = dt / nsub, in ONE kernel

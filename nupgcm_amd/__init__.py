@@ -21,6 +21,6 @@ from .sampling import (GridDiagnostics, GridIntegrals, GridSamples, Located, Poi
                        sample_slice, sample_to_grid, zonal_mean, zonal_width)
 from .timesteppers import BDF1, BDF2, update_dt, update_t
 from .tracers import PassiveTracers, TracerSpec
-from .watermass import BuoyancyClasses, ClassRecorder, ClassTable
+from .watermass import BuoyancyClasses, ClassRecorder, ClassTable, MixingTable
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -163,6 +163,7 @@ def _declare(L, partial=False):
         "npg_integrals_create": [P, VP, VP, PP], "npg_integrals_destroy": [P], "npg_integrals_compute": [P, P, P, C.c_int, P],
         "npg_classes_create": [P, VP, VP, VP, VP, VP, C.c_int, VP, I64, VP, I64, PP], "npg_classes_destroy": [P],
         "npg_classes_compute": [P, P, P, D, P, P],
+        "npg_classes_set_diffusivity": [P, VP, D, VP, D], "npg_classes_mixing": [P, P, D, D, D, D, D, P, P],
         "npg_particles_create": [P, I64, PP], "npg_particles_destroy": [P], "npg_particles_set": [P, VP, D],
         "npg_particles_set_period": [P, VP], "npg_particles_advance": [P, P, P, P, P, D, D, D, I64],
         "npg_particles_download": [P, VP, VP, VP, VP, VP], "npg_particles_positions": [P, P],
@@ -226,5 +227,6 @@ NPG_FE_FP64, NPG_FE_FP32 = 0, 1
 NPG_SAMPLE_U, NPG_SAMPLE_P, NPG_SAMPLE_B, NPG_SAMPLE_GRAD_B = 1, 2, 3, 4
 NPG_NINT = 15
 NPG_NCLS = 8
+NPG_NMIX = 8
 NPG_CG_MULTI_MAX = 32
 NPG_MAT_M, NPG_MAT_KH, NPG_MAT_KV, NPG_MAT_A, NPG_MAT_B = 1, 2, 3, 4, 5

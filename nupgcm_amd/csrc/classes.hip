@@ -22,7 +22,9 @@
 #include "device_utils.h"
 #include "fe_dev.h"
 #include "classes_core.h"
+#include "mixing_core.h"
 
+static_assert(NPG_NMIX == npg::kNMix, "NPG_NMIX of the header and kNMix of mixing_core.h must agree");
 static_assert(NPG_NCLS == npg::kNCls, "NPG_NCLS of the header and kNCls of classes_core.h must agree");
 static_assert(npg::kClsInfo <= npg::kPartStride, "a partial row holds the channels and the dropped count");
 
@@ -143,6 +145,82 @@ __global__ void __launch_bounds__(kBlock) k_classes_convert(const long long *__r
         out[i] = (double)itab[i] / scale[i & (kNCls - 1)];
 }
 
+// ---- water-mass transformation by mixing (npg_classes_mixing, mixing_core.h): the same two passes over the same grid with the
+// NPG_NMIX diffusivity-weighted channels.  No velocity is gathered; the diffusivities of a sample come from the tables
+// kap_h / kap_v0 [ns][ncell] (coalesced across the lanes of a wave) or, where a table is null, from the scalar.  k_classes_fold,
+// k_classes_convert, the partial rows, the scales and the integer table are the census's (NPG_NMIX == NPG_NCLS). --------------------
+struct MixCoef {
+    const double *kh, *kv0;      // [ns][ncell] or null: the scalar holds everywhere
+    double kh_s, kv0_s;
+    MixClosure cl;
+    __device__ __forceinline__ double h(int s, int64_t c, int64_t ncell) const { return kh ? kh[(size_t)s * ncell + c] : kh_s; }
+    __device__ __forceinline__ double v0(int s, int64_t c, int64_t ncell) const { return kv0 ? kv0[(size_t)s * ncell + c] : kv0_s; }
+};
+
+template <int NB>
+__global__ void __launch_bounds__(kBlock) k_mixing_scan(FeDev d, const double *__restrict__ cy, const double *__restrict__ cz,
+                                                        const uint8_t *__restrict__ mask, ClsRule r, MixCoef k,
+                                                        const double *__restrict__ xb, double N2, double *__restrict__ part) {
+    __shared__ double sh[(kBlock / kWave) * kPartStride];
+    const ClsCells cells{d, cy, cz};
+    double acc[kClsInfo];
+#pragma unroll
+    for (int a = 0; a < kClsInfo; ++a) acc[a] = 0.0;
+    for (int64_t c = blockIdx.x * (int64_t)kBlock + threadIdx.x; c < d.ncell; c += (int64_t)gridDim.x * kBlock) {
+        if (mask && !mask[c]) continue;
+        MixCell<NB> n;
+        mix_cell_load<NB>(cells, xb, c, n);
+        for (int s = 0; s < r.ns; ++s) {
+            double term[kNMix];
+            int64_t band, cls;
+            if (mix_sample<NB, false>(n, r.lam + 4 * s, r.wq[s], N2, k.h(s, c, d.ncell), k.v0(s, c, d.ncell), k.cl, r.y_edges, r.ny,
+                                      r.b_edges, r.nb, &band, &cls, term)) {
+#pragma unroll
+                for (int a = 0; a < kNMix; ++a) acc[a] += fabs(term[a]);
+            } else {
+                acc[kNMix] += 1.0;
+            }
+        }
+    }
+    block_store_partials<kClsInfo, kBlock / kWave>(acc, kClsInfo, sh, part);
+}
+
+template <int NB>
+__global__ void __launch_bounds__(kBlock) k_mixing_bin(FeDev d, const double *__restrict__ cy, const double *__restrict__ cz,
+                                                       const uint8_t *__restrict__ mask, ClsRule r, MixCoef k,
+                                                       const double *__restrict__ xb, double N2, const double *__restrict__ scale,
+                                                       long long *__restrict__ itab) {
+    const ClsCells cells{d, cy, cz};
+    double sc[kNMix];
+#pragma unroll
+    for (int a = 0; a < kNMix; ++a) sc[a] = scale[a];
+    int64_t run[kNMix], cur = -1;
+#pragma unroll
+    for (int a = 0; a < kNMix; ++a) run[a] = 0;
+    for (int64_t c = blockIdx.x * (int64_t)kBlock + threadIdx.x; c < d.ncell; c += (int64_t)gridDim.x * kBlock) {
+        if (mask && !mask[c]) continue;
+        MixCell<NB> n;
+        mix_cell_load<NB>(cells, xb, c, n);
+        for (int s = 0; s < r.ns; ++s) {
+            double term[kNMix];
+            int64_t band, cls;
+            if (!mix_sample<NB, true>(n, r.lam + 4 * s, r.wq[s], N2, k.h(s, c, d.ncell), k.v0(s, c, d.ncell), k.cl, r.y_edges, r.ny,
+                                      r.b_edges, r.nb, &band, &cls, term))
+                continue;
+            const int64_t bin = band * (r.nb + 1) + cls;             // band <= ny, cls <= nb: inside the table
+            if (bin != cur) {
+                if (cur >= 0) classes_flush(itab, cur, run);
+                cur = bin;
+#pragma unroll
+                for (int a = 0; a < kNMix; ++a) run[a] = 0;
+            }
+#pragma unroll
+            for (int a = 0; a < kNMix; ++a) run[a] += class_quantise(term[a], sc[a]);
+        }
+    }
+    if (cur >= 0) classes_flush(itab, cur, run);
+}
+
 }  // namespace npg
 
 using namespace npg;
@@ -157,6 +235,10 @@ struct npg_classes {
     long long *itab = nullptr;   // [(ny + 1)(nb + 1)][NPG_NCLS]
     int ns = 0, nblocks = 0;
     int64_t ny = 0, nb = 0, nbins = 0;
+    // the diffusivities of npg_classes_mixing (npg_classes_set_diffusivity)
+    double *kap = nullptr;       // [2][ns][ncell]: kappa_h then kappa_v0 at the samples (a half is unused where the scalar holds)
+    bool kap_set = false, kh_table = false, kv0_table = false;
+    double kh_s = 0.0, kv0_s = 0.0;
 };
 
 NPG_API int npg_classes_destroy(npg_classes *K) {
@@ -167,6 +249,7 @@ NPG_API int npg_classes_destroy(npg_classes *K) {
     hipFree(K->rule);
     hipFree(K->part);
     hipFree(K->itab);
+    hipFree(K->kap);
     delete K;
     return NPG_OK;
 }
@@ -274,6 +357,80 @@ NPG_API int npg_classes_compute(npg_classes *K, const npg_vec *x_inv, const npg_
         hipLaunchKernelGGL(k_classes_bin<10>, grid, block, 0, st, d, cy, cz, K->mask, r, x_inv->d, b->d, N2, scale, K->itab);
     else
         hipLaunchKernelGGL(k_classes_bin<4>, grid, block, 0, st, d, cy, cz, K->mask, r, x_inv->d, b->d, N2, scale, K->itab);
+    NPG_HIP(hipGetLastError());
+    const unsigned cgrid = (unsigned)std::min<int64_t>((nent + kBlock - 1) / kBlock, 4 * kNumCU);
+    hipLaunchKernelGGL(k_classes_convert, dim3(cgrid), block, 0, st, K->itab, nent, scale, table->d);
+    NPG_HIP(hipGetLastError());
+    return NPG_OK;
+}
+
+NPG_API int npg_classes_set_diffusivity(npg_classes *K, const double *kappa_h, double kappa_h_scalar, const double *kappa_v0,
+                                        double kappa_v0_scalar) {
+    NPG_REQUIRE(K, "npg_classes_set_diffusivity: NULL argument");
+    const int64_t nc = K->fe->d.ncell;
+    const int ns = K->ns;
+    const char *err = kappa_h ? nullptr : check_diffusivity(kappa_h_scalar);
+    NPG_REQUIRE(!err, "npg_classes_set_diffusivity: the scalar kappa_h %s, got %.17g", err, kappa_h_scalar);
+    err = kappa_v0 ? nullptr : check_diffusivity(kappa_v0_scalar);
+    NPG_REQUIRE(!err, "npg_classes_set_diffusivity: the scalar kappa_v0 %s, got %.17g", err, kappa_v0_scalar);
+    const double *src[2] = {kappa_h, kappa_v0};
+    for (int t = 0; t < 2; ++t)
+        for (int64_t i = 0; src[t] && i < nc * ns; ++i)
+            NPG_REQUIRE(!check_diffusivity(src[t][i]), "npg_classes_set_diffusivity: %s[%lld][%d] must be finite and >= 0, got %.17g",
+                        t ? "kappa_v0" : "kappa_h", (long long)(i / ns), (int)(i % ns), src[t][i]);
+    NPG_HIP(hipSetDevice(K->ctx->device));
+    NPG_HIP(hipStreamSynchronize(K->ctx->stream));               // a mixing call in flight still reads the tables it was given
+    if ((kappa_h || kappa_v0) && !K->kap) NPG_HIP(hipMalloc((void **)&K->kap, (size_t)2 * ns * nc * sizeof(double)));
+    std::vector<double> tr;
+    for (int t = 0; t < 2; ++t) {
+        if (!src[t]) continue;
+        tr.resize((size_t)ns * nc);                              // [ncell][ns] -> [ns][ncell]
+        for (int64_t c = 0; c < nc; ++c)
+            for (int s = 0; s < ns; ++s) tr[(size_t)s * nc + c] = src[t][(size_t)c * ns + s];
+        NPG_HIP(hipMemcpy(K->kap + (size_t)t * ns * nc, tr.data(), tr.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    K->kh_table = kappa_h != nullptr, K->kv0_table = kappa_v0 != nullptr;
+    K->kh_s = kappa_h_scalar, K->kv0_s = kappa_v0_scalar;
+    K->kap_set = true;
+    return NPG_OK;
+}
+
+NPG_API int npg_classes_mixing(npg_classes *K, const npg_vec *b, double N2, double kappa_c, double N2min, double alpha, double N2c,
+                               npg_vec *table, npg_vec *info) {
+    NPG_REQUIRE(K && b && table && info, "npg_classes_mixing: NULL argument");
+    NPG_REQUIRE(K->kap_set, "npg_classes_mixing: no diffusivities: call npg_classes_set_diffusivity first");
+    npg_fe *fe = K->fe;
+    NPG_REQUIRE(b->n == fe->n_b, "npg_classes_mixing: the buoyancy vector has %lld entries, expected %lld", (long long)b->n,
+                (long long)fe->n_b);
+    NPG_REQUIRE(table->n >= K->nbins * NPG_NMIX, "npg_classes_mixing: table holds %lld doubles, needs (ny + 1)(nb + 1) NPG_NMIX = %lld",
+                (long long)table->n, (long long)(K->nbins * NPG_NMIX));
+    NPG_REQUIRE(info->n >= 1 + NPG_NMIX, "npg_classes_mixing: info holds %lld doubles, needs 1 + NPG_NMIX = %d", (long long)info->n,
+                1 + NPG_NMIX);
+    NPG_REQUIRE(!check_diffusivity(N2), "npg_classes_mixing: N2 must be finite and >= 0, got %.17g", N2);
+    NPG_REQUIRE(!check_diffusivity(kappa_c), "npg_classes_mixing: kappa_c must be finite and >= 0, got %.17g", kappa_c);
+    NPG_REQUIRE(!check_diffusivity(alpha), "npg_classes_mixing: alpha must be finite and >= 0, got %.17g", alpha);
+    NPG_REQUIRE(!check_diffusivity(N2c), "npg_classes_mixing: N2c must be finite and >= 0, got %.17g", N2c);
+    NPG_REQUIRE(!(kappa_c > 0.0) || N2min > 0.0, "npg_classes_mixing: kappa_c > 0 needs N2min > 0, got %.17g", N2min);
+    NPG_REQUIRE(b->ctx == fe->ctx && table->ctx == fe->ctx && info->ctx == fe->ctx, "npg_classes_mixing: arguments of different contexts");
+    NPG_HIP(hipSetDevice(fe->ctx->device));
+    hipStream_t st = fe->ctx->stream;
+    const FeDev &d = fe->d;
+    const double *lam = K->rule, *wq = lam + (size_t)4 * K->ns, *ye = wq + K->ns, *be = ye + K->ny;
+    double *scale = K->rule + (size_t)5 * K->ns + K->ny + K->nb;
+    const ClsRule r{lam, wq, ye, be, K->ns, K->ny, K->nb};
+    const MixCoef k{K->kh_table ? K->kap : nullptr, K->kv0_table ? K->kap + (size_t)K->ns * d.ncell : nullptr, K->kh_s, K->kv0_s,
+                    MixClosure{kappa_c, N2min, alpha, N2c}};
+    const double *cy = K->cyz, *cz = K->cyz + (size_t)4 * d.ncell;
+    const int64_t nent = K->nbins * kNMix;
+    const dim3 grid((unsigned)K->nblocks), block(kBlock);
+    NPG_HIP(hipMemsetAsync(K->itab, 0, (size_t)nent * sizeof(long long), st));
+    if (d.nb == 10) hipLaunchKernelGGL(k_mixing_scan<10>, grid, block, 0, st, d, cy, cz, K->mask, r, k, b->d, N2, K->part);
+    else hipLaunchKernelGGL(k_mixing_scan<4>, grid, block, 0, st, d, cy, cz, K->mask, r, k, b->d, N2, K->part);
+    NPG_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_classes_fold, dim3(1), block, 0, st, K->part, K->nblocks, info->d, scale);
+    NPG_HIP(hipGetLastError());
+    if (d.nb == 10) hipLaunchKernelGGL(k_mixing_bin<10>, grid, block, 0, st, d, cy, cz, K->mask, r, k, b->d, N2, scale, K->itab);
+    else hipLaunchKernelGGL(k_mixing_bin<4>, grid, block, 0, st, d, cy, cz, K->mask, r, k, b->d, N2, scale, K->itab);
     NPG_HIP(hipGetLastError());
     const unsigned cgrid = (unsigned)std::min<int64_t>((nent + kBlock - 1) / kBlock, 4 * kNumCU);
     hipLaunchKernelGGL(k_classes_convert, dim3(cgrid), block, 0, st, K->itab, nent, scale, table->d);

@@ -1467,6 +1467,10 @@ struct npg_classes {
     std::vector<double> part;        // [nchunk][kClsInfo]
     std::vector<int64_t> itab;       // [(ny + 1)(nb + 1)][NPG_NCLS]
     int64_t nbins = 0;
+    // the diffusivities of npg_classes_mixing (npg_classes_set_diffusivity): [ncell][ns], empty where the scalar holds
+    std::vector<double> kh, kv0;
+    double kh_s = 0.0, kv0_s = 0.0;
+    bool kap_set = false;
 };
 namespace {
 struct HostClsCells {    // the engine's cell tables as class_cell_load reads them ([cell][component])
@@ -1606,6 +1610,117 @@ NPG_API int npg_classes_compute(npg_classes *K, const npg_vec *x_inv, const npg_
     }
 #pragma omp parallel for schedule(static)
     for (int64_t i = 0; i < nent; ++i) table->d[i] = (double)itab[i] / scale[i % NPG_NCLS];
+    return NPG_OK;
+}
+
+// ---- water-mass transformation by mixing (csrc/classes.hip: k_mixing_scan / k_mixing_bin on the host): the per-sample arithmetic is
+// the SAME code (csrc/mixing_core.h); the passes, the chunks, the scales and the integer table are those of npg_classes_compute ------
+#include "../csrc/mixing_core.h"
+static_assert(NPG_NMIX == npg::kNMix, "NPG_NMIX of the header and kNMix of mixing_core.h must agree");
+namespace {
+template <int NB, int PASS>
+inline void mixing_cell(const npg_classes *K, const HostClsCells &t, const double *xb, double N2, const npg::MixClosure &cl, int64_t c,
+                        double *acc, const double *scale, int64_t *itab) {
+    npg::MixCell<NB> n;
+    npg::mix_cell_load<NB>(t, xb, c, n);
+    const int ns = (int)K->wq.size();
+    const int64_t ny = (int64_t)K->y_edges.size(), nb = (int64_t)K->b_edges.size();
+    int64_t run[NPG_NMIX] = {0, 0, 0, 0, 0, 0, 0, 0}, cur = -1;
+    for (int s = 0; s < ns; ++s) {
+        double term[NPG_NMIX];
+        int64_t band = 0, cls = 0;
+        const double kh = K->kh.empty() ? K->kh_s : K->kh[(size_t)c * ns + s], kv0 = K->kv0.empty() ? K->kv0_s : K->kv0[(size_t)c * ns + s];
+        const bool ok = npg::mix_sample<NB, PASS == 2>(n, &K->lam[(size_t)4 * s], K->wq[(size_t)s], N2, kh, kv0, cl, K->y_edges.data(), ny,
+                                                       K->b_edges.data(), nb, &band, &cls, term);
+        if (PASS == 1) {
+            if (ok) for (int k = 0; k < NPG_NMIX; ++k) acc[k] += std::fabs(term[k]);
+            else acc[NPG_NMIX] += 1.0;
+        } else if (ok) {
+            const int64_t bin = band * (nb + 1) + cls;
+            if (bin != cur) {
+                if (cur >= 0) classes_flush(itab, cur, run);
+                cur = bin;
+                for (int k = 0; k < NPG_NMIX; ++k) run[k] = 0;
+            }
+            for (int k = 0; k < NPG_NMIX; ++k) run[k] += npg::class_quantise(term[k], scale[k]);
+        }
+    }
+    if (PASS == 2 && cur >= 0) classes_flush(itab, cur, run);
+}
+}  // namespace
+
+NPG_API int npg_classes_set_diffusivity(npg_classes *K, const double *kappa_h, double kappa_h_scalar, const double *kappa_v0,
+                                        double kappa_v0_scalar) {
+    REQUIRE(K, "npg_classes_set_diffusivity: NULL argument");
+    const int64_t nc = K->fe->ncell;
+    const int ns = (int)K->wq.size();
+    const char *err = kappa_h ? nullptr : npg::check_diffusivity(kappa_h_scalar);
+    REQUIRE(!err, "npg_classes_set_diffusivity: the scalar kappa_h %s, got %.17g", err, kappa_h_scalar);
+    err = kappa_v0 ? nullptr : npg::check_diffusivity(kappa_v0_scalar);
+    REQUIRE(!err, "npg_classes_set_diffusivity: the scalar kappa_v0 %s, got %.17g", err, kappa_v0_scalar);
+    const double *src[2] = {kappa_h, kappa_v0};
+    for (int t = 0; t < 2; ++t)
+        for (int64_t i = 0; src[t] && i < nc * ns; ++i)
+            REQUIRE(!npg::check_diffusivity(src[t][i]), "npg_classes_set_diffusivity: %s[%lld][%d] must be finite and >= 0, got %.17g",
+                    t ? "kappa_v0" : "kappa_h", (long long)(i / ns), (int)(i % ns), src[t][i]);
+    if (kappa_h) K->kh.assign(kappa_h, kappa_h + nc * ns);
+    else K->kh.clear();
+    if (kappa_v0) K->kv0.assign(kappa_v0, kappa_v0 + nc * ns);
+    else K->kv0.clear();
+    K->kh_s = kappa_h_scalar, K->kv0_s = kappa_v0_scalar;
+    K->kap_set = true;
+    return NPG_OK;
+}
+
+NPG_API int npg_classes_mixing(npg_classes *K, const npg_vec *b, double N2, double kappa_c, double N2min, double alpha, double N2c,
+                               npg_vec *table, npg_vec *info) {
+    REQUIRE(K && b && table && info, "npg_classes_mixing: NULL argument");
+    REQUIRE(K->kap_set, "npg_classes_mixing: no diffusivities: call npg_classes_set_diffusivity first");
+    const npg_fe *fe = K->fe;
+    REQUIRE(b->n == fe->n_b, "npg_classes_mixing: the buoyancy vector has %lld entries, expected %lld", (long long)b->n, (long long)fe->n_b);
+    REQUIRE(table->n >= K->nbins * NPG_NMIX, "npg_classes_mixing: table holds %lld doubles, needs (ny + 1)(nb + 1) NPG_NMIX = %lld",
+            (long long)table->n, (long long)(K->nbins * NPG_NMIX));
+    REQUIRE(info->n >= 1 + NPG_NMIX, "npg_classes_mixing: info holds %lld doubles, needs 1 + NPG_NMIX = %d", (long long)info->n, 1 + NPG_NMIX);
+    REQUIRE(!npg::check_diffusivity(N2), "npg_classes_mixing: N2 must be finite and >= 0, got %.17g", N2);
+    REQUIRE(!npg::check_diffusivity(kappa_c), "npg_classes_mixing: kappa_c must be finite and >= 0, got %.17g", kappa_c);
+    REQUIRE(!npg::check_diffusivity(alpha), "npg_classes_mixing: alpha must be finite and >= 0, got %.17g", alpha);
+    REQUIRE(!npg::check_diffusivity(N2c), "npg_classes_mixing: N2c must be finite and >= 0, got %.17g", N2c);
+    REQUIRE(!(kappa_c > 0.0) || N2min > 0.0, "npg_classes_mixing: kappa_c > 0 needs N2min > 0, got %.17g", N2min);
+    REQUIRE(b->ctx == fe->ctx && table->ctx == fe->ctx && info->ctx == fe->ctx, "npg_classes_mixing: arguments of different contexts");
+    const npg::MixClosure cl{kappa_c, N2min, alpha, N2c};
+    const int64_t nc = fe->ncell, nchunk = (nc + npg::kClsChunk - 1) / npg::kClsChunk, nent = K->nbins * NPG_NMIX;
+    const HostClsCells t{fe, K->cy.data(), K->cz.data()};
+    const uint8_t *mask = K->mask.empty() ? nullptr : K->mask.data();
+    const double *xb = b->d;
+    int64_t *itab = K->itab.data();
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < nent; ++i) itab[i] = 0;
+#pragma omp parallel for schedule(static)
+    for (int64_t k = 0; k < nchunk; ++k) {
+        double acc[npg::kClsInfo];
+        for (int a = 0; a < npg::kClsInfo; ++a) acc[a] = 0.0;
+        for (int64_t c = k * npg::kClsChunk; c < std::min(nc, (k + 1) * npg::kClsChunk); ++c) {
+            if (mask && !mask[c]) continue;
+            if (fe->nb == 10) mixing_cell<10, 1>(K, t, xb, N2, cl, c, acc, nullptr, nullptr);
+            else mixing_cell<4, 1>(K, t, xb, N2, cl, c, acc, nullptr, nullptr);
+        }
+        for (int a = 0; a < npg::kClsInfo; ++a) K->part[(size_t)k * npg::kClsInfo + a] = acc[a];
+    }
+    double scale[NPG_NMIX];
+    for (int a = 0; a < npg::kClsInfo; ++a) {
+        double sum = 0.0;
+        for (int64_t k = 0; k < nchunk; ++k) sum += K->part[(size_t)k * npg::kClsInfo + a];
+        if (a < NPG_NMIX) info->d[1 + a] = sum, scale[a] = npg::class_scale(sum);
+        else info->d[0] = sum;
+    }
+#pragma omp parallel for schedule(static)
+    for (int64_t c = 0; c < nc; ++c) {
+        if (mask && !mask[c]) continue;
+        if (fe->nb == 10) mixing_cell<10, 2>(K, t, xb, N2, cl, c, nullptr, scale, itab);
+        else mixing_cell<4, 2>(K, t, xb, N2, cl, c, nullptr, scale, itab);
+    }
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < nent; ++i) table->d[i] = (double)itab[i] / scale[i % NPG_NMIX];
     return NPG_OK;
 }
 

@@ -1,0 +1,102 @@
+"""Water-mass transformation by mixing (BuoyancyClasses.mixing, npg_classes_mixing) on the CPU() architecture -
+libnupgcm_host.so runs the same per-sample arithmetic as the device kernels (csrc/mixing_core.h) - against the numpy restatement of
+tests/mixing_ref.py: every entry with the closure off and on, the tie to the census and to MeshIntegrals, closed forms and the
+closure's limits, scalars against tables, bit-identical repeat and interleaved calls, dropped samples, shapes, refusals, the
+MixingTable arithmetic and the recorder.  No GPU."""
+import pytest
+
+import nupgcm_amd as npg
+from tests import integrals_ref as ir
+from tests import mixing_ref as mr
+from tests import sampling_ref as sr
+
+
+@pytest.fixture(scope="module")
+def arch():
+    return npg.CPU()
+
+
+@pytest.fixture(scope="module")
+def flux_model(arch):
+    """no Dirichlet b"""
+    return sr.bowl_model(arch, "bowl_surface_flux", nsteps=3)
+
+
+@pytest.fixture(scope="module")
+def mix_model(arch):
+    """N2 = 1 / alpha and Dirichlet b: B and b' bin differently, Dirichlet nodes count"""
+    return sr.bowl_model(arch, "bowl_mixing", nsteps=3)
+
+
+@pytest.fixture(scope="module")
+def p1_model(arch):
+    return sr.bowl_model(arch, "bowl_mixing", b_order=1, nsteps=3)
+
+
+def channel(arch):
+    """the small channel basin (periodic seam) with a random state"""
+    model = sr.channel_model(arch)
+    ir.random_state(model)
+    return model
+
+
+def test_both_libraries_export_the_mixing_entry_points():
+    mr.check_exports()
+
+
+def test_table_against_the_restatement_bowl_p2(mix_model):
+    mr.check_table(mix_model, "bowl P2")
+
+
+def test_table_against_the_restatement_bowl_p1(p1_model):
+    mr.check_table(p1_model, "bowl P1")
+
+
+def test_table_against_the_restatement_channel_basin(arch):
+    mr.check_table(channel(arch), "channel basin")
+
+
+def test_table_against_the_restatement_embedded_2d(arch):
+    mr.check_table(ir.bowl2d_model(arch), "bowl 2-D")
+
+
+def test_channel_0_is_the_census(mix_model, p1_model):
+    mr.check_census_tie(mix_model, "bowl P2")
+    mr.check_census_tie(p1_model, "bowl P1")
+
+
+def test_sums_over_the_bins_equal_the_mesh_integrals(arch):
+    mr.check_integrals_tie(mr.linear_kappa_model(arch), "bowl P1, kappa linear in x")
+
+
+def test_closed_forms_and_closure_limits(flux_model):
+    mr.check_closed_forms(flux_model, "bowl P2")
+
+
+def test_scalars_equal_constant_tables(mix_model):
+    mr.check_scalars_equal_tables(mix_model)
+
+
+def test_determinism_and_the_shared_handle(mix_model):
+    mr.check_determinism(mix_model)
+
+
+def test_dropped_samples(flux_model, p1_model):
+    mr.check_dropped(flux_model, "bowl P2")
+    mr.check_dropped(p1_model, "bowl P1")
+
+
+def test_shapes(mix_model):
+    mr.check_shapes(mix_model, "bowl P2")
+
+
+def test_refusals(flux_model):
+    mr.check_refusals(flux_model)
+
+
+def test_mixing_table_arithmetic():
+    mr.check_mixing_table_arithmetic()
+
+
+def test_class_recorder_with_mixing_as_on_plot(arch, tmp_path):
+    mr.check_recorder(lambda: sr.bowl_model(arch, "bowl_surface_flux"), tmp_path)
