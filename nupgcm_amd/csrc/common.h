@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -35,6 +36,24 @@ NPG_SHARED void set_error(const char *fmt, ...);
             return NPG_EINVAL;              \
         }                                   \
     } while (0)
+
+// environment switches: the integer value of `name`, `dflt` where it is not set
+inline int env_int(const char *name, int dflt) {
+    const char *t = getenv(name);
+    return t ? atoi(t) : dflt;
+}
+inline int64_t env_int64(const char *name, int64_t dflt) {
+    const char *t = getenv(name);
+    return t ? atoll(t) : dflt;
+}
+// Is this process traced by rocprofv3 (which marks its child with these variables)?  Under its kernel tracer (ROCm 7.2) a
+// hipGraphLaunch whose batch of AQL packets straddles the end of the 1 MiB queue ring segfaults inside librocprofiler-sdk.so's
+// queue interception (it reads the batch as one contiguous block and runs off the ring's mapping; symbolised backtrace and a
+// library-free reproducer: profiles/r03_rocprofv3_graph_fault.txt, tools/graph_trace_probe.hip; short runs that never wrap the
+// ring profile fine).  Whoever replays captured graphs (gmres.hip, mg.hip, ilu.hip) launches eagerly in a traced process by default.
+inline bool profiler_attached() {
+    return getenv("ROCPROFILER_LIBRARY_CTOR") || getenv("ROCPROF_OUTPUT_PATH") || getenv("ROCP_TOOL_LIBRARIES");
+}
 
 constexpr int kWave = 64;          // CDNA4 wavefront
 constexpr int kBlock = 256;        // 4 waves per workgroup everywhere

@@ -1258,6 +1258,52 @@ using namespace npg;
 // npg_gmres_last_config: entries of the report, in this order (nupgcm_amd/iterative_solvers.py names them)
 constexpr int kCfgLen = 18;
 
+// The environment switches that are read ONCE per process, by the first solve (DESIGN.md 4.2 lists every switch; NPG_GMRES_ONEFOLD,
+// NPG_GMRES_FUSEDROWS and NPG_HALO_OVERLAP_VERBOSE are read at every solve, where they are used)
+struct GmresKnobs {
+    int split = env_int("NPG_GMRES_SPLIT", -1);
+    int basis = env_int("NPG_GMRES_BASIS", 0);
+    int pyth = env_int("NPG_GMRES_PYTH", 1);
+    int lazy2 = env_int("NPG_GMRES_LAZY2", 1);
+    int fast = env_int("NPG_GMRES_FAST", 1);
+    int rev = env_int("NPG_ORTH_REVERSE", 0);
+    int rows_wg = std::max(64, env_int("NPG_GMRES_ROWS_WG", kMaxG));      // (tuning: fewer partial rows for the next prologue to fold)
+    int xg = env_int("NPG_GMRES_XG", 1);
+    int xg_csr = env_int("NPG_GMRES_XG_CSR", -1);
+    int window = env_int("NPG_GMRES_WINDOW", 1);
+    int win_ord = env_int("NPG_WIN_ORD", 0);
+    int win_pre = env_int("NPG_WIN_PRE", 1);
+    // a traced process launches eagerly unless told otherwise (profiler_attached(), common.h: why); =0 forces graph replay there
+    int eager = env_int("NPG_GMRES_EAGER", profiler_attached());
+    int trace = env_int("NPG_GMRES_TRACE", 0);
+    int dist_graph = env_int("NPG_DIST_GRAPH", -1);
+    int overlap = env_int("NPG_HALO_OVERLAP", -1);
+    int overlap_unverified = env_int("NPG_HALO_OVERLAP_UNVERIFIED", 0);
+    int64_t overlap_min_ghosts = env_int64("NPG_HALO_OVERLAP_MIN_GHOSTS", 200000);
+    int reserve_cus = env_int("NPG_HALO_RESERVE_CUS", 4);
+    GmresKnobs() {
+        if (eager && profiler_attached() && !getenv("NPG_GMRES_EAGER"))
+            fprintf(stderr, "[npg] rocprofv3 detected: GMRES restart cycles are launched eagerly instead of replayed from hipGraphs "
+                            "(rocprofiler-sdk faults on graph launches that wrap the AQL ring; NPG_GMRES_EAGER=0 overrides)\n");
+    }
+};
+
+// What one solve launches: the kernels' argument block and everything else the launches of a cycle depend on.  Host only.  The captured
+// cycle graphs bake all of it in, so the whole plan is their cache key - compared with memcmp: gmres_plan zeroes it with memset first.
+struct GmresPlan {
+    GDev d;
+    int lanes;                  // lane instance of the products with the matrix (npg_csr::lanes - npg_csr_set_lanes changes it)
+    int dist;                   // distributed cycle: halo exchanges, partial rows folded to one row and summed over the ranks
+    int kernel_only;            // ... on a transport whose in-cycle calls only launch kernels (the peer windows)
+    int use_graph;              // the cycles replay from the captured graphs (0: every cycle is launched eagerly)
+    int a_nt, a_int;            // tiles of the Arnoldi launches / those of them without ghost columns, which come first
+    int grid;                   // workgroups of a step's one Arnoldi launch
+    int overlap;                // distributed split cycle: the interior tiles run beside the halo exchange, the others behind it
+    int reserve;                // ... CUs that the interior launch leaves free (RCCL)
+    int grid_int, grid_bnd;     // ... workgroups of the interior and of the boundary launch
+    int64_t xg_floats;          // floats of the gather-layout copy GDev::xg (0: the copy is not used)
+};
+
 struct npg_gmres {
     npg_ctx *ctx = nullptr;
     int64_t n = 0;
@@ -1277,7 +1323,7 @@ struct npg_gmres {
     hipGraph_t graph[2] = {nullptr, nullptr};
     hipGraphExec_t exec[2] = {nullptr, nullptr};
     hipEvent_t ev[2] = {nullptr, nullptr};
-    GDev key;
+    GmresPlan key;                // the plan those graphs were captured for
     bool have_graph = false;
     // profile mode: eager launches with HIP events around every Arnoldi (SpMV) kernel
     bool profile = false;
@@ -1308,12 +1354,9 @@ struct npg_gmres {
     bool have_cfg = false;
 };
 
-// fold one set of partial rows into a single row (split and distributed modes) and sum it over the ranks (distributed)
-static int fold_rows(npg_gmres *ws, const double *part, int nrows, int slot, hipStream_t st, bool dist) {
-    double *out = ws->Rg + slot * kKP;
-    if (dist) return fold_allreduce_rows(ws->ctx, part, nrows, out, st);     // peer transport: fold + exchange in ONE kernel
-    hipLaunchKernelGGL(k_reduce_rows, dim3(1), dim3(1024), 0, st, part, nrows, out);
-    return NPG_OK;
+// distributed cycle: fold one set of partial rows into a single row and sum it over the ranks (peer transport: fold + exchange in ONE kernel)
+static int fold_rows(npg_gmres *ws, const double *part, int nrows, int slot, hipStream_t st) {
+    return fold_allreduce_rows(ws->ctx, part, nrows, ws->Rg + slot * kKP, st);
 }
 
 template <int NG, typename BT>
@@ -1413,74 +1456,39 @@ static void launch_residual_L(const GDev &d, hipStream_t st) {
         hipLaunchKernelGGL((k_gmres_residual<L>), dim3(d.G1), dim3(kKB), 0, st, d);
 }
 
-// One restart cycle.  `ws` is needed whenever partial rows are folded (split and/or distributed mode).
+// the lane instance (npg_csr::lanes: 4, 8, 16, otherwise 32) as a type: f(std::integral_constant<int, L>())
+template <class F>
+static auto with_lanes(int lanes, F f) {
+    switch (lanes) {
+        case 4: return f(std::integral_constant<int, 4>());
+        case 8: return f(std::integral_constant<int, 8>());
+        case 16: return f(std::integral_constant<int, 16>());
+        default: return f(std::integral_constant<int, 32>());
+    }
+}
+
+// One restart cycle as the plan has it and, behind it, its outcome for the host into result slot `slot`: the carried state and,
+// with the fused row kernel, the status word of its hand-off.
 template <int L>
-static int launch_cycle_L(const GDev &d, hipStream_t st, hipEvent_t *pev, npg_gmres *ws, bool dist) {
+static int launch_cycle_L(const GmresPlan &p, hipStream_t st, hipEvent_t *pev, npg_gmres *ws, int slot) {
+    const GDev &d = p.d;
+    const bool dist = p.dist;
     int rc = NPG_OK;
-    const bool fold = dist;
-    // distributed split cycle: the tiles that read no ghost column run while the exchange of wt's ghost segment is in
-    // flight on the plan's own stream (NPG_HALO_OVERLAP=0: exchange first, one launch)
-    // default: on with the peer windows (two kernels on one stream around the interior tiles); with RCCL (a second stream and
-    // two events, never run between two physical GPUs) only when asked for - NPG_HALO_OVERLAP=1 / npg_gmres_set_dist_options
-    static const int overlap_env = getenv("NPG_HALO_OVERLAP") ? atoi(getenv("NPG_HALO_OVERLAP")) : -1;
-    const bool kernel_only = dist && comm_is_kernel_only(ws->ctx);
-    int want = !dist ? 0 : ws->halo_overlap >= 0 ? ws->halo_overlap : (overlap_env >= 0 ? overlap_env : (kernel_only || ws->ctx->shm ? 1 : 0));
-    // RCCL's two-stream overlap has never run between two physical GPUs: REFUSED (not merely off by default) unless the caller
-    // states that it knows - NPG_HALO_OVERLAP_UNVERIFIED=1.  (The two-event arrangement itself is sound: rerun with the peer
-    // kernel on a second stream after the epoch fix, profiles/r04_overlap_rerun.txt.)
-    static const int unverified_ok = getenv("NPG_HALO_OVERLAP_UNVERIFIED") ? atoi(getenv("NPG_HALO_OVERLAP_UNVERIFIED")) : 0;
-    if (want && dist && !kernel_only && !ws->ctx->shm && !unverified_ok) {
-        static bool told = false;
-        if (!told && (told = true))
-            fprintf(stderr, "[npg] halo overlap on the RCCL transport was asked for but has never been verified on two physical GPUs: "
-                            "running the exchange before the Arnoldi launch instead (NPG_HALO_OVERLAP_UNVERIFIED=1 overrides)\n");
-        want = 0;
-    }
-    // tile range of the Arnoldi launches: the windowed set where the gather-layout instance has one
-    const int a_nt = d.wt_ptr ? d.nwt : d.ntiles, a_int = d.wt_ptr ? d.nwt_int : d.nt_int;
-    // By DEFAULT the two-launch form is taken only when at least half of the tiles read no ghost column: splitting costs a second
-    // launch with its prologue and a second partly filled round of workgroups, and with hardly any interior tiles there is nothing to
-    // run beside the exchange (rank 4 of 8 of bowl3D h = 0.02 before the interior-first numbering of partition.py: 106 of 2 606 tiles
-    // interior, 81.8 us per iteration split against 73.5 us exchanged first - profiles/r05_dist_cycle.txt) AND the exchange is large
-    // enough for its wire time to exceed what the split costs: the END ranks of the 8-rank partition of that system have 1 000 of
-    // 1 783 tiles interior and 19 k ghost entries (150 KB: ~1 us on an xGMI link) - split, they took 67 us per iteration where the
-    // inner ranks took 59, and the slowest rank sets the pace (section 5 there).  NPG_HALO_OVERLAP_MIN_GHOSTS: 200 000 entries
-    // = 1.6 MB ~ 10 us on one link.  An explicit request (NPG_HALO_OVERLAP=1 / npg_gmres_set_dist_options) splits whenever both
-    // parts are non-empty.
-    const bool asked = dist && (ws->halo_overlap >= 0 || overlap_env >= 0);
-    static const int64_t min_ghosts = getenv("NPG_HALO_OVERLAP_MIN_GHOSTS") ? atoll(getenv("NPG_HALO_OVERLAP_MIN_GHOSTS")) : 200000;
-    const bool big = dist && ws->halo && ws->halo->n_ghost >= min_ghosts;
-    const bool overlap = dist && d.split && want && a_int > 0 && a_int < a_nt && (asked || (2 * a_int >= a_nt && big));
-    const int maxg = ws ? std::min(kMaxG, 3 * ws->ctx->num_cu) : kMaxG;
-    static const int reserve_env = getenv("NPG_HALO_RESERVE_CUS") ? atoi(getenv("NPG_HALO_RESERVE_CUS")) : 4;
-    const int reserve = std::max(0, std::min(reserve_env, maxg / 6));
-    if (dist && getenv("NPG_HALO_OVERLAP_VERBOSE")) {
-        static int last = -1;
-        const int now = (overlap ? 2 : 0) + (d.split ? 1 : 0);
-        if (now != last && (last = now, true))
-            fprintf(stderr, "halo overlap %s: %d interior / %d boundary tiles per Arnoldi step (split %d)\n", overlap ? "on" : "off",
-                    a_int, a_nt - a_int, d.split);
-    }
     // distributed + gather-layout input: the ghosts of wt are also stored as floats behind the owned part of the copy
     float *g32 = (dist && d.xg.p) ? d.xg.p + d.xg.pos(d.n) : nullptr;
     for (int j = 0; j < d.mem; ++j) {
-        if (overlap) {
+        if (p.overlap) {
             if ((rc = halo_exchange_async(ws->halo, d.wt, g32, d.gslot, d.xg.p))) return rc;
             if (pev) hipEventRecord(pev[2 * j], st);
-            // RCCL: the interior launch leaves a few CUs free - its workgroups are persistent (they hold their CU until the last
-            // tile) and RCCL's send/recv kernels on the other stream could otherwise not start before they are all done.  Peer
-            // windows: nothing of ours runs beside it (the neighbours' stores need no CU here): full grid.
-            const int gi = kernel_only ? maxg : maxg - 3 * reserve;
-            launch_arnoldi_split<L>(d, std::min(a_int, gi), j, 0, a_int, st);
+            launch_arnoldi_split<L>(d, p.grid_int, j, 0, p.a_int, st);
             if ((rc = halo_exchange_wait(ws->halo))) return rc;
-            launch_arnoldi_split<L>(d, std::min(a_nt - a_int, maxg), j, a_int, a_nt, st);
+            launch_arnoldi_split<L>(d, p.grid_bnd, j, p.a_int, p.a_nt, st);
             if (pev) hipEventRecord(pev[2 * j + 1], st);
             launch_rows_kernel(d, j, st, false);
         } else {
         if (dist && (rc = halo_exchange_raw(ws->halo, d.wt, g32, d.gslot, d.xg.p))) return rc;
         if (d.split) {
-            launch_arnoldi_split<L>(d, std::min(d.G1, std::max(1, a_nt)), j, 0, a_nt, st, pev ? pev[2 * j] : nullptr,
-                                    pev ? pev[2 * j + 1] : nullptr);
+            launch_arnoldi_split<L>(d, p.grid, j, 0, p.a_nt, st, pev ? pev[2 * j] : nullptr, pev ? pev[2 * j + 1] : nullptr);
             if (d.fusedrows && j < kFusedMaxCols) {
                 launch_rows_fused(d, j, st);     // sums, fold and update in one resident launch
                 continue;
@@ -1489,40 +1497,28 @@ static int launch_cycle_L(const GDev &d, hipStream_t st, hipEvent_t *pev, npg_gm
             if (d.onefold) hipLaunchKernelGGL(k_gmres_fold_first, dim3(1), dim3(kRB), 0, st, d, j, const_cast<double *>(d.Q1));
         } else {
             if (pev) hipEventRecord(pev[2 * j], st);
-            hipLaunchKernelGGL((k_gmres_arnoldi<L, true>), dim3(d.G1), dim3(kKB), 0, st, d, j, 0, d.ntiles);
+            hipLaunchKernelGGL((k_gmres_arnoldi<L, true>), dim3(p.grid), dim3(kKB), 0, st, d, j, 0, d.ntiles);
             if (pev) hipEventRecord(pev[2 * j + 1], st);
         }
         }
-        if (fold && (rc = fold_rows(ws, d.P1, d.GP1, 0, st, dist))) return rc;
+        if (dist && (rc = fold_rows(ws, d.P1, d.GP1, 0, st))) return rc;
         if (d.split)
             launch_rows_kernel(d, j, st, true);
         else
             hipLaunchKernelGGL(k_gmres_orth, dim3(d.G2), dim3(kKB), 0, st, d, j);
-        if (fold && !d.pyth && (rc = fold_rows(ws, d.P2, d.GP2, 1, st, dist))) return rc;
+        if (dist && !d.pyth && (rc = fold_rows(ws, d.P2, d.GP2, 1, st))) return rc;
     }
     hipLaunchKernelGGL(k_gmres_update, dim3(d.G2), dim3(kKB), 0, st, d);
     if (dist && (rc = halo_exchange_raw(ws->halo, d.x))) return rc;
     launch_residual_L<L>(d, st);
-    if (fold && (rc = fold_rows(ws, d.PR, d.G1, 2, st, dist))) return rc;
+    if (dist && (rc = fold_rows(ws, d.PR, d.G1, 2, st))) return rc;
+    NPG_HIP(hipMemcpyAsync(ws->h_C + slot, ws->C, sizeof(Snap), hipMemcpyDeviceToHost, st));
+    if (d.fusedrows) NPG_HIP(hipMemcpyAsync(ws->h_ho + slot, d.ho->status, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     return rc;
 }
 
-static void launch_residual(const GDev &d, int lanes, hipStream_t st) {
-    switch (lanes) {
-        case 4: launch_residual_L<4>(d, st); break;
-        case 8: launch_residual_L<8>(d, st); break;
-        case 16: launch_residual_L<16>(d, st); break;
-        default: launch_residual_L<32>(d, st); break;
-    }
-}
-
-static int launch_cycle(const GDev &d, int lanes, hipStream_t st, hipEvent_t *pev, npg_gmres *ws, bool dist) {
-    switch (lanes) {
-        case 4: return launch_cycle_L<4>(d, st, pev, ws, dist);
-        case 8: return launch_cycle_L<8>(d, st, pev, ws, dist);
-        case 16: return launch_cycle_L<16>(d, st, pev, ws, dist);
-        default: return launch_cycle_L<32>(d, st, pev, ws, dist);
-    }
+static int launch_cycle(const GmresPlan &p, hipStream_t st, hipEvent_t *pev, npg_gmres *ws, int slot) {
+    return with_lanes(p.lanes, [&](auto lanes) { return launch_cycle_L<decltype(lanes)::value>(p, st, pev, ws, slot); });
 }
 
 NPG_API int npg_gmres_create(npg_ctx *ctx, int64_t n, int memory, npg_gmres **out) {
@@ -1612,58 +1608,18 @@ NPG_API int npg_gmres_set_halo(npg_gmres *ws, npg_halo *h) {
     return NPG_OK;
 }
 
-NPG_API int npg_gmres_solve(npg_gmres *ws, const npg_csr *A_in, int precond_kind, double precond_scalar,
-                            const npg_vec *precond_diag, const npg_vec *y, npg_vec *x, double atol, double rtol,
-                            int64_t itmax, double reorth_eta, npg_solve_stats *stats) {
-    NPG_REQUIRE(ws && A_in && y && x, "npg_gmres_solve: NULL argument");
-    ws->have_cfg = false;         // (npg_gmres_last_config reports nothing for a solve that fails)
-    if (A_in->uperm && !A_in->uperm_active) {
-        // npg_csr_block_nodes_dofs: right-hand side, iterate (warm start in, solution out) and a vector preconditioner come and go
-        // in the CALLER's DoF order - three gather passes in, one scatter pass out, then the solve proper on the library's order
-        NPG_REQUIRE(!ws->halo, "npg_gmres_solve: a matrix with an internal renumbering cannot be a distributed row block");
-        NPG_REQUIRE(y->n == A_in->m && x->n == A_in->m, "npg_gmres_solve: vector lengths do not match the matrix");
-        npg_csr *Am = const_cast<npg_csr *>(A_in);
-        npg_vec yi = *y, xi = *x, di;
-        yi.d = Am->uvec[0];
-        xi.d = Am->uvec[1];
-        yi.owns = xi.owns = false;
-        perm_gather(A_in, yi.d, y->d);
-        perm_gather(A_in, xi.d, x->d);
-        const npg_vec *dp = precond_diag;
-        if (precond_kind == NPG_PRECOND_DIAG && precond_diag) {
-            NPG_REQUIRE(precond_diag->n == A_in->m, "npg_gmres_solve: bad preconditioner");
-            di = *precond_diag;
-            di.d = Am->uvec[2];
-            di.owns = false;
-            perm_gather(A_in, di.d, precond_diag->d);
-            dp = &di;
-        }
-        Am->uperm_active = true;
-        const int rc = npg_gmres_solve(ws, A_in, precond_kind, precond_scalar, dp, &yi, &xi, atol, rtol, itmax, reorth_eta, stats);
-        Am->uperm_active = false;
-        if (rc) return rc;
-        perm_scatter(A_in, x->d, xi.d);
-        NPG_HIP(hipStreamSynchronize(ws->ctx->stream));
-        return NPG_OK;
-    }
-    const npg_csr *A = spmv_form(A_in);           // (the record-form companion of a plain matrix, if it has one)
-    if (int rc = check_record_view(A, true, "npg_gmres_solve")) return rc;     // (full node records: the split kernels, forced below)
-    const int64_t nloc = ws->n + ws->n_ghost;     // distributed: vectors the SpMV reads hold [owned | ghosts]
-    NPG_REQUIRE(A->m == ws->n && A->n == nloc && y->n == ws->n && x->n == nloc,
-                "npg_gmres_solve: workspace is for n=%lld (+%lld ghosts) but A is %lldx%lld, y has %lld, x has %lld",
-                (long long)ws->n, (long long)ws->n_ghost, (long long)A->m, (long long)A->n, (long long)y->n,
-                (long long)x->n);
-    NPG_REQUIRE(precond_kind == NPG_PRECOND_NONE || precond_kind == NPG_PRECOND_SCALAR ||
-                    (precond_kind == NPG_PRECOND_DIAG && precond_diag && precond_diag->n == ws->n),
-                "npg_gmres_solve: bad preconditioner");
-    const auto t0 = std::chrono::steady_clock::now();
+// Which kernel instances, on which grids, a solve launches: EVERY selection rule is here.  Fills the plan except for the pointers of
+// the buffers that exist only once the selection says they are needed (gmres_plan_buffers).  `reorth_eta`: as the kernels get it.
+static void gmres_plan(GmresPlan &p, npg_gmres *ws, const npg_csr *A, int precond_kind, double precond_scalar, const npg_vec *precond_diag,
+                       const npg_vec *y, npg_vec *x, double rtol, double reorth_eta, const GmresKnobs &k) {
     npg_ctx *ctx = ws->ctx;
-    hipStream_t st = ctx->stream;
-    npg_gmres *dist = ws->halo ? ws : nullptr;
-    if (dist) reorth_eta = 0.0;     // the on-the-fly second pass would need basis rows of ghost columns
-
-    GDev d;
-    memset(&d, 0, sizeof d);
+    const bool dist = ws->halo != nullptr;
+    const int maxg = std::min(kMaxG, 3 * ctx->num_cu);
+    memset(&p, 0, sizeof p);
+    p.lanes = A->lanes;
+    p.dist = dist;
+    p.kernel_only = dist && comm_is_kernel_only(ctx);
+    GDev &d = p.d;
     d.A = csr_view(A);
     d.tile_ptr = A->tile_ptr;
     d.ntiles = A->ntiles;
@@ -1681,139 +1637,87 @@ NPG_API int npg_gmres_solve(npg_gmres *ws, const npg_csr *A_in, int precond_kind
     d.P1 = ws->P1;
     d.P2 = ws->P2;
     d.PR = ws->PR;
-    d.G1 = std::max(1, std::min<int>(A->ntiles, std::min(kMaxG, 3 * ctx->num_cu)));
-    d.G2 = (int)std::max<int64_t>(1, std::min<int64_t>((ws->n + kNS - 1) / kNS, std::min(kMaxG, 3 * ctx->num_cu)));
-    static const int split_env = getenv("NPG_GMRES_SPLIT") ? atoi(getenv("NPG_GMRES_SPLIT")) : -1;
-    const int split_req = ws->split_mode >= 0 ? ws->split_mode : split_env;
+    d.G1 = std::max(1, std::min<int>(A->ntiles, maxg));
+    d.G2 = (int)std::max<int64_t>(1, std::min<int64_t>((ws->n + kNS - 1) / kNS, maxg));
+    const int split_req = ws->split_mode >= 0 ? ws->split_mode : k.split;
     // measured on MI355X (bowl3D h = 0.1 / 0.08 / 0.05: 23.7 vs 26.0, 27.0 vs 32.0, 50.5 vs 72.6 us per iteration): the
     // split organisation wins from the smallest mesh of interest on; the fused kernels remain for tiny systems
     d.split = split_req >= 0 ? (split_req != 0) : (ws->n >= 8192 ? 1 : 0);
     if (A->pk9) d.split = 1;        // (full node records are served by the split kernels only)
     // distributed: one all-reduce per Arnoldi step (norm of the orthogonalised vector by Pythagoras); NPG_GMRES_PYTH=0
     // or a cancellation flagged by an earlier cycle selects the explicitly reduced norm (a second all-reduce)
-    static const int pyth_env = getenv("NPG_GMRES_PYTH") ? atoi(getenv("NPG_GMRES_PYTH")) : 1;
-    d.pyth = (dist && pyth_env && !ws->explicit_norm) ? 1 : 0;
-    static const int lazy_env = getenv("NPG_GMRES_LAZY2") ? atoi(getenv("NPG_GMRES_LAZY2")) : 1;
-    d.lazy2 = (!dist && lazy_env) ? 1 : 0;
+    d.pyth = (dist && k.pyth && !ws->explicit_norm) ? 1 : 0;
+    d.lazy2 = (!dist && k.lazy2) ? 1 : 0;
     // one GPU, split mode: no second-pass sums until a solve reports that a column needed them (NPG_GMRES_FAST=0: never)
-    static const int fast_env = getenv("NPG_GMRES_FAST") ? atoi(getenv("NPG_GMRES_FAST")) : 1;
     // (only at the default threshold or below, where a second pass is a rare event; a caller asking for eta > 0.1 wants them)
-    // distributed runs take no second pass at all (reorth_eta = 0 above): they always use the fast instance, whose exactly
+    // distributed runs take no second pass at all (reorth_eta = 0 for them): they always use the fast instance, whose exactly
     // summed norm is what the explicit-norm fallback reduces over the ranks
-    d.fast = (d.split && fast_env && reorth_eta <= 0.1 + 1e-12 && (dist || (d.lazy2 && !ws->safe_mode))) ? 1 : 0;
-    d.GR = (int)std::max<int64_t>(1, std::min<int64_t>((ws->n + kRB - 1) / kRB, std::min(kMaxG, 3 * ctx->num_cu)));
-    // distributed: ONE workgroup folds the row kernels' partial rows before they travel (k_peer_fold_allreduce) - a rank's
-    // share of the rows is latency-bound in these kernels anyway, so fewer, longer workgroups cost nothing and the fold
-    // reads 256 rows in one trip instead of 768 in three
-    if (dist) d.GR = std::min(d.GR, 256);
-    static const int rev_env = getenv("NPG_ORTH_REVERSE") ? atoi(getenv("NPG_ORTH_REVERSE")) : 0;
-    d.rev = rev_env;
+    d.fast = (d.split && k.fast && reorth_eta <= 0.1 + 1e-12 && (dist || (d.lazy2 && !ws->safe_mode))) ? 1 : 0;
+    d.rev = k.rev;
     d.ldv = d.split ? (int64_t)((ws->n + 31) / 32) * 32 : 0;
     // Compressed basis (split organisation only): the stored columns in fp32.  They serve the Gram-Schmidt sums and the
     // update x += V y; the vector that enters the next SpMV is formed from wt in fp64, the true residual is recomputed in
     // fp64 at every restart, and all arithmetic is fp64 - what the stored copy limits is the accuracy a SINGLE cycle can
     // add (~1e-7 of the residual it starts from), so it is the default only for tolerances a cycle never exceeds.
-    static const int basis_env = getenv("NPG_GMRES_BASIS") ? atoi(getenv("NPG_GMRES_BASIS")) : 0;
-    const int basis_req = ws->basis_bits ? ws->basis_bits : basis_env;
+    const int basis_req = ws->basis_bits ? ws->basis_bits : k.basis;
     const bool basis32 = d.split && (basis_req == 32 || (basis_req == 0 && rtol >= 1e-7));
     d.Vf = basis32 ? reinterpret_cast<float *>(ws->Vi) : nullptr;
-    if (basis32) {          // the row kernels take two rows per thread there
-        // (NPG_GMRES_ROWS_WG: tuning - fewer workgroups = fewer partial rows for the next kernel's prologue to fold)
-        static const int rows_wg = getenv("NPG_GMRES_ROWS_WG") ? std::max(64, atoi(getenv("NPG_GMRES_ROWS_WG"))) : kMaxG;
-        d.GR = (int)std::max<int64_t>(1, std::min<int64_t>((ws->n + 2 * kRB - 1) / (2 * kRB), std::min(dist ? 256 : std::min(kMaxG, rows_wg), 3 * ctx->num_cu)));
-        d.GP1 = d.GR;
-        d.GP2 = d.GR;
-    }
+    // grid of the row kernels.  distributed: ONE workgroup folds their partial rows before they travel (k_peer_fold_allreduce) -
+    // a rank's share of the rows is latency-bound in these kernels anyway, so fewer, longer workgroups cost nothing and the fold
+    // reads 256 rows in one trip instead of 768 in three.  fp32-stored basis: they take two rows per thread (and NPG_GMRES_ROWS_WG).
+    const int64_t rows_per_wg = basis32 ? 2 * kRB : kRB;
+    const int rows_cap = std::min(dist ? 256 : (basis32 ? std::min(kMaxG, k.rows_wg) : kMaxG), 3 * ctx->num_cu);
+    d.GR = (int)std::max<int64_t>(1, std::min<int64_t>((ws->n + rows_per_wg - 1) / rows_per_wg, rows_cap));
     d.GP1 = d.split ? d.GR : d.G1;
     d.GP2 = d.split ? d.GR : d.G2;
     // Gather-layout fp32 copy of the SpMV input (one GPU, fp32-stored basis, fast mode, node-blocked matrix): the Arnoldi kernel
     // is bound by its gather instructions and a node's three components then come with ONE 16-byte gather.
     // The rounding is the one the stored basis column has anyway.  NPG_GMRES_XG=0 turns it off.
-    static const int xg_env = getenv("NPG_GMRES_XG") ? atoi(getenv("NPG_GMRES_XG")) : 1;
-    d.xg = GatherMap{nullptr, 0, 0, 0, 0};
     // plain-CSR matrices (function-valued viscosity: the full-stress form has no node records): the copy is then the vector in
     // fp32, every gather 4 bytes instead of 8 - measured on the channel basin at 4.1 M unknowns: Arnoldi kernel 1 019 against
     // 1 075 us; from 100 000 rows on (below that the solve is latency-bound and the extra stores buy nothing);
     // NPG_GMRES_XG_CSR=0 / 1 forces it off / on at any size
-    static const int xg_csr_env = getenv("NPG_GMRES_XG_CSR") ? atoi(getenv("NPG_GMRES_XG_CSR")) : -1;
-    const bool xg_csr = xg_csr_env >= 0 ? xg_csr_env != 0 : ws->n >= 100000;
-    if ((ws->gather32 >= 0 ? ws->gather32 : xg_env) && basis32 && d.fast && (A->nnode() > 0 || xg_csr) && (dist ? A->n == A->m + ws->n_ghost : A->n == A->m)) {
+    const bool xg_csr = k.xg_csr >= 0 ? k.xg_csr != 0 : ws->n >= 100000;
+    if ((ws->gather32 >= 0 ? ws->gather32 : k.xg) && basis32 && d.fast && (A->nnode() > 0 || xg_csr) && (dist ? A->n == A->m + ws->n_ghost : A->n == A->m)) {
         // node slots: the owned block nodes and, behind them, the ghost nodes the windowed tiles use as record columns
         // (NOT gather32_floats(A): that is the stand-alone product's question and answers 0 for a rank's row block - round 5's first
         //  version sized the copy without the ghost slots through it and the unpack wrote 4 ngn floats past the end)
         const int64_t nslots = A->wtile_ptr ? gather32_nodes(A) : A->nnode();
-        const int64_t nbr = A->block_rows(), need = 4 * nslots + (A->n - nbr) + 8;
-        if (ws->xg_len < need) {
-            if (ws->xg) NPG_HIP(hipFree(ws->xg));
-            ws->xg = nullptr;
-            NPG_HIP(hipMalloc((void **)&ws->xg, (size_t)need * sizeof(float)));
-            ws->xg_len = need;
-            ws->xg_key[0] = -1;
-        }
-        if (ws->xg_key[0] != A->nfull || ws->xg_key[1] != A->nsurf || ws->xg_key[2] != (int)A->n) {
-            NPG_HIP(hipMemsetAsync(ws->xg, 0, (size_t)ws->xg_len * sizeof(float), st));      // the pads must read as zero
-            ws->xg_key[0] = A->nfull;
-            ws->xg_key[1] = A->nsurf;
-            ws->xg_key[2] = (int)A->n;
-        }
-        d.xg = GatherMap{ws->xg, 3 * A->nfull, A->nfull, (int)nbr, (int)(4 * nslots - nbr)};
+        const int64_t nbr = A->block_rows();
+        p.xg_floats = 4 * nslots + (A->n - nbr) + 8;
+        d.xg = GatherMap{nullptr, 3 * A->nfull, A->nfull, (int)nbr, (int)(4 * nslots - nbr)};
         d.gslot = A->wtile_ptr ? A->gslot : nullptr;
         // windowed tile set of the block rows (spmv_window.h; NPG_GMRES_WINDOW=0: the ordinary tiles)
-        static const int win_env = getenv("NPG_GMRES_WINDOW") ? atoi(getenv("NPG_GMRES_WINDOW")) : 1;
-        if (win_env && ws->gather32 != 2 && d.split && A->wtile_ptr && !A->pk9 && nbr > 0) {
+        if (k.window && ws->gather32 != 2 && d.split && A->wtile_ptr && !A->pk9 && nbr > 0) {
             d.wt_ptr = A->wtile_ptr;
             d.W = win_view(A);
             d.nwt = A->nwtiles;
             d.nwt_int = A->nwtiles_interior;
             d.wl = A->wlanes;
-            static const int ord_env = getenv("NPG_WIN_ORD") ? atoi(getenv("NPG_WIN_ORD")) : 0;
-            static const int pre_env = getenv("NPG_WIN_PRE") ? atoi(getenv("NPG_WIN_PRE")) : 1;
-            d.word = ord_env || (A->nwrow_tiles == 0 && A->m > A->block_rows());
-            d.wpre = pre_env;
+            d.word = k.win_ord || (A->nwrow_tiles == 0 && A->m > A->block_rows());
+            d.wpre = k.win_pre;
         }
     }
     // One GPU, split organisation, fast kernels: the first-pass sums are folded once and the basis column is formed by the dots
     // kernel (NPG_GMRES_ONEFOLD=0: every orthogonalisation workgroup folds them, the Arnoldi epilogue stores the column).  Same
     // sums in the same order, same expression for the column: the switch changes no bit of any result.
-    const char *onefold_env = getenv("NPG_GMRES_ONEFOLD");
-    d.onefold = (!dist && d.split && d.fast && !(onefold_env && atoi(onefold_env) == 0)) ? 1 : 0;
+    d.onefold = (!dist && d.split && d.fast && env_int("NPG_GMRES_ONEFOLD", 1) != 0) ? 1 : 0;
     d.vdots = (d.onefold && d.Vf) ? 1 : 0;
     // ... and, with the fp32-stored basis, the three row launches of a step as one resident launch (k_gmres_rows_fused;
     // NPG_GMRES_FUSEDROWS=0: the separate launches).  It is the onefold arrangement in one kernel, so it selects that arrangement
     // for the cycle's other steps too; NPG_GMRES_ONEFOLD=0 chooses among the separate launches, i.e. with NPG_GMRES_FUSEDROWS=0 or
     // where the fused kernel does not apply.  Only on a grid that is resident as a whole: the hand-off waits for every workgroup.
-    const char *fusedrows_env = getenv("NPG_GMRES_FUSEDROWS");
-    if (!dist && d.split && d.fast && d.Vf && !d.rev && !ws->fused_off && !(fusedrows_env && atoi(fusedrows_env) == 0)) {
+    if (!dist && d.split && d.fast && d.Vf && !d.rev && !ws->fused_off && env_int("NPG_GMRES_FUSEDROWS", 1) != 0) {
         if (ws->fused_blocks < 0) ws->fused_blocks = rows_fused_blocks_per_cu();
-        if (d.GR <= ctx->num_cu * ws->fused_blocks) {
-            if (!ws->ho) {
-                NPG_HIP(hipMalloc((void **)&ws->ho, sizeof(RowsHandOff)));
-                NPG_HIP(hipMemsetAsync(ws->ho, 0, sizeof(RowsHandOff), st));
-                NPG_HIP(hipHostMalloc((void **)&ws->h_ho, 2 * sizeof(unsigned long long), hipHostMallocDefault));
-                ws->h_ho[0] = ws->h_ho[1] = 0;
-            }
-            d.fusedrows = 1;
-            d.ho = ws->ho;
-            d.onefold = d.vdots = 1;
-        }
+        if (d.GR <= ctx->num_cu * ws->fused_blocks) d.fusedrows = d.onefold = d.vdots = 1;
     }
-    if (dist) {
-        d.Q1 = ws->Rg;
-        d.Q2 = ws->Rg + kKP;
-        d.QR = ws->Rg + 2 * kKP;
-        d.nQ1 = d.nQ2 = d.nQR = 1;
-    } else {
-        d.Q1 = d.P1;
-        d.Q2 = d.P2;
-        d.QR = d.PR;
-        d.nQ1 = d.GP1;
-        d.nQ2 = d.GP2;
-        d.nQR = d.G1;
-        if (d.onefold) {            // (slot 0 of the all-reduced rows is free on one GPU)
-            d.Q1 = ws->Rg;
-            d.nQ1 = 1;
-        }
-    }
+    const bool one1 = dist || d.onefold;        // (slot 0 of the all-reduced rows is free on one GPU)
+    d.Q1 = one1 ? ws->Rg : d.P1;
+    d.Q2 = dist ? ws->Rg + kKP : d.P2;
+    d.QR = dist ? ws->Rg + 2 * kKP : d.PR;
+    d.nQ1 = one1 ? 1 : d.GP1;
+    d.nQ2 = dist ? 1 : d.GP2;
+    d.nQR = dist ? 1 : d.G1;
     d.C = ws->C;
     d.T = ws->T;
     d.c = ws->c;
@@ -1826,218 +1730,231 @@ NPG_API int npg_gmres_solve(npg_gmres *ws, const npg_csr *A_in, int precond_kind
     d.hist_cap = ws->hist_cap;
     d.prm = ws->prm;
 
-    if (itmax <= 0) itmax = 2 * ws->n;
-    ws->h_prm->atol = atol;
-    ws->h_prm->rtol = rtol;
-    ws->h_prm->eta2 = reorth_eta <= 0.0 ? -1.0 : reorth_eta * reorth_eta;
-    ws->h_prm->btol = std::pow(2.220446049250313e-16, 0.75);
-    ws->h_prm->itmax = itmax;
-    NPG_HIP(hipMemcpyAsync(ws->prm, ws->h_prm, sizeof(GParams), hipMemcpyHostToDevice, st));
-    Snap c0{};
-    c0.first = 1;
-    ws->h_C[0] = c0;
-    NPG_HIP(hipMemcpyAsync(ws->C, ws->h_C, sizeof(Snap), hipMemcpyHostToDevice, st));
-    NPG_HIP(hipStreamSynchronize(st));      // h_C[0] is reused below as a result slot
-
-    // Under rocprofv3's kernel tracer (ROCm 7.2) a hipGraphLaunch whose batch of AQL packets straddles the end of the 1 MiB
-    // queue ring segfaults inside librocprofiler-sdk.so's queue interception (it reads the batch as one contiguous block and
-    // runs off the ring's mapping; symbolised backtrace and a library-free reproducer: profiles/r03_rocprofv3_graph_fault.txt,
-    // tools/graph_trace_probe.hip).  A traced process therefore launches eagerly unless told otherwise (NPG_GMRES_EAGER=0
-    // forces graph replay; short runs that never wrap the ring profile fine).  rocprofv3 marks its child with these variables.
-    static const int traced = getenv("ROCPROFILER_LIBRARY_CTOR") || getenv("ROCPROF_OUTPUT_PATH") || getenv("ROCP_TOOL_LIBRARIES");
-    static const int eager = getenv("NPG_GMRES_EAGER") ? atoi(getenv("NPG_GMRES_EAGER")) : traced;
-    static bool said = false;
-    if (eager && traced && !getenv("NPG_GMRES_EAGER") && !said && (said = true))
-        fprintf(stderr, "[npg] rocprofv3 detected: GMRES restart cycles are launched eagerly instead of replayed from hipGraphs "
-                        "(rocprofiler-sdk faults on graph launches that wrap the AQL ring; NPG_GMRES_EAGER=0 overrides)\n");
-    static const int trace = getenv("NPG_GMRES_TRACE") ? atoi(getenv("NPG_GMRES_TRACE")) : 0;
-
     // Distributed cycles.  On the peer transport (comm.hip) every communication step is a kernel on a HIP stream, so the
     // cycle replays from one hipGraph exactly like the single-GPU cycle - the default there (NPG_DIST_GRAPH=0 turns it off).
     // With RCCL in the cycle the calls can be captured too (the exchange stream forks from and joins the captured stream
     // through the plan's events), but a captured collective costs more than an eager one and has only
     // run on a one-rank communicator: opt-in (NPG_DIST_GRAPH=1 / npg_gmres_set_dist_options).  The host-driven shm
     // rehearsal transport cannot be captured.
-    static const int dist_graph_env = getenv("NPG_DIST_GRAPH") ? atoi(getenv("NPG_DIST_GRAPH")) : -1;
-    const bool kernel_only = dist && comm_is_kernel_only(ws->ctx);
-    const bool graph_dist = dist && !ws->ctx->shm &&
-                            (kernel_only ? (dist_graph_env != 0 && ws->dist_graph != 0) : ((ws->dist_graph > 0 || dist_graph_env > 0) && ws->ctx->comm));
-    // (re)capture the per-cycle graphs when any baked-in argument changed
-    auto capture_graphs = [&]() -> int {
-        for (int k = 0; k < 2; ++k) {
-            if (ws->exec[k]) hipGraphExecDestroy(ws->exec[k]);
-            if (ws->graph[k]) hipGraphDestroy(ws->graph[k]);
-            ws->exec[k] = nullptr;
-            ws->graph[k] = nullptr;
-            ws->have_graph = false;
-            NPG_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            int rcg = launch_cycle(d, A->lanes, st, nullptr, ws, dist != nullptr);
-            if (rcg) {
-                hipGraph_t broken = nullptr;
-                hipStreamEndCapture(st, &broken);
-                if (broken) hipGraphDestroy(broken);
-                return rcg;
-            }
-            NPG_HIP(hipMemcpyAsync(ws->h_C + k, ws->C, sizeof(Snap), hipMemcpyDeviceToHost, st));
-            if (d.fusedrows) NPG_HIP(hipMemcpyAsync(ws->h_ho + k, d.ho->status, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-            NPG_HIP(hipStreamEndCapture(st, &ws->graph[k]));
-            NPG_HIP(hipGraphInstantiate(&ws->exec[k], ws->graph[k], nullptr, nullptr, 0));
-        }
-        memcpy(&ws->key, &d, sizeof d);
-        ws->have_graph = true;
-        return NPG_OK;
-    };
-    const bool use_graph = (!dist || graph_dist) && !eager && !ws->profile;
-    if (use_graph && (!ws->have_graph || memcmp(&ws->key, &d, sizeof(GDev)) != 0)) {
-        int rcg = capture_graphs();
-        if (rcg) return rcg;
-    }
+    const bool graph_dist = dist && !ctx->shm &&
+                            (p.kernel_only ? (k.dist_graph != 0 && ws->dist_graph != 0) : ((ws->dist_graph > 0 || k.dist_graph > 0) && ctx->comm));
+    p.use_graph = (!dist || graph_dist) && !k.eager && !ws->profile;
 
-    // first true residual, then cycles until the carried state says done
-    if (dist) {
-        int rcd = halo_exchange_raw(ws->halo, d.x);
-        if (rcd) return rcd;
+    // tile range of the Arnoldi launches: the windowed set where the gather-layout instance has one
+    p.a_nt = d.wt_ptr ? d.nwt : d.ntiles;
+    p.a_int = d.wt_ptr ? d.nwt_int : d.nt_int;
+    p.grid = d.split ? std::min(d.G1, std::max(1, p.a_nt)) : d.G1;
+    if (!dist) return;
+    // distributed split cycle: the tiles that read no ghost column run while the exchange of wt's ghost segment is in
+    // flight on the plan's own stream (NPG_HALO_OVERLAP=0: exchange first, one launch)
+    // default: on with the peer windows (two kernels on one stream around the interior tiles); with RCCL (a second stream and
+    // two events, never run between two physical GPUs) only when asked for - NPG_HALO_OVERLAP=1 / npg_gmres_set_dist_options
+    int want = ws->halo_overlap >= 0 ? ws->halo_overlap : (k.overlap >= 0 ? k.overlap : (p.kernel_only || ctx->shm ? 1 : 0));
+    // RCCL's two-stream overlap has never run between two physical GPUs: REFUSED (not merely off by default) unless the caller
+    // states that it knows - NPG_HALO_OVERLAP_UNVERIFIED=1.  (The two-event arrangement itself is sound: rerun with the peer
+    // kernel on a second stream after the epoch fix, profiles/r04_overlap_rerun.txt.)
+    if (want && !p.kernel_only && !ctx->shm && !k.overlap_unverified) {
+        static bool told = false;
+        if (!told && (told = true))
+            fprintf(stderr, "[npg] halo overlap on the RCCL transport was asked for but has never been verified on two physical GPUs: "
+                            "running the exchange before the Arnoldi launch instead (NPG_HALO_OVERLAP_UNVERIFIED=1 overrides)\n");
+        want = 0;
     }
-    launch_residual(d, A->lanes, st);
+    // By DEFAULT the two-launch form is taken only when at least half of the tiles read no ghost column: splitting costs a second
+    // launch with its prologue and a second partly filled round of workgroups, and with hardly any interior tiles there is nothing to
+    // run beside the exchange (rank 4 of 8 of bowl3D h = 0.02 before the interior-first numbering of partition.py: 106 of 2 606 tiles
+    // interior, 81.8 us per iteration split against 73.5 us exchanged first - profiles/r05_dist_cycle.txt) AND the exchange is large
+    // enough for its wire time to exceed what the split costs: the END ranks of the 8-rank partition of that system have 1 000 of
+    // 1 783 tiles interior and 19 k ghost entries (150 KB: ~1 us on an xGMI link) - split, they took 67 us per iteration where the
+    // inner ranks took 59, and the slowest rank sets the pace (section 5 there).  NPG_HALO_OVERLAP_MIN_GHOSTS: 200 000 entries
+    // = 1.6 MB ~ 10 us on one link.  An explicit request (NPG_HALO_OVERLAP=1 / npg_gmres_set_dist_options) splits whenever both
+    // parts are non-empty.
+    const bool asked = ws->halo_overlap >= 0 || k.overlap >= 0;
+    const bool big = ws->halo->n_ghost >= k.overlap_min_ghosts;
+    p.overlap = d.split && want && p.a_int > 0 && p.a_int < p.a_nt && (asked || (2 * p.a_int >= p.a_nt && big));
+    if (p.overlap) {
+        // RCCL: the interior launch leaves a few CUs free - its workgroups are persistent (they hold their CU until the last
+        // tile) and RCCL's send/recv kernels on the other stream could otherwise not start before they are all done.  Peer
+        // windows: nothing of ours runs beside it (the neighbours' stores need no CU here): full grid.
+        p.reserve = p.kernel_only ? 0 : std::max(0, std::min(k.reserve_cus, maxg / 6));
+        p.grid_int = std::min(p.a_int, maxg - 3 * p.reserve);
+        p.grid_bnd = std::min(p.a_nt - p.a_int, maxg);
+    }
+    if (getenv("NPG_HALO_OVERLAP_VERBOSE")) {
+        static int last = -1;
+        const int now = (p.overlap ? 2 : 0) + (d.split ? 1 : 0);
+        if (now != last && (last = now, true))
+            fprintf(stderr, "halo overlap %s: %d interior / %d boundary tiles per Arnoldi step (split %d)\n", p.overlap ? "on" : "off",
+                    p.a_int, p.a_nt - p.a_int, d.split);
+    }
+}
+
+// The buffers that only some plans need, made (or grown) on first use, and their pointers entered into the plan: the gather-layout
+// copy of the SpMV input with its pads zeroed, the hand-off state of the fused row kernel.
+static int gmres_plan_buffers(GmresPlan &p, npg_gmres *ws, const npg_csr *A, hipStream_t st) {
+    if (p.xg_floats) {
+        if (ws->xg_len < p.xg_floats) {
+            if (ws->xg) NPG_HIP(hipFree(ws->xg));
+            ws->xg = nullptr;
+            NPG_HIP(hipMalloc((void **)&ws->xg, (size_t)p.xg_floats * sizeof(float)));
+            ws->xg_len = p.xg_floats;
+            ws->xg_key[0] = -1;
+        }
+        if (ws->xg_key[0] != A->nfull || ws->xg_key[1] != A->nsurf || ws->xg_key[2] != (int)A->n) {
+            NPG_HIP(hipMemsetAsync(ws->xg, 0, (size_t)ws->xg_len * sizeof(float), st));      // the pads must read as zero
+            ws->xg_key[0] = A->nfull;
+            ws->xg_key[1] = A->nsurf;
+            ws->xg_key[2] = (int)A->n;
+        }
+        p.d.xg.p = ws->xg;
+    }
+    if (p.d.fusedrows) {
+        if (!ws->ho) {
+            NPG_HIP(hipMalloc((void **)&ws->ho, sizeof(RowsHandOff)));
+            NPG_HIP(hipMemsetAsync(ws->ho, 0, sizeof(RowsHandOff), st));
+            NPG_HIP(hipHostMalloc((void **)&ws->h_ho, 2 * sizeof(unsigned long long), hipHostMallocDefault));
+            ws->h_ho[0] = ws->h_ho[1] = 0;
+        }
+        p.d.ho = ws->ho;
+    }
+    return NPG_OK;
+}
+
+// (re)capture the per-cycle graphs when anything they bake in - the plan - has changed
+static int ensure_graphs(npg_gmres *ws, const GmresPlan &p, hipStream_t st) {
+    if (!p.use_graph || (ws->have_graph && memcmp(&ws->key, &p, sizeof p) == 0)) return NPG_OK;
+    for (int k = 0; k < 2; ++k) {
+        if (ws->exec[k]) hipGraphExecDestroy(ws->exec[k]);
+        if (ws->graph[k]) hipGraphDestroy(ws->graph[k]);
+        ws->exec[k] = nullptr;
+        ws->graph[k] = nullptr;
+        ws->have_graph = false;
+        NPG_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+        int rc = launch_cycle(p, st, nullptr, ws, k);
+        if (rc) {
+            hipGraph_t broken = nullptr;
+            hipStreamEndCapture(st, &broken);
+            if (broken) hipGraphDestroy(broken);
+            return rc;
+        }
+        NPG_HIP(hipStreamEndCapture(st, &ws->graph[k]));
+        NPG_HIP(hipGraphInstantiate(&ws->exec[k], ws->graph[k], nullptr, nullptr, 0));
+    }
+    memcpy(&ws->key, &p, sizeof p);
+    ws->have_graph = true;
+    return NPG_OK;
+}
+
+// the true residual that starts a cycle, of the iterate as it stands: wt = P (b - A x) and its squared norm
+static int launch_first_residual(npg_gmres *ws, const GmresPlan &p, hipStream_t st) {
+    if (int rc = p.dist ? halo_exchange_raw(ws->halo, p.d.x) : NPG_OK) return rc;
+    with_lanes(p.lanes, [&](auto lanes) { launch_residual_L<decltype(lanes)::value>(p.d, st); });
     NPG_HIP(hipGetLastError());
-    if (dist) {
-        int rcd = fold_rows(ws, d.PR, d.G1, 2, st, true);
-        if (rcd) return rcd;
+    return p.dist ? fold_rows(ws, p.d.PR, p.d.G1, 2, st) : NPG_OK;
+}
+
+// done == 5, distributed: ||w||^2 - ||h||^2 met cancellation and the device interrupted the pass before that column.  Carry on
+// from the current iterate with explicitly reduced norms (a second all-reduce per step), for this and all later solves of the
+// workspace.  `last` = the state read from result slot `slot`; returns with the stream idle and the slot a result slot again.
+static int restart_with_explicit_norms(npg_gmres *ws, GmresPlan &p, Snap &last, int slot, hipStream_t st) {
+    NPG_HIP(hipStreamSynchronize(st));           // (pipelined: the cycle enqueued ahead has exited at once)
+    p.d.pyth = 0;
+    ws->explicit_norm = true;
+    // the captured cycles have pyth = 1 baked into their kernel arguments: replaying them would flag the same cancellation for
+    // ever - capture the explicit-norm cycle
+    if (int rc = ensure_graphs(ws, p, st)) return rc;
+    last.done = 0;
+    last.inner = 0;
+    ws->h_C[slot] = last;
+    NPG_HIP(hipMemcpyAsync(ws->C, ws->h_C + slot, sizeof(Snap), hipMemcpyHostToDevice, st));
+    if (int rc = launch_first_residual(ws, p, st)) return rc;
+    NPG_HIP(hipStreamSynchronize(st));
+    return NPG_OK;
+}
+
+// A hand-off of k_gmres_rows_fused that ran out of time has set the status word: that launch and every later one skipped the
+// update, so the iterate is not to be trusted.  Report it, re-zero the hand-off state and keep to the separate launches.
+static int fused_gave_up(npg_gmres *ws, hipStream_t st) {
+    hipStreamSynchronize(st);
+    hipMemset(ws->ho, 0, sizeof(RowsHandOff));
+    ws->h_ho[0] = ws->h_ho[1] = 0;
+    ws->fused_off = true;
+    ws->have_graph = false;
+    npg::set_error("npg_gmres_solve: the grid-wide hand-off of the fused row kernel timed out (a workgroup was not resident); "
+                   "the iterate is not valid - this workspace uses the separate row launches from now on");
+    return NPG_EHIP;
+}
+
+// Cycles until the carried state says done, at most max_cycles.  Cycle c+1 is enqueued before the host reads the outcome of
+// cycle c: the device never idles waiting for the host, and a cycle launched after convergence costs only its early-exit kernels.
+// Profile mode: eager launches with HIP events around every Arnoldi (SpMV) kernel, one cycle at a time - the events are read between two cycles.
+static int run_cycles(npg_gmres *ws, GmresPlan &p, int64_t max_cycles, Snap &last, hipStream_t st, std::chrono::steady_clock::time_point t0, int trace) {
+    if (ws->profile && ws->pev.empty()) {
+        ws->pev.resize(2 * ws->mem);
+        for (auto &e : ws->pev) NPG_HIP(hipEventCreate(&e));
     }
-    const int64_t max_cycles = (itmax + ws->mem - 1) / ws->mem + 1;
-    Snap last{};
     double t_launch = 0.0;
     int64_t n_launch = 0;
     auto enqueue_cycle = [&](int slot) -> int {
         const auto l0 = std::chrono::steady_clock::now();
-        if (eager || (dist && !graph_dist)) {
-            int rcc = launch_cycle(d, A->lanes, st, nullptr, ws, dist != nullptr);
-            if (rcc) return rcc;
-            NPG_HIP(hipMemcpyAsync(ws->h_C + slot, ws->C, sizeof(Snap), hipMemcpyDeviceToHost, st));
-            if (d.fusedrows) NPG_HIP(hipMemcpyAsync(ws->h_ho + slot, d.ho->status, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        } else {
+        if (p.use_graph)
             NPG_HIP(hipGraphLaunch(ws->exec[slot], st));
-        }
+        else if (int rc = launch_cycle(p, st, ws->profile ? ws->pev.data() : nullptr, ws, slot))
+            return rc;
         NPG_HIP(hipEventRecord(ws->ev[slot], st));
         t_launch += std::chrono::duration<double>(std::chrono::steady_clock::now() - l0).count();
         ++n_launch;
         return NPG_OK;
     };
-    // A hand-off of k_gmres_rows_fused that ran out of time has set the status word: that launch and every later one skipped the
-    // update, so the iterate is not to be trusted.  Report it, re-zero the hand-off state and keep to the separate launches.
-    auto fused_gave_up = [&]() -> int {
-        hipStreamSynchronize(st);
-        hipMemset(ws->ho, 0, sizeof(RowsHandOff));
-        ws->h_ho[0] = ws->h_ho[1] = 0;
-        ws->fused_off = true;
-        ws->have_graph = false;
-        npg::set_error("npg_gmres_solve: the grid-wide hand-off of the fused row kernel timed out (a workgroup was not resident); "
-                       "the iterate is not valid - this workspace uses the separate row launches from now on");
-        return NPG_EHIP;
-    };
-    if (!ws->profile) {
-        // cycle c+1 is enqueued before the host reads the outcome of cycle c: the device never idles waiting for the
-        // host, and a cycle launched after convergence costs only its early-exit kernels
-        int rc0 = enqueue_cycle(0);
-        if (rc0) return rc0;
-        for (int64_t cyc = 0;; ++cyc) {
-            const int cur = (int)(cyc & 1), nxt = cur ^ 1;
-            const bool more = cyc + 1 < max_cycles;
-            if (more) {
-                rc0 = enqueue_cycle(nxt);
-                if (rc0) return rc0;
-            }
-            NPG_HIP(hipEventSynchronize(ws->ev[cur]));
-            last = ws->h_C[cur];
-            if (d.fusedrows && ws->h_ho[cur] != 0) return fused_gave_up();
-            if (last.done == 5) {
-                // distributed: ||w||^2 - ||h||^2 met cancellation and the device interrupted the pass before that column.
-                // Carry on from the current iterate with explicitly reduced norms (a second all-reduce per step), for
-                // this and all later solves of the workspace.
-                NPG_HIP(hipStreamSynchronize(st));           // the cycle enqueued ahead has exited at once
-                d.pyth = 0;
-                ws->explicit_norm = true;
-                if (use_graph) {
-                    // the captured cycles have pyth = 1 baked into their kernel arguments: replaying them would flag the
-                    // same cancellation for ever - capture the explicit-norm cycle
-                    rc0 = capture_graphs();
-                    if (rc0) return rc0;
-                }
-                last.done = 0;
-                last.inner = 0;
-                ws->h_C[cur] = last;
-                NPG_HIP(hipMemcpyAsync(ws->C, ws->h_C + cur, sizeof(Snap), hipMemcpyHostToDevice, st));
-                if (dist && (rc0 = halo_exchange_raw(ws->halo, d.x))) return rc0;
-                launch_residual(d, A->lanes, st);
-                if (dist && (rc0 = fold_rows(ws, d.PR, d.G1, 2, st, true))) return rc0;
-                NPG_HIP(hipStreamSynchronize(st));           // h_C[cur] is a result slot again from here on
-                rc0 = enqueue_cycle(cur);
-                if (rc0) return rc0;
-                cyc = -1 + (cur == 0 ? 0 : 1);               // keep the slot parity of the ping-pong
-                continue;
-            }
-            if (last.done != 0 || !more) break;
+    int rc = enqueue_cycle(0);
+    if (rc) return rc;
+    for (int64_t cyc = 0;; ++cyc) {
+        const int cur = (int)(cyc & 1), nxt = cur ^ 1;
+        const bool more = cyc + 1 < max_cycles;
+        if (more && !ws->profile && (rc = enqueue_cycle(nxt))) return rc;
+        NPG_HIP(hipEventSynchronize(ws->ev[cur]));
+        last = ws->h_C[cur];
+        if (p.d.fusedrows && ws->h_ho[cur] != 0) return fused_gave_up(ws, st);
+        if (last.done == 5) {
+            if ((rc = restart_with_explicit_norms(ws, p, last, cur, st))) return rc;
+            if ((rc = enqueue_cycle(cur))) return rc;
+            cyc = -1 + (cur == 0 ? 0 : 1);               // keep the slot parity of the ping-pong
+            continue;
         }
-        NPG_HIP(hipStreamSynchronize(st));
-        if (trace)
-            fprintf(stderr,
-                    "[npg gmres] %s: %lld cycle launches, %.1f us host time per launch, %d iterations, %.1f us wall per "
-                    "iteration, %d second GS passes, fused rows %d (row grid %d, %d workgroups per CU admitted)\n",
-                    eager ? "eager" : "graph", (long long)n_launch, 1e6 * t_launch / (double)n_launch, last.iter,
-                    1e6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() /
-                        std::max(1, last.iter),
-                    last.nreorth, d.fusedrows, d.GR, ws->fused_blocks);
-    } else {
-        if (ws->pev.empty()) {
-            ws->pev.resize(2 * ws->mem);
-            for (auto &e : ws->pev) NPG_HIP(hipEventCreate(&e));
-        }
-        for (int64_t cyc = 0; cyc < max_cycles; ++cyc) {
-            int rcp = launch_cycle(d, A->lanes, st, ws->pev.data(), ws, dist != nullptr);
-            if (rcp) return rcp;
-            NPG_HIP(hipMemcpyAsync(ws->h_C, ws->C, sizeof(Snap), hipMemcpyDeviceToHost, st));
-            if (d.fusedrows) NPG_HIP(hipMemcpyAsync(ws->h_ho, d.ho->status, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-            NPG_HIP(hipStreamSynchronize(st));
-            if (d.fusedrows && ws->h_ho[0] != 0) return fused_gave_up();
-            last = ws->h_C[0];
-            if (last.done == 5) {           // see the pipelined loop: explicit norms from here on
-                d.pyth = 0;
-                ws->explicit_norm = true;
-                last.done = 0;
-                last.inner = 0;
-                ws->h_C[0] = last;
-                NPG_HIP(hipMemcpyAsync(ws->C, ws->h_C, sizeof(Snap), hipMemcpyHostToDevice, st));
-                int rcx = NPG_OK;
-                if (dist && (rcx = halo_exchange_raw(ws->halo, d.x))) return rcx;
-                launch_residual(d, A->lanes, st);
-                if (dist && (rcx = fold_rows(ws, d.PR, d.G1, 2, st, true))) return rcx;
-                NPG_HIP(hipStreamSynchronize(st));
-                continue;
-            }
-            if (last.done != 0) break;      // the last (partial) cycle is not counted: some of its kernels exit early
+        if (last.done != 0) break;      // (profile mode: the last (partial) cycle is not counted: some of its kernels exit early)
+        if (ws->profile)
             for (int j = 0; j < ws->mem; ++j) {
                 float ms = 0.f;
                 NPG_HIP(hipEventElapsedTime(&ms, ws->pev[2 * j], ws->pev[2 * j + 1]));
                 ws->prof_ms += ms;
                 ws->prof_launches += 1;
             }
-        }
+        if (!more) break;
+        if (ws->profile && (rc = enqueue_cycle(nxt))) return rc;
     }
+    NPG_HIP(hipStreamSynchronize(st));
+    if (trace)
+        fprintf(stderr,
+                "[npg gmres] %s: %lld cycle launches, %.1f us host time per launch, %d iterations, %.1f us wall per "
+                "iteration, %d second GS passes, fused rows %d (row grid %d, %d workgroups per CU admitted)\n",
+                p.use_graph ? "graph" : "eager", (long long)n_launch, 1e6 * t_launch / (double)n_launch, last.iter,
+                1e6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() /
+                    std::max(1, last.iter),
+                last.nreorth, p.d.fusedrows, p.d.GR, ws->fused_blocks);
+    return NPG_OK;
+}
+
+// what the solve launched (npg_gmres_last_config; gmres_plan reroutes on size, tolerance, matrix form and safe_mode) and how it ended
+static int gmres_report(npg_gmres *ws, const GmresPlan &p, const Snap &last, std::chrono::steady_clock::time_point t0, npg_solve_stats *stats) {
+    const GDev &d = p.d;
     ws->hist_len = std::min<int64_t>((int64_t)last.iter + 1, ws->hist_cap);
-    {
-        // what launch_cycle dispatched on (the selection rules above reroute on size, tolerance, matrix form and safe_mode)
-        const int a_nt = d.wt_ptr ? d.nwt : d.ntiles;
-        const int32_t cfg[kCfgLen] = {d.split, d.Vf ? 32 : 64, d.fast, d.xg.p ? (d.xg.nbr == 0 ? 2 : 1) : 0, d.wt_ptr ? 1 : 0,
-                                      d.wt_ptr ? d.wl : 0, d.wt_ptr ? d.word : 0, A->lanes, A->pk9 ? 1 : 0, dist ? 1 : 0, d.pyth,
-                                      a_nt, d.split ? std::min(d.G1, std::max(1, a_nt)) : d.G1, d.split ? d.GR : d.G2, d.n, d.mem,
-                                      d.lazy2, d.fusedrows};
-        memcpy(ws->cfg, cfg, sizeof cfg);
-        ws->have_cfg = true;
-    }
-    if (dist) {
-        int rcc = comm_check(ctx);      // a replayed cycle reports communication timeouts through the status word only
-        if (rcc) return rcc;
-    }
+    const int32_t cfg[kCfgLen] = {d.split, d.Vf ? 32 : 64, d.fast, d.xg.p ? (d.xg.nbr == 0 ? 2 : 1) : 0, d.wt_ptr ? 1 : 0,
+                                  d.wt_ptr ? d.wl : 0, d.wt_ptr ? d.word : 0, p.lanes, d.A.pk9 ? 1 : 0, p.dist, d.pyth,
+                                  p.a_nt, p.grid, d.split ? d.GR : d.G2, d.n, d.mem, d.lazy2, d.fusedrows};
+    memcpy(ws->cfg, cfg, sizeof cfg);
+    ws->have_cfg = true;
+    // a replayed cycle reports communication timeouts through the status word only
+    if (int rc = p.dist ? comm_check(ws->ctx) : NPG_OK) return rc;
     if (stats) {
         stats->solved = (last.done == 1 || last.done == 4) ? 1 : 0;
         stats->niter = last.iter;
@@ -2053,6 +1970,88 @@ NPG_API int npg_gmres_solve(npg_gmres *ws, const npg_csr *A_in, int precond_kind
         stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
     return NPG_OK;
+}
+
+// npg_csr_block_nodes_dofs: right-hand side, iterate (warm start in, solution out) and a vector preconditioner come and go
+// in the CALLER's DoF order - three gather passes in, one scatter pass out, then the solve proper on the library's order
+static int solve_in_caller_order(npg_gmres *ws, const npg_csr *A_in, int precond_kind, double precond_scalar, const npg_vec *precond_diag,
+                                 const npg_vec *y, npg_vec *x, double atol, double rtol, int64_t itmax, double reorth_eta,
+                                 npg_solve_stats *stats) {
+    NPG_REQUIRE(!ws->halo, "npg_gmres_solve: a matrix with an internal renumbering cannot be a distributed row block");
+    NPG_REQUIRE(y->n == A_in->m && x->n == A_in->m, "npg_gmres_solve: vector lengths do not match the matrix");
+    npg_csr *Am = const_cast<npg_csr *>(A_in);
+    npg_vec yi = *y, xi = *x, di;
+    yi.d = Am->uvec[0];
+    xi.d = Am->uvec[1];
+    yi.owns = xi.owns = false;
+    perm_gather(A_in, yi.d, y->d);
+    perm_gather(A_in, xi.d, x->d);
+    const npg_vec *dp = precond_diag;
+    if (precond_kind == NPG_PRECOND_DIAG && precond_diag) {
+        NPG_REQUIRE(precond_diag->n == A_in->m, "npg_gmres_solve: bad preconditioner");
+        di = *precond_diag;
+        di.d = Am->uvec[2];
+        di.owns = false;
+        perm_gather(A_in, di.d, precond_diag->d);
+        dp = &di;
+    }
+    Am->uperm_active = true;
+    const int rc = npg_gmres_solve(ws, A_in, precond_kind, precond_scalar, dp, &yi, &xi, atol, rtol, itmax, reorth_eta, stats);
+    Am->uperm_active = false;
+    if (rc) return rc;
+    perm_scatter(A_in, x->d, xi.d);
+    NPG_HIP(hipStreamSynchronize(ws->ctx->stream));
+    return NPG_OK;
+}
+
+NPG_API int npg_gmres_solve(npg_gmres *ws, const npg_csr *A_in, int precond_kind, double precond_scalar,
+                            const npg_vec *precond_diag, const npg_vec *y, npg_vec *x, double atol, double rtol,
+                            int64_t itmax, double reorth_eta, npg_solve_stats *stats) {
+    NPG_REQUIRE(ws && A_in && y && x, "npg_gmres_solve: NULL argument");
+    ws->have_cfg = false;         // (npg_gmres_last_config reports nothing for a solve that fails)
+    if (A_in->uperm && !A_in->uperm_active)
+        return solve_in_caller_order(ws, A_in, precond_kind, precond_scalar, precond_diag, y, x, atol, rtol, itmax, reorth_eta, stats);
+    const npg_csr *A = spmv_form(A_in);           // (the record-form companion of a plain matrix, if it has one)
+    if (int rc = check_record_view(A, true, "npg_gmres_solve")) return rc;     // (full node records: the split kernels, forced in gmres_plan)
+    const int64_t nloc = ws->n + ws->n_ghost;     // distributed: vectors the SpMV reads hold [owned | ghosts]
+    NPG_REQUIRE(A->m == ws->n && A->n == nloc && y->n == ws->n && x->n == nloc,
+                "npg_gmres_solve: workspace is for n=%lld (+%lld ghosts) but A is %lldx%lld, y has %lld, x has %lld",
+                (long long)ws->n, (long long)ws->n_ghost, (long long)A->m, (long long)A->n, (long long)y->n,
+                (long long)x->n);
+    NPG_REQUIRE(precond_kind == NPG_PRECOND_NONE || precond_kind == NPG_PRECOND_SCALAR ||
+                    (precond_kind == NPG_PRECOND_DIAG && precond_diag && precond_diag->n == ws->n),
+                "npg_gmres_solve: bad preconditioner");
+    const auto t0 = std::chrono::steady_clock::now();
+    hipStream_t st = ws->ctx->stream;
+    static const GmresKnobs knobs;
+    if (ws->halo) reorth_eta = 0.0;     // distributed: the on-the-fly second pass would need basis rows of ghost columns
+
+    // the plan: selection decides instances, grids and buffer sizes; the buffers are made; their pointers complete the plan
+    GmresPlan p;
+    gmres_plan(p, ws, A, precond_kind, precond_scalar, precond_diag, y, x, rtol, reorth_eta, knobs);
+    if (int rc = gmres_plan_buffers(p, ws, A, st)) return rc;
+
+    if (itmax <= 0) itmax = 2 * ws->n;
+    ws->h_prm->atol = atol;
+    ws->h_prm->rtol = rtol;
+    ws->h_prm->eta2 = reorth_eta <= 0.0 ? -1.0 : reorth_eta * reorth_eta;
+    ws->h_prm->btol = std::pow(2.220446049250313e-16, 0.75);
+    ws->h_prm->itmax = itmax;
+    NPG_HIP(hipMemcpyAsync(ws->prm, ws->h_prm, sizeof(GParams), hipMemcpyHostToDevice, st));
+    Snap c0{};
+    c0.first = 1;
+    ws->h_C[0] = c0;
+    NPG_HIP(hipMemcpyAsync(ws->C, ws->h_C, sizeof(Snap), hipMemcpyHostToDevice, st));
+    NPG_HIP(hipStreamSynchronize(st));      // h_C[0] is reused below as a result slot
+
+    if (int rc = ensure_graphs(ws, p, st)) return rc;
+
+    // first true residual, then cycles until the carried state says done
+    if (int rc = launch_first_residual(ws, p, st)) return rc;
+    const int64_t max_cycles = (itmax + ws->mem - 1) / ws->mem + 1;
+    Snap last{};
+    if (int rc = run_cycles(ws, p, max_cycles, last, st, t0, knobs.trace)) return rc;
+    return gmres_report(ws, p, last, t0, stats);
 }
 
 NPG_API int npg_gmres_set_dist_options(npg_gmres *ws, int overlap, int graph) {

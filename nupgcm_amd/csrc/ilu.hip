@@ -277,7 +277,7 @@ NPG_API int npg_ilu0_create(npg_ctx *ctx, const npg_csr *A, npg_ilu0 **out) {
     NPG_HIP(hipMemcpy(m->rows_l, rl.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
     NPG_HIP(hipMemcpy(m->rows_u, ru.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
     // (graph replay under rocprofv3's tracer: see mg.hip)
-    const bool traced = getenv("ROCPROFILER_LIBRARY_CTOR") || getenv("ROCPROF_OUTPUT_PATH") || getenv("ROCP_TOOL_LIBRARIES");
+    const bool traced = profiler_attached();
     m->use_graph = getenv("NPG_ILU_EAGER") ? atoi(getenv("NPG_ILU_EAGER")) == 0 : !traced;
     int rc = ilu_factor(m, A);
     if (rc) return rc;

@@ -419,7 +419,7 @@ NPG_API int npg_precond_create(npg_ctx *ctx, int kind, int nparts, npg_precond *
     // relaunching hipGraphs under rocprofv3's kernel tracer can fault inside the tool (a batch of AQL packets that straddles
     // the end of the queue ring: profiles/r03_rocprofv3_graph_fault.txt): a traced process launches the cycle eagerly unless
     // NPG_MG_EAGER=0 says otherwise
-    const bool traced = getenv("ROCPROFILER_LIBRARY_CTOR") || getenv("ROCPROF_OUTPUT_PATH") || getenv("ROCP_TOOL_LIBRARIES");
+    const bool traced = profiler_attached();
     pc->use_graphs = getenv("NPG_MG_EAGER") ? atoi(getenv("NPG_MG_EAGER")) == 0 : !traced;
     static bool said = false;
     if (traced && !getenv("NPG_MG_EAGER") && !said && (said = true))

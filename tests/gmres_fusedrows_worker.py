@@ -32,7 +32,7 @@ def main():
     out = sys.argv[1]
     os.environ["NPG_GMRES_FUSEDROWS"] = sys.argv[2]        # (read by every solve)
     os.environ["NPG_GMRES_ONEFOLD"] = sys.argv[3]
-    os.environ["NPG_GMRES_ROWS_WG"] = "64"                 # (read once, by the first solve with an fp32-stored basis)
+    os.environ["NPG_GMRES_ROWS_WG"] = "64"                 # (read once, by the first solve of the process)
     arch = npg.GPU()
     res = {}
 

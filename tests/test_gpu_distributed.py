@@ -75,7 +75,7 @@ def test_peer_and_shm_transports_give_the_same_bits(tmp_path):
                                                           (3, True, True, "peer")])
 def test_multi_rank_rehearsal(serial, world, blocks, split, transport, tmp_path):
     """split: force the split GMRES cycle that rank blocks of >= 8192 rows use - its Arnoldi step runs the tiles without
-    ghost columns before the halo exchange has completed and the others behind it (gmres.hip, launch_cycle_L)."""
+    ghost columns before the halo exchange has completed and the others behind it (gmres.hip: decided in gmres_plan, launched by launch_cycle_L)."""
     ref, y = serial
     out = str(tmp_path / "dist")
     r = _launch(world, out, 3, "blocks" if blocks else "csr", transport, split=split)

@@ -286,6 +286,67 @@ def test_one_rank_distributed(arch, n, memory):
              1e-13, 2e-14, ks_for(memory), setup=_halo_setup(arch, n, keep))
 
 
+# ---- profile mode and the graph cache ---------------------------------------------------------------------------------------
+PROFILE = [  # (name, n, memory, setup, distributed, want)
+    ("fused", 513, 5, dict(), False, dict(split=0)),
+    ("split-fp64", 20001, 9, dict(split=1, basis=64), False, dict(split=1, basis=64, fusedrows=0)),
+    ("split-fp32", 20001, 9, dict(split=1, basis=32), False, dict(split=1, basis=32, fusedrows=1)),
+    ("one-rank-distributed", 12001, 9, dict(), True, dict(distributed=1, split=1)),
+]
+
+
+@pytest.mark.parametrize("case", PROFILE, ids=[c[0] for c in PROFILE])
+def test_profile_mode_same_bits(arch, case):
+    """set_profile(True) (eager launches, the Arnoldi kernels timed by events: what bench.py --full takes its roofline figure from)
+    changes no bit: two full cycles and a third that stops at itmax, against the same solve replayed from the captured graphs.
+    The two full cycles are the ones counted: 2 * memory timed launches."""
+    name, n, memory, setup, distributed, want = case
+    A, b, x0, dv = synth(n, 11 + memory)
+    dA = npg.on_architecture(arch, A)
+    keep, profiled = [], []
+    base = _halo_setup(arch, n, keep) if distributed else _setup(setup)
+
+    def with_profile(ws):
+        base(ws)
+        ws.set_profile(True)
+        profiled.append(ws)
+
+    k = 2 * memory + 3
+    st, hist, x, cfg = one_solve(arch, dA, b, x0, n, memory, k, dv, base, 0.1)
+    stp, histp, xp, cfgp = one_solve(arch, dA, b, x0, n, memory, k, dv, with_profile, 0.1)
+    for key, v in want.items():
+        assert cfg[key] == v, (name, key, cfg)
+    assert st["niter"] == k and len(hist) == k + 1, (name, st)
+    assert np.array_equal(histp, hist) and np.array_equal(xp, x), name
+    for key in ("niter", "nreorth", "nflagged", "status"):
+        assert stp[key] == st[key], (name, key, stp, st)
+    assert cfgp == cfg, (name, cfgp, cfg)
+    ms, launches = profiled[0].get_profile()
+    assert ms > 0.0 and launches == 2 * memory, (name, ms, launches)
+
+
+def test_lanes_change_recaptures(arch):
+    """npg_csr_set_lanes between two solves of ONE workspace with the SAME device vectors (no kernel argument changes): the captured
+    cycle has the lane instance baked in, so the second solve has to capture again - it is, bit for bit, a fresh workspace's solve
+    at the new lane count"""
+    n, memory = 20001, 9
+    A, b, x0, _ = synth(n, 3 + memory)
+    dA, db, x = npg.on_architecture(arch, A), npg.on_architecture(arch, b), npg.on_architecture(arch, x0)
+    setup = _setup(dict(split=1, basis=64))
+    k = 2 * memory + 3
+    ws = npg.GmresWorkspace(arch.ctx, n, memory=memory)
+    setup(ws)
+    for lanes in (4, 32):
+        dA.set_lanes(lanes)
+        x.upload(x0)
+        ws.solve(dA, db, x, None, atol=0.0, rtol=0.0, itmax=k, reorth_eta=0.1)
+        assert ws.last_config()["L"] == lanes, ws.last_config()
+    hist, x = ws.history(), x.to_host()
+    _, hist32, x32, cfg32 = one_solve(arch, dA, b, x0, n, memory, k, None, setup, 0.1)
+    assert cfg32["L"] == 32, cfg32
+    assert np.array_equal(hist, hist32) and np.array_equal(x, x32)
+
+
 # ---- inversion matrices (bowl3D) -------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def bowl():
@@ -487,7 +548,7 @@ def test_windowed_product_of_a_row_block_with_ghost_nodes(arch, bowl):
 # ---- coverage ------------------------------------------------------------------------------------------------------------------
 # The Arnoldi instances launch_arnoldi_split (gmres.hip, "static void launch_arnoldi_split": nine branches) and the fused launch in
 # launch_cycle_L can dispatch on one GPU, as last_config() keys (split, xg, pk9, windowed, wl, word).  word (ORD) is set by
-# npg_gmres_solve as NPG_WIN_ORD || (no row tiles in the windowed set && rows behind the block rows); the bowl inversion matrices
+# gmres_plan as NPG_WIN_ORD || (no row tiles in the windowed set && rows behind the block rows); the bowl inversion matrices
 # have row tiles, so the ORD instances run in the child process of test_windowed_ord_instances.  Row kernels (launch_rows_kernel):
 # NG = (j + 8) / 8 for j < memory, basis 64 / 32, fast or full orthogonalisation - reached by every split case with memory >= 25 at
 # k = 2 memory + 3.
