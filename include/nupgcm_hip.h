@@ -635,7 +635,7 @@ int npg_classes_mixing(npg_classes *K, const npg_vec *b, double N2, double kappa
                        npg_vec *table, npg_vec *info);   /* table, info: as npg_classes_compute */
 
 /* ---- Lagrangian particles advected through the device-resident flow (new work: offline tracking needs u saved every step) -----
- * n particles on the device: position [n][3], the cell each was last located in, status (0 alive, 1 lost), wind [n][3] and t_lost.
+ * n particles on the device: position [n][3], the cell each was last located in, status (0 alive, 1 lost, 2 stuck), wind [n][3] and t_lost.
  * npg_particles_advance carries every live particle through nsub classical RK4 steps of dx/dt = u(x, t), h = dt / nsub, in ONE kernel
  * (csrc/particles_core.h): per stage locate -> evaluate u (closed-form P2 through the DoF tables, as npg_fe_sample(NPG_SAMPLE_U)) ->
  * next stage point; the remembered cell is accepted without reading the bins when the point's min lambda there is >= 1e-8, otherwise
@@ -661,6 +661,35 @@ int npg_particles_advance(npg_particles *P, npg_fe *fe, npg_locator *loc, const 
 int npg_particles_download(const npg_particles *P, double *xyz, int32_t *cell, int32_t *status, int32_t *wind, double *t_lost);
 /* device copy of the positions into a vector of 3 n doubles: what npg_locator_find / npg_fe_sample take (b along a path) */
 int npg_particles_positions(const npg_particles *P, npg_vec *out);
+
+/* ---- diffusing particles and reflecting walls (csrc/particles_walk_core.h; opt-in: npg_particles_advance keeps its bits) -----------
+ * npg_particles_walk is npg_particles_advance - the same arguments, the same clock, the same RK4 step - with every move of a particle
+ * (the three stage points, the RK4 end point, the random displacement) walked from cell to cell through a neighbour table: across an
+ * interior face into the neighbour, across a periodic seam with the face's translation, off a boundary face by reflection of the
+ * remainder (r <- r - 2 (r . n) n), which the particle's reflection counter counts for the moves that move the particle (the end
+ * point and the random displacement; a stage point's reflections and crossings are its own).  More than 64 face events in one move,
+ * or an end point that npg_locator_find would refuse: the step is not taken and the particle is STUCK - status 2, otherwise the rule
+ * of a lost one.  A seed that is NaN or outside the mesh is lost (status 1), as before.
+ *   nbr[ncell][4]       the cell across the face opposite local vertex i (the locator's vertex order), -1 = a boundary face
+ *   shift[ncell][4][3]  the translation in periods (-1, 0, 1) a point takes on each axis when it crosses that face: x += shift L,
+ *                       wind -= shift (unwrapped = x + wind L stays where it was); nonzero only across a periodic seam.  On an axis
+ *                       with a period the table must carry the seam (a walked point is not wrapped), on any other it must not.
+ * Diffusion (optional; without it: reflecting advection): kappa_h[ncell][4], kappa_v[ncell][4] at each cell's own vertices, piecewise
+ * linear (kappa = sum lambda_i kappa_i, grad kappa constant in the cell), finite and >= 0.  After each RK4 step of length h, in the
+ * cell of its end point (Visser's scheme with uniform increments):
+ *   delta = c_d h (d_x kappa_h, d_y kappa_h, d_z kappa_v);   kappa* = max(kappa + delta . grad kappa / 2, 0) for kappa_h and kappa_v;
+ *   Delta_a = delta_a + R_a sqrt(6 c_d kappa*_a h),          R = the generator's three uniforms in (-1, 1): variance 2 c_d kappa* h.
+ * Generator: Philox4x32-10, key = seed (low, high word), counter = (particle index low, high, step number low, high), R_a =
+ * (2 w_a + 1) 2^-32 - 1 from words 0..2.  The step number counts the steps of npg_particles_walk since npg_particles_set (nsub per
+ * call).  A second npg_particles_set_diffusion replaces the first; kappa_h = kappa_v = NULL switches diffusion off. */
+int npg_particles_set_walls(npg_particles *P, const int32_t *nbr, const int8_t *shift, int64_t ncell);
+int npg_particles_set_diffusion(npg_particles *P, const double *kappa_h, const double *kappa_v, int64_t ncell, double c_d, uint64_t seed);
+int npg_particles_walk(npg_particles *P, npg_fe *fe, npg_locator *loc, const npg_vec *x_a, const npg_vec *x_b, double s0, double s1,
+                       double dt, int64_t nsub);
+/* nreflect[n] (host; zeros before any walls were set) and the step number; either may be NULL */
+int npg_particles_download_walk(const npg_particles *P, int32_t *nreflect, uint64_t *step);
+/* the generator alone: R of n consecutive particle indices from first_index at one step number, out = 3 n doubles */
+int npg_particles_uniforms(npg_ctx *ctx, uint64_t seed, uint64_t first_index, int64_t n, uint64_t step, npg_vec *out);
 
 /* ---- passive tracers carried by the flow (new work: the reference evolves b' alone) -------------------------------------------
  * K scalars stepped with the model's own advection-diffusion operator: the same BDF scheme, the same matrix M + theta (Kh + Kv) and the

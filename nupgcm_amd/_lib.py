@@ -96,7 +96,7 @@ def lib():
 
 def _declare(L, partial=False):
     P, I64, I32, D, VP = C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_void_p
-    PP = C.POINTER(C.c_void_p)
+    PP, U64 = C.POINTER(C.c_void_p), C.c_uint64
     sig = {
         "npg_ctx_create": [C.c_int, PP], "npg_ctx_destroy": [P], "npg_ctx_sync": [P],
         "npg_mem_status": [P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
@@ -167,6 +167,9 @@ def _declare(L, partial=False):
         "npg_particles_create": [P, I64, PP], "npg_particles_destroy": [P], "npg_particles_set": [P, VP, D],
         "npg_particles_set_period": [P, VP], "npg_particles_advance": [P, P, P, P, P, D, D, D, I64],
         "npg_particles_download": [P, VP, VP, VP, VP, VP], "npg_particles_positions": [P, P],
+        "npg_particles_set_walls": [P, VP, VP, I64], "npg_particles_set_diffusion": [P, VP, VP, I64, D, U64],
+        "npg_particles_walk": [P, P, P, P, P, D, D, D, I64], "npg_particles_download_walk": [P, VP, VP],
+        "npg_particles_uniforms": [P, U64, U64, I64, U64, P],
         "npg_tracers_create": [P, C.c_int, PP], "npg_tracers_destroy": [P], "npg_tracers_set": [P, C.c_int, VP, D, D],
         "npg_tracers_rhs": [P, C.c_int, D, D, P, P, P, P, P, P, P],
         "npg_comm_unique_id": [VP], "npg_comm_init": [P, VP, C.c_int, C.c_int],

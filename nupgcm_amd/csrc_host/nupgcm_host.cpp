@@ -1727,6 +1727,7 @@ NPG_API int npg_classes_mixing(npg_classes *K, const npg_vec *b, double N2, doub
 // ---- Lagrangian particles in the flow (csrc/particles.hip on the host): the RK4 step, the remembered cell, the periodic wrap and the
 // rule for leaving the mesh are the SAME code (csrc/particles_core.h), looped over the particles with OpenMP -------------------------
 #include "../csrc/particles_core.h"
+#include "../csrc/particles_walk_core.h"
 
 struct npg_particles {
     npg_ctx *ctx = nullptr;
@@ -1735,6 +1736,14 @@ struct npg_particles {
     double L[3] = {0.0, 0.0, 0.0};
     std::vector<double> xyz, t_lost;
     std::vector<int32_t> cell, status, wind;
+    // npg_particles_walk: the wall tables, the diffusivities, the generator's key and the count of steps since npg_particles_set
+    int64_t wall_ncell = -1, kappa_ncell = -1;       // -1 = not set
+    bool wall_axis[3] = {false, false, false};
+    std::vector<int32_t> nbr, nreflect;
+    std::vector<int8_t> shift;
+    std::vector<double> kappa_h, kappa_v;
+    double cd = 0.0;
+    uint64_t seed = 0, step = 0;
 };
 
 NPG_API int npg_particles_create(npg_ctx *ctx, int64_t n, npg_particles **out) {
@@ -1759,6 +1768,8 @@ NPG_API int npg_particles_set(npg_particles *P, const double *xyz, double t0) {
     REQUIRE(P && (P->n == 0 || xyz), "npg_particles_set: NULL argument");
     REQUIRE(std::isfinite(t0), "npg_particles_set: t0 is not finite");
     P->t = t0;
+    P->step = 0;
+    std::fill(P->nreflect.begin(), P->nreflect.end(), 0);
     if (P->n) std::copy(xyz, xyz + 3 * P->n, P->xyz.begin());
     std::fill(P->t_lost.begin(), P->t_lost.end(), NAN);
     std::fill(P->cell.begin(), P->cell.end(), -1);
@@ -1806,6 +1817,106 @@ NPG_API int npg_particles_advance(npg_particles *P, npg_fe *fe, npg_locator *loc
         P->cell[(size_t)i] = p.c;
     }
     P->t += dt;
+    return NPG_OK;
+}
+NPG_API int npg_particles_set_walls(npg_particles *P, const int32_t *nbr, const int8_t *shift, int64_t ncell) {
+    REQUIRE(P && nbr && shift, "npg_particles_set_walls: NULL argument");
+    REQUIRE(ncell >= 1 && ncell <= INT32_MAX, "npg_particles_set_walls: ncell = %lld", (long long)ncell);
+    bool has[3];
+    const char *err = npg::check_wall_tables(nbr, shift, ncell, P->L, has);
+    REQUIRE(!err, "npg_particles_set_walls: %s", err);
+    P->nbr.assign(nbr, nbr + ncell * 4);
+    P->shift.assign(shift, shift + ncell * 12);
+    P->nreflect.resize((size_t)P->n, 0);
+    P->wall_ncell = ncell;
+    for (int a = 0; a < 3; ++a) P->wall_axis[a] = has[a];
+    return NPG_OK;
+}
+NPG_API int npg_particles_set_diffusion(npg_particles *P, const double *kappa_h, const double *kappa_v, int64_t ncell, double c_d,
+                                        uint64_t seed) {
+    REQUIRE(P, "npg_particles_set_diffusion: NULL handle");
+    if (!kappa_h && !kappa_v) {              // diffusion off
+        P->kappa_h.clear(), P->kappa_v.clear(), P->kappa_ncell = -1;
+        return NPG_OK;
+    }
+    REQUIRE(kappa_h && kappa_v, "npg_particles_set_diffusion: NULL argument (kappa_h and kappa_v are given together)");
+    REQUIRE(ncell >= 1 && ncell <= INT32_MAX, "npg_particles_set_diffusion: ncell = %lld", (long long)ncell);
+    REQUIRE(P->wall_ncell < 0 || P->wall_ncell == ncell, "npg_particles_set_diffusion: ncell = %lld, the wall tables have %lld cells",
+            (long long)ncell, (long long)P->wall_ncell);
+    const char *err = npg::check_kappa_tables(kappa_h, kappa_v, ncell, c_d);
+    REQUIRE(!err, "npg_particles_set_diffusion: %s", err);
+    P->kappa_h.assign(kappa_h, kappa_h + ncell * 4);
+    P->kappa_v.assign(kappa_v, kappa_v + ncell * 4);
+    P->kappa_ncell = ncell, P->cd = c_d, P->seed = seed;
+    return NPG_OK;
+}
+NPG_API int npg_particles_walk(npg_particles *P, npg_fe *fe, npg_locator *loc, const npg_vec *x_a, const npg_vec *x_b, double s0,
+                               double s1, double dt, int64_t nsub) {
+    REQUIRE(P && fe && loc && x_a && x_b, "npg_particles_walk: NULL argument");
+    REQUIRE(fe->ctx == P->ctx && loc->ctx == P->ctx && x_a->ctx == P->ctx && x_b->ctx == P->ctx,
+            "npg_particles_walk: arguments of different contexts");
+    REQUIRE(loc->ncell == fe->ncell, "npg_particles_walk: the locator was built for another mesh (an embedded 2-D engine has no "
+            "locator: particles need a tetrahedral mesh)");
+    REQUIRE(x_a->n == fe->n_inv && x_b->n == fe->n_inv, "npg_particles_walk: the flow vectors have %lld and %lld entries, expected %lld",
+            (long long)x_a->n, (long long)x_b->n, (long long)fe->n_inv);
+    const char *err = npg::check_particle_call(s0, s1, dt, nsub);
+    REQUIRE(!err, "npg_particles_walk: %s", err);
+    REQUIRE(P->wall_ncell >= 0, "npg_particles_walk: no walls - call npg_particles_set_walls first");
+    REQUIRE(P->wall_ncell == loc->ncell, "npg_particles_walk: the wall tables have ncell = %lld, the locator %lld",
+            (long long)P->wall_ncell, (long long)loc->ncell);
+    REQUIRE(P->kappa_ncell < 0 || P->kappa_ncell == loc->ncell, "npg_particles_walk: the diffusivity tables have ncell = %lld, the locator %lld",
+            (long long)P->kappa_ncell, (long long)loc->ncell);
+    for (int a = 0; a < 3; ++a)
+        REQUIRE(P->wall_axis[a] == (P->L[a] > 0.0), "npg_particles_walk: axis %d has period %g but the wall tables carry %s seam "
+                "shift on it - a walked particle crosses a seam through the table", a, P->L[a], P->wall_axis[a] ? "a" : "no");
+    const npg::ParticleCall call = npg::make_particle_call(P->t, s0, s1, dt, nsub);
+    const uint64_t step0 = P->step;
+    const HostTables t{fe, fe->u_diri.data(), fe->b_diri.data(), fe->nb};
+    const npg::BinTables &bt = loc->t;
+    const npg::ParticleMesh m{bt.grid, bt.bin_ptr.data(), bt.bin_cells.data(), bt.geo.data(), {P->L[0], P->L[1], P->L[2]}};
+    const bool blend = x_a->d != x_b->d, diffuse = P->kappa_ncell >= 0;
+    const npg::WalkTables w{P->nbr.data(), P->shift.data(), P->kappa_h.data(), P->kappa_v.data(), P->cd, (uint32_t)P->seed,
+                            (uint32_t)(P->seed >> 32)};
+    const double *xa = x_a->d, *xb = blend ? x_b->d : x_a->d;
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < P->n; ++i) {
+        if (P->status[(size_t)i] != 0) continue;         // lost or stuck: nothing moves it
+        npg::ParticleState p;
+        for (int a = 0; a < 3; ++a) p.x[a] = P->xyz[(size_t)3 * i + a], p.wind[a] = P->wind[(size_t)3 * i + a];
+        p.c = P->cell[(size_t)i];
+        int32_t nrefl = P->nreflect[(size_t)i];
+        const uint64_t idx = (uint64_t)i;
+        const int64_t done = blend ? (diffuse ? npg::particle_walk<true, true>(m, w, t, xa, xb, call, nsub, idx, step0, p, nrefl)
+                                              : npg::particle_walk<true, false>(m, w, t, xa, xb, call, nsub, idx, step0, p, nrefl))
+                                   : (diffuse ? npg::particle_walk<false, true>(m, w, t, xa, xb, call, nsub, idx, step0, p, nrefl)
+                                              : npg::particle_walk<false, false>(m, w, t, xa, xb, call, nsub, idx, step0, p, nrefl));
+        if (done < nsub) {
+            P->status[(size_t)i] = done < 0 ? 1 : 2;
+            P->t_lost[(size_t)i] = done > 0 ? call.t + (double)done * call.h : call.t;
+            if (done < 0) continue;                      // lost where the call found it: the seed stays as it was given
+        }
+        for (int a = 0; a < 3; ++a) P->xyz[(size_t)3 * i + a] = p.x[a], P->wind[(size_t)3 * i + a] = p.wind[a];
+        P->cell[(size_t)i] = p.c;
+        P->nreflect[(size_t)i] = nrefl;
+    }
+    P->t += dt, P->step += (uint64_t)nsub;
+    return NPG_OK;
+}
+NPG_API int npg_particles_download_walk(const npg_particles *P, int32_t *nreflect, uint64_t *step) {
+    REQUIRE(P, "npg_particles_download_walk: NULL handle");
+    if (step) *step = P->step;
+    if (nreflect) {
+        std::fill(nreflect, nreflect + P->n, 0);
+        std::copy(P->nreflect.begin(), P->nreflect.end(), nreflect);
+    }
+    return NPG_OK;
+}
+NPG_API int npg_particles_uniforms(npg_ctx *ctx, uint64_t seed, uint64_t first_index, int64_t n, uint64_t step, npg_vec *out) {
+    REQUIRE(ctx && out, "npg_particles_uniforms: NULL argument");
+    REQUIRE(n >= 0 && out->ctx == ctx && out->n == 3 * n, "npg_particles_uniforms: out must hold 3 n = %lld doubles of this context",
+            (long long)(3 * n));
+    for (int64_t i = 0; i < n; ++i)
+        npg::particle_uniforms((uint32_t)seed, (uint32_t)(seed >> 32), first_index + (uint64_t)i, step, out->d + 3 * i);
     return NPG_OK;
 }
 NPG_API int npg_particles_download(const npg_particles *P, double *xyz, int32_t *cell, int32_t *status, int32_t *wind, double *t_lost) {

@@ -7,7 +7,10 @@ timesteps), after a warm-up call, by device events, best and median of 20:
     between them are NOT counted, which flatters this baseline.
 The share of the step's locations (stages 2, 3, 4 and the end point; stage 1 is carried over) that the remembered cell serves without
 an election is counted on the host from one download of the located stage points.
-Usage: python tools/particles_bench.py [--workload L] [--steps K] [--reps R] [--log2n N]"""
+--diffusion adds, after the lines above and in the same process, npg_particles_walk(nsub = 1) (k_particles_walk) from the
+same seeds and h: with walls only, and with walls and diffusion - the model's kappa forcings at the vertices, c_d h = 1e-4 - next to
+the frozen npg_particles_advance timed above.
+Usage: python tools/particles_bench.py [--workload L] [--steps K] [--reps R] [--log2n N] [--diffusion]"""
 import argparse
 import os
 import sys
@@ -53,6 +56,7 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--log2n", type=int, default=20)
+    ap.add_argument("--diffusion", action="store_true")
     a = ap.parse_args()
     arch = npg.GPU()
     ctx = arch.ctx
@@ -116,6 +120,22 @@ def main():
     print(f"npg_particles_advance(nsub = 1), blended, by events: best {bl[0]:.3f} ms, median {bl[1]:.3f} ms")
     print(f"4 x (npg_locator_find + npg_fe_sample(U)) by events: best {base[0]:.3f} ms, median {base[1]:.3f} ms")
     print(f"ratio fused / unfused = {dev[0] / base[0]:.2f} (best), {dev[1] / base[1]:.2f} (median)")
+    if not a.diffusion:
+        return
+    frc = model.forcings
+    for label, dif in (("walls only", None), ("walls and diffusion", (frc.kappa_h, frc.kappa_v, 1e-4 / h))):
+        t1 = time.time()
+        tw = npg.ParticleTracker(model, x0, nsub=1, walls=True, diffusion=dif, seed=1)
+        setup = time.time() - t1
+
+        def walk():
+            L.check(lib.npg_particles_walk(tw.h, tw.fe.h, tw.loc.h, x.h, x.h, 0.0, 1.0, h, 1))
+        wk = timed(ctx, walk, a.reps)
+        st = tw.status
+        print(f"npg_particles_walk(nsub = 1), frozen, {label}, by events: best {wk[0]:.3f} ms, median {wk[1]:.3f} ms of {a.reps} "
+              f"({n / wk[0] / 1e3:.1f} Mparticle-steps/s; {wk[0] / dev[0]:.2f} x npg_particles_advance); after {a.reps + 1} steps "
+              f"{int((st == 0).sum())} alive, {int((st == 1).sum())} lost, {int((st == 2).sum())} stuck, {int(tw.reflections.sum())} "
+              f"reflections; tables and seeds set up in {setup:.1f} s")
 
 
 if __name__ == "__main__":
