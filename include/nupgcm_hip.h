@@ -691,6 +691,36 @@ int npg_particles_download_walk(const npg_particles *P, int32_t *nreflect, uint6
 /* the generator alone: R of n consecutive particle indices from first_index at one step number, out = 3 n doubles */
 int npg_particles_uniforms(npg_ctx *ctx, uint64_t seed, uint64_t first_index, int64_t n, uint64_t step, npg_vec *out);
 
+/* ---- maps on buoyancy surfaces (new work: the reference overlays contour lines of b on slices) ----------------------------------
+ * Where the surfaces B = B_k of the full buoyancy B = N2 z + b' lie over fixed columns (x_j, y_j), and the flow on them
+ * (csrc/surfaces_core.h).  npg_surfaces_create tiles every column into the cells the vertical line passes through,
+ * top to bottom: segments (cell, z_top, z_bot) that abut bit for bit, from the locator's cell records.  A cell's interval is
+ * {z : lambda_i >= 0 for all i}; a constraint that does not depend on z (|d_z lambda_i| <= 1e-12 |grad lambda_i|) is met iff
+ * lambda_i >= -1e-10; intervals no longer than 1e-12 of the box's z extent are dropped; the sweep starts at the highest interval
+ * top and takes, among the intervals that contain the point just below, the one that reaches deepest (ties: the lowest cell id).
+ * It stops at the first gap: a column is its uppermost connected piece.  A column without an interval, or with NaN coordinates, is
+ * dry.  xy[ncol][2] is host memory (copied); the engine and the locator must outlive the handle (one context; a partitioned locator and a
+ * locator of another mesh - an embedded 2-D engine has none - are refused).
+ * npg_surfaces_compute: one thread per column walks its segments once.  Along a segment B is a quadratic in z through its values at
+ * the top (carried from the segment above), the midpoint and the bottom - exact for P2 b', linear for P1 - and "above" means
+ * B - B_k >= 0.  Ends that differ: one crossing; ends that agree: two where the vertex of the parabola lies inside and on the other
+ * side.  out[9][nlev][ncol]: z of the uppermost crossing, z of the lowermost, the number of crossings, and at the uppermost one u_x,
+ * u_y, u_z, d_x B, d_y B, d_z B (evaluated as npg_fe_sample does; N2 added to d_z).  cols[4][ncol]: z_top, z_bot, B at the top, B at
+ * the bottom.  No crossing, or a dry column: NaN (the count is 0).  The same bits on every call.  levels[nlev] is host memory,
+ * finite and strictly increasing.  Validation (NPG_EINVAL + message) happens before anything is launched or written. */
+typedef struct npg_surfaces npg_surfaces;
+#define NPG_NSURF 9
+int npg_surfaces_create(npg_fe *fe, npg_locator *loc, const double *xy, int64_t ncol, npg_surfaces **out);
+int npg_surfaces_destroy(npg_surfaces *S);
+/* the number of segments, the most of one column and the number of dry columns; any may be NULL */
+int npg_surfaces_info(const npg_surfaces *S, int64_t *nseg, int64_t *max_per_col, int64_t *ndry);
+/* per column (host arrays, any may be NULL): z_top, z_bot (NaN where dry) and the number of segments */
+int npg_surfaces_columns(const npg_surfaces *S, double *z_top, double *z_bot, int32_t *nseg);
+/* the segments themselves, column after column (host arrays of npg_surfaces_info's nseg entries, any may be NULL) */
+int npg_surfaces_segments(const npg_surfaces *S, int32_t *cell, double *z_top, double *z_bot);
+int npg_surfaces_compute(npg_surfaces *S, const npg_vec *x_inv, const npg_vec *b, double N2, const double *levels, int nlev,
+                         npg_vec *out, npg_vec *cols);
+
 /* ---- passive tracers carried by the flow (new work: the reference evolves b' alone) -------------------------------------------
  * K scalars stepped with the model's own advection-diffusion operator: the same BDF scheme, the same matrix M + theta (Kh + Kv) and the
  * same velocity extrapolation as b' (csrc/tracers_core.h).  Tracer k has nodal values c (free DoFs in the buoyancy

@@ -170,6 +170,10 @@ def _declare(L, partial=False):
         "npg_particles_set_walls": [P, VP, VP, I64], "npg_particles_set_diffusion": [P, VP, VP, I64, D, U64],
         "npg_particles_walk": [P, P, P, P, P, D, D, D, I64], "npg_particles_download_walk": [P, VP, VP],
         "npg_particles_uniforms": [P, U64, U64, I64, U64, P],
+        "npg_surfaces_create": [P, P, VP, I64, PP], "npg_surfaces_destroy": [P],
+        "npg_surfaces_info": [P, C.POINTER(I64), C.POINTER(I64), C.POINTER(I64)], "npg_surfaces_columns": [P, VP, VP, VP],
+        "npg_surfaces_segments": [P, VP, VP, VP],
+        "npg_surfaces_compute": [P, P, P, D, VP, C.c_int, P, P],
         "npg_tracers_create": [P, C.c_int, PP], "npg_tracers_destroy": [P], "npg_tracers_set": [P, C.c_int, VP, D, D],
         "npg_tracers_rhs": [P, C.c_int, D, D, P, P, P, P, P, P, P],
         "npg_comm_unique_id": [VP], "npg_comm_init": [P, VP, C.c_int, C.c_int],
@@ -231,5 +235,6 @@ NPG_SAMPLE_U, NPG_SAMPLE_P, NPG_SAMPLE_B, NPG_SAMPLE_GRAD_B = 1, 2, 3, 4
 NPG_NINT = 15
 NPG_NCLS = 8
 NPG_NMIX = 8
+NPG_NSURF = 9
 NPG_CG_MULTI_MAX = 32
 NPG_MAT_M, NPG_MAT_KH, NPG_MAT_KV, NPG_MAT_A, NPG_MAT_B = 1, 2, 3, 4, 5

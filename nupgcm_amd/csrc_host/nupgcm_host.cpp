@@ -1936,6 +1936,95 @@ NPG_API int npg_particles_positions(const npg_particles *P, npg_vec *out) {
     return NPG_OK;
 }
 
+// ---- maps on buoyancy surfaces (csrc/surfaces.hip on the host): the tiling of the columns and the scan of one column are the SAME
+// code (csrc/surfaces_core.h), looped over the columns with OpenMP ------------------------------------------------------------------
+#include "../csrc/surfaces_core.h"
+static_assert(NPG_NSURF == npg::kNSurf, "NPG_NSURF of the header and kNSurf of surfaces_core.h must agree");
+
+struct npg_surfaces {
+    npg_ctx *ctx = nullptr;
+    npg_fe *fe = nullptr;
+    npg_locator *loc = nullptr;
+    int64_t ncol = 0;
+    std::vector<double> xy;
+    npg::ColumnTables t;
+};
+
+NPG_API int npg_surfaces_create(npg_fe *fe, npg_locator *loc, const double *xy, int64_t ncol, npg_surfaces **out) {
+    REQUIRE(fe && loc && out && (xy || ncol == 0), "npg_surfaces_create: NULL argument");
+    REQUIRE(ncol >= 0 && ncol <= ((int64_t)1 << 30), "npg_surfaces_create: 0 .. 2^30 columns, got %lld", (long long)ncol);
+    REQUIRE(loc->ctx == fe->ctx, "npg_surfaces_create: arguments of different contexts");
+    REQUIRE(loc->ncell == fe->ncell, "npg_surfaces_create: the locator was built for another mesh (an embedded 2-D engine has no "
+            "locator: buoyancy surfaces need a tetrahedral mesh)");
+    npg_surfaces *S = new npg_surfaces();
+    S->ctx = fe->ctx, S->fe = fe, S->loc = loc, S->ncol = ncol;
+    if (ncol) S->xy.assign(xy, xy + 2 * ncol);
+    const char *err = npg::build_columns(loc->t.geo.data(), loc->ncell, loc->t.grid.lo[2], loc->t.grid.hi[2], xy, ncol, S->t);
+    if (err) {
+        delete S;
+        REQUIRE(false, "%s", err);
+    }
+    *out = S;
+    return NPG_OK;
+}
+NPG_API int npg_surfaces_destroy(npg_surfaces *S) {
+    delete S;
+    return NPG_OK;
+}
+NPG_API int npg_surfaces_info(const npg_surfaces *S, int64_t *nseg, int64_t *max_per_col, int64_t *ndry) {
+    REQUIRE(S, "npg_surfaces_info: NULL handle");
+    if (nseg) *nseg = S->t.col_ptr[(size_t)S->ncol];
+    if (max_per_col) *max_per_col = S->t.max_per_col;
+    if (ndry) *ndry = S->t.ndry;
+    return NPG_OK;
+}
+NPG_API int npg_surfaces_columns(const npg_surfaces *S, double *z_top, double *z_bot, int32_t *nseg) {
+    REQUIRE(S, "npg_surfaces_columns: NULL handle");
+    for (int64_t j = 0; j < S->ncol; ++j) {
+        const int64_t s0 = S->t.col_ptr[(size_t)j], s1 = S->t.col_ptr[(size_t)j + 1];
+        if (z_top) z_top[j] = s1 > s0 ? S->t.seg_ztop[(size_t)s0] : NAN;
+        if (z_bot) z_bot[j] = s1 > s0 ? S->t.seg_zbot[(size_t)s1 - 1] : NAN;
+        if (nseg) nseg[j] = (int32_t)(s1 - s0);
+    }
+    return NPG_OK;
+}
+NPG_API int npg_surfaces_segments(const npg_surfaces *S, int32_t *cell, double *z_top, double *z_bot) {
+    REQUIRE(S, "npg_surfaces_segments: NULL handle");
+    if (cell) std::copy(S->t.seg_cell.begin(), S->t.seg_cell.end(), cell);
+    if (z_top) std::copy(S->t.seg_ztop.begin(), S->t.seg_ztop.end(), z_top);
+    if (z_bot) std::copy(S->t.seg_zbot.begin(), S->t.seg_zbot.end(), z_bot);
+    return NPG_OK;
+}
+NPG_API int npg_surfaces_compute(npg_surfaces *S, const npg_vec *x_inv, const npg_vec *b, double N2, const double *levels, int nlev,
+                                 npg_vec *out, npg_vec *cols) {
+    REQUIRE(S && x_inv && b && out && cols, "npg_surfaces_compute: NULL argument");
+    const char *err = npg::check_levels(levels, nlev, N2);
+    REQUIRE(!err, "npg_surfaces_compute: %s", err);
+    REQUIRE(x_inv->ctx == S->ctx && b->ctx == S->ctx && out->ctx == S->ctx && cols->ctx == S->ctx,
+            "npg_surfaces_compute: arguments of different contexts");
+    const npg_fe *fe = S->fe;
+    REQUIRE(x_inv->n == fe->n_inv, "npg_surfaces_compute: the flow vector has %lld entries, expected %lld", (long long)x_inv->n,
+            (long long)fe->n_inv);
+    REQUIRE(b->n == fe->n_b, "npg_surfaces_compute: the buoyancy vector has %lld entries, expected %lld", (long long)b->n,
+            (long long)fe->n_b);
+    REQUIRE(out->n == (int64_t)npg::kNSurf * nlev * S->ncol && cols->n == (int64_t)npg::kNSurfCol * S->ncol,
+            "npg_surfaces_compute: out must hold %d nlev ncol = %lld and cols %d ncol = %lld entries, got %lld and %lld", npg::kNSurf,
+            (long long)npg::kNSurf * nlev * S->ncol, npg::kNSurfCol, (long long)npg::kNSurfCol * S->ncol, (long long)out->n,
+            (long long)cols->n);
+    const HostTables t{fe, fe->u_diri.data(), fe->b_diri.data(), fe->nb};
+    const npg::SurfaceColumns sc{S->t.col_ptr.data(), S->t.seg_cell.data(), S->t.seg_ztop.data(), S->t.seg_zbot.data(), S->xy.data(),
+                                 S->loc->t.geo.data(), S->ncol};
+    std::vector<int32_t> cross((size_t)nlev * (size_t)S->ncol);
+#pragma omp parallel for schedule(dynamic, 64)
+    for (int64_t j = 0; j < S->ncol; ++j) {
+        if (fe->nb == 10) npg::column_surfaces<10>(sc, t, b->d, N2, levels, nlev, j, out->d, cross.data(), cols->d);
+        else npg::column_surfaces<4>(sc, t, b->d, N2, levels, nlev, j, out->d, cross.data(), cols->d);
+    }
+#pragma omp parallel for schedule(static)
+    for (int64_t o = 0; o < (int64_t)cross.size(); ++o) npg::surface_fields(sc, t, x_inv->d, b->d, N2, nlev, o, cross.data(), out->d);
+    return NPG_OK;
+}
+
 // ---- passive tracers carried by the flow (csrc/tracers.hip on the host): the per-cell arithmetic is the SAME code
 // (csrc/tracers_core.h); pass 2 walks the engine's inverted index in cell order, as gather_rows does. ----------------------------------
 #include "../csrc/tracers_core.h"
