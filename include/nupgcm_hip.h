@@ -576,6 +576,46 @@ int npg_integrals_destroy(npg_integrals *I);
 /* out: NPG_NINT doubles on the device. x_inv = [u; p], b = buoyancy vector. */
 int npg_integrals_compute(npg_integrals *I, const npg_vec *x_inv, const npg_vec *b, int full_stress, npg_vec *out);
 
+/* ---- quadrature integrals of the state over the mesh's BOUNDARY faces (new work: the reference has no boundary diagnostics) -----
+ * Where the model is forced and where it dissipates: wind work, buoyancy flux, drag, pressure against the bottom.  A face is (cell,
+ * local face k = the side lambda_k = 0 of that cell, a group 0 .. ngroup - 1); the fields and their gradients are the CELL's, the
+ * rule is the 9-point face rule of the project's surface load vectors (weights summing to 1/2) lifted into the cell, the measure
+ * qw area2, n the outward unit normal (csrc/boundary_core.h).  NPG_NBND channels per group:
+ *    0  1 (area)          1..3  n (closed boundary: 0)         4  z n_z (closed boundary: the volume)       5  u . n
+ *    6  b'                7  b' u . n                          8  p                9..11  p n                12  p u . n
+ *   13..15  t = nu (grad u) n, or 2 nu sigma n with full_stress = 1               16  u . t
+ *   17  kappa_h (d_x b' n_x + d_y b' n_y) + kappa_v d_z b' n_z                     18  kappa_v n_z
+ *   19  tau_x u_x + tau_y u_y                                  20  F               21  d_z b'                22, 23  u_x, u_y
+ * RAW integrals: the model's prefactors are the caller's.  Always fp64.  Dirichlet nodes count with their values.  nu, kappa_h,
+ * kappa_v (the BACKGROUND value), tau_x, tau_y, F are the caller's values at the face points, tables [9][nface] set by
+ * npg_boundary_set_coeff (copied; NULL removes one; every value finite); a missing table contributes 0.  npg_boundary_set_closure adds
+ * the convection closure of npg_classes_mixing to kappa_v, evaluated from the point's own d_z b' (kappa_c = 0, the default: off, tanh is
+ * not evaluated).
+ * face_xyz[9][nface]: the face's own three nodes, (3 node + axis) major, in the order of the face's sorted vertices;
+ * face_normal[3][nface]; face_area2[nface] = twice the area; face_mask[nface] or NULL: 1 = this face counts.
+ * One lane per face, the faces that count sorted by group (stably: the caller's order within a group) into rows of 256 that hold ONE
+ * group each, one partial row per workgroup, one workgroup per group folds its rows: no atomics, rows that depend on the face counts
+ * alone, one summation order - the same bits on every call.  out[ngroup][NPG_NBND]; faces_out (or NULL) [NPG_NBND][nface]: every
+ * face's own integrals in the caller's order, zeros for a face that does not count.
+ * Validation (NPG_EINVAL + message) happens before anything is launched: NULL arguments, vector lengths, face_cell out of range,
+ * face_local > 3, face_group >= ngroup, ngroup outside 1 .. 8, non-finite geometry, full_stress not 0 or 1, an embedded 2-D engine.
+ * nface = 0, a mask that leaves nothing or an empty group give zeros for that group.  The engine must outlive the handle. */
+typedef struct npg_boundary npg_boundary;
+#define NPG_NBND 24
+#define NPG_BND_NU 0
+#define NPG_BND_KH 1
+#define NPG_BND_KV 2
+#define NPG_BND_TAUX 3
+#define NPG_BND_TAUY 4
+#define NPG_BND_FLUX 5
+int npg_boundary_create(npg_fe *fe, int64_t nface, const int32_t *face_cell, const uint8_t *face_local, const uint8_t *face_group,
+                        int ngroup, const double *face_xyz, const double *face_normal, const double *face_area2,
+                        const uint8_t *face_mask, npg_boundary **out);
+int npg_boundary_set_coeff(npg_boundary *B, int which, const double *table);
+int npg_boundary_set_closure(npg_boundary *B, double kappa_c, double N2min, double alpha, double N2c);
+int npg_boundary_compute(npg_boundary *B, const npg_vec *x_inv, const npg_vec *b, int full_stress, npg_vec *out, npg_vec *faces_out);
+int npg_boundary_destroy(npg_boundary *B);
+
 /* ---- the state binned into (latitude band, buoyancy class) (new work: the reference overlays isopycnals on a z-coordinate psi) --
  * A joint table [ny + 1][nb + 1][NPG_NCLS] over the cells of the mesh (csrc/classes_core.h).
  * Sample rule - NOT the engine's quadrature (Keast's rule has a negative weight): ns barycentric points rule_lam[ns][4] with weights

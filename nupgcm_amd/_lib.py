@@ -161,6 +161,9 @@ def _declare(L, partial=False):
         "npg_located_download": [P, VP, VP], "npg_locator_find": [P, P, I64, P], "npg_fe_sample": [P, C.c_int, P, P, P],
         "npg_fe_grid_integrals": [P, P, P, P, D, P, I64, I64, I64, P, P],
         "npg_integrals_create": [P, VP, VP, PP], "npg_integrals_destroy": [P], "npg_integrals_compute": [P, P, P, C.c_int, P],
+        "npg_boundary_create": [P, I64, VP, VP, VP, C.c_int, VP, VP, VP, VP, PP], "npg_boundary_destroy": [P],
+        "npg_boundary_set_coeff": [P, C.c_int, VP], "npg_boundary_set_closure": [P, D, D, D, D],
+        "npg_boundary_compute": [P, P, P, C.c_int, P, P],
         "npg_classes_create": [P, VP, VP, VP, VP, VP, C.c_int, VP, I64, VP, I64, PP], "npg_classes_destroy": [P],
         "npg_classes_compute": [P, P, P, D, P, P],
         "npg_classes_set_diffusivity": [P, VP, D, VP, D], "npg_classes_mixing": [P, P, D, D, D, D, D, P, P],
@@ -233,6 +236,8 @@ NPG_BDF1, NPG_BDF2 = 1, 2
 NPG_FE_FP64, NPG_FE_FP32 = 0, 1
 NPG_SAMPLE_U, NPG_SAMPLE_P, NPG_SAMPLE_B, NPG_SAMPLE_GRAD_B = 1, 2, 3, 4
 NPG_NINT = 15
+NPG_NBND = 24
+NPG_BND_NU, NPG_BND_KH, NPG_BND_KV, NPG_BND_TAUX, NPG_BND_TAUY, NPG_BND_FLUX = range(6)
 NPG_NCLS = 8
 NPG_NMIX = 8
 NPG_NSURF = 9

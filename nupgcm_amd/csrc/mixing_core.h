@@ -32,6 +32,12 @@ struct MixClosure {
     double kappa_c, N2min, alpha, N2c;
 };
 
+// the closure's part of kappa_v where d_z b' = bz (called with cl.kappa_c > 0 only); boundary_core.h evaluates the same expression
+NPG_HD double closure_kappa(const MixClosure &cl, double bz) {
+    const double a = cl.alpha * (cl.N2c + bz);
+    return cl.kappa_c * (1.0 + tanh(-a / cl.N2min)) / 2.0;
+}
+
 // the nodal values of one cell: ClassCell without the velocity
 template <int NB>
 struct MixCell {
@@ -76,8 +82,7 @@ NPG_UNROLL
     const double gz = bz + N2;
     double kc = 0.0, kv = kv0;
     if (cl.kappa_c > 0.0) {
-        const double a = cl.alpha * (cl.N2c + bz);
-        kc = cl.kappa_c * (1.0 + tanh(-a / cl.N2min)) / 2.0;
+        kc = closure_kappa(cl, bz);
         kv = kv0 + kc;
     }
     const double gh2 = gx * gx + gy * gy;

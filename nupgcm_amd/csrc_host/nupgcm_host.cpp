@@ -1451,6 +1451,151 @@ NPG_API int npg_integrals_compute(npg_integrals *I, const npg_vec *x_inv, const 
     return NPG_OK;
 }
 
+// ---- quadrature integrals of the state over the mesh's boundary faces (csrc/boundary.hip on the host): the per-face arithmetic, the
+// validation, the sort by group and the rows of kBndChunk faces are the SAME code (csrc/boundary_core.h).  One partial row per row of
+// faces, a group's rows folded in index order: the sums do not depend on the number of threads. ------------------------------------------
+#include "../csrc/boundary_core.h"
+static_assert(NPG_NBND == npg::kNBnd, "NPG_NBND of the header and kNBnd of boundary_core.h must agree");
+static_assert(NPG_BND_NU == npg::kBndNu && NPG_BND_KH == npg::kBndKh && NPG_BND_KV == npg::kBndKv && NPG_BND_TAUX == npg::kBndTauX &&
+                  NPG_BND_TAUY == npg::kBndTauY && NPG_BND_FLUX == npg::kBndFlux,
+              "the coefficient codes of the header and of boundary_core.h must agree");
+
+struct npg_boundary {
+    npg_fe *fe = nullptr;
+    int64_t nface = 0;
+    int ngroup = 0;
+    npg::BndLayout lay;
+    npg::BndShape shape;
+    npg::MixClosure cl{0.0, 0.0, 0.0, 0.0};
+    std::vector<int32_t> cell;               // the faces that count, sorted: [nkept]
+    std::vector<uint8_t> local;
+    std::vector<double> area2, normal, z;    // [nkept], [3][nkept], [3][nkept]
+    std::vector<double> coef[npg::kBndNCoef];   // [9][nkept] or empty
+    std::vector<double> part;                // [nrows][NPG_NBND]
+};
+namespace {
+struct HostFaces {       // the sorted face tables and the engine's cell tables as face_integrals reads them
+    const npg_boundary *B;
+    const npg_fe *fe;
+    size_t nk;           // faces that count
+    int64_t cell(int64_t f) const { return B->cell[(size_t)f]; }
+    int local(int64_t f) const { return B->local[(size_t)f]; }
+    double area2(int64_t f) const { return B->area2[(size_t)f]; }
+    double n(int a, int64_t f) const { return B->normal[(size_t)a * nk + f]; }
+    double z(int j, int64_t f) const { return B->z[(size_t)j * nk + f]; }
+    bool has(int i) const { return !B->coef[i].empty(); }
+    double coef(int i, int q, int64_t f) const { return B->coef[i][(size_t)q * nk + f]; }
+    double G(int k, int64_t c) const { return fe->G[(size_t)c * 12 + k]; }
+    double u(const double *x, int l, int64_t c) const { return fval(x, fe->u_diri, fe->cu[(size_t)c * 30 + l]); }
+    double p(const double *x, int m, int64_t c) const {
+        const int32_t i = fe->cp[(size_t)c * 4 + m];
+        return i >= 0 ? x[i] : 0.0;          // the pinned vertex of the zero-mean space
+    }
+    double b(const double *x, int i, int64_t c) const { return fval(x, fe->b_diri, fe->cb[(size_t)c * fe->nb + i]); }
+};
+}  // namespace
+
+NPG_API int npg_boundary_create(npg_fe *fe, int64_t nface, const int32_t *face_cell, const uint8_t *face_local, const uint8_t *face_group,
+                                int ngroup, const double *face_xyz, const double *face_normal, const double *face_area2,
+                                const uint8_t *face_mask, npg_boundary **out) {
+    REQUIRE(fe && out, "npg_boundary_create: NULL argument");
+    {   // an embedded 2-D engine keeps every quadrature point on the face lambda_4 = 0 of its padded tetrahedra: it has no boundary faces
+        bool flat = true;
+        for (int q = 0; q < fe->nq; ++q) flat = flat && fe->N1[(size_t)q * 4 + 3] == 0.0;
+        REQUIRE(!flat, "npg_boundary_create: an embedded 2-D engine is refused (its boundary is made of segments, not of faces)");
+    }
+    npg_boundary *B = new npg_boundary();
+    const std::string err = npg::bnd_build_layout(fe->ncell, nface, face_cell, face_local, face_group, ngroup, face_xyz, face_normal,
+                                                  face_area2, face_mask, B->lay);
+    if (!err.empty()) {
+        delete B;
+        REQUIRE(false, "%s", err.c_str());
+    }
+    B->fe = fe;
+    B->nface = nface;
+    B->ngroup = ngroup;
+    npg::bnd_shape_tables(B->shape);
+    const size_t n = B->lay.orig.size();
+    B->cell.resize(n), B->local.resize(n), B->area2.resize(n), B->normal.resize(3 * n), B->z.resize(3 * n);
+    for (size_t i = 0; i < n; ++i) {
+        const size_t f = (size_t)B->lay.orig[i];
+        B->cell[i] = face_cell[f], B->local[i] = face_local[f], B->area2[i] = face_area2[f];
+        for (int a = 0; a < 3; ++a)
+            B->normal[a * n + i] = face_normal[(size_t)a * nface + f], B->z[a * n + i] = face_xyz[(size_t)(3 * a + 2) * nface + f];
+    }
+    B->part.assign(B->lay.rows.size() * NPG_NBND, 0.0);
+    *out = B;
+    return NPG_OK;
+}
+NPG_API int npg_boundary_destroy(npg_boundary *B) {
+    delete B;
+    return NPG_OK;
+}
+NPG_API int npg_boundary_set_coeff(npg_boundary *B, int which, const double *table) {
+    REQUIRE(B, "npg_boundary_set_coeff: NULL argument");
+    REQUIRE(which >= 0 && which < npg::kBndNCoef, "npg_boundary_set_coeff: which must be NPG_BND_NU .. NPG_BND_FLUX, got %d", which);
+    const size_t n = B->lay.orig.size();
+    std::vector<double> t;
+    if (table) {
+        t.resize(npg::kBndQ * n);
+        for (int q = 0; q < npg::kBndQ; ++q)
+            for (size_t i = 0; i < n; ++i) {
+                const double v = table[(size_t)q * B->nface + B->lay.orig[i]];
+                REQUIRE(std::isfinite(v), "npg_boundary_set_coeff: table %d is not finite at point %d of face %d", which, q, B->lay.orig[i]);
+                t[q * n + i] = v;
+            }
+    }
+    B->coef[which].swap(t);
+    return NPG_OK;
+}
+NPG_API int npg_boundary_set_closure(npg_boundary *B, double kappa_c, double N2min, double alpha, double N2c) {
+    REQUIRE(B, "npg_boundary_set_closure: NULL argument");
+    REQUIRE(std::isfinite(kappa_c) && kappa_c >= 0.0 && std::isfinite(N2min) && std::isfinite(alpha) && std::isfinite(N2c),
+            "npg_boundary_set_closure: kappa_c must be finite and >= 0, N2min, alpha and N2c finite");
+    REQUIRE(kappa_c == 0.0 || N2min > 0.0, "npg_boundary_set_closure: kappa_c > 0 needs N2min > 0, got %g", N2min);
+    B->cl = npg::MixClosure{kappa_c, N2min, alpha, N2c};
+    return NPG_OK;
+}
+NPG_API int npg_boundary_compute(npg_boundary *B, const npg_vec *x_inv, const npg_vec *b, int full_stress, npg_vec *out, npg_vec *faces_out) {
+    REQUIRE(B && x_inv && b && out, "npg_boundary_compute: NULL argument");
+    const npg_fe *fe = B->fe;
+    REQUIRE(x_inv->n == fe->n_inv, "npg_boundary_compute: the flow vector has %lld entries, expected %lld", (long long)x_inv->n,
+            (long long)fe->n_inv);
+    REQUIRE(b->n == fe->n_b, "npg_boundary_compute: the buoyancy vector has %lld entries, expected %lld", (long long)b->n, (long long)fe->n_b);
+    REQUIRE(out->n >= (int64_t)B->ngroup * NPG_NBND, "npg_boundary_compute: out holds %lld doubles, needs ngroup * NPG_NBND = %d",
+            (long long)out->n, B->ngroup * NPG_NBND);
+    REQUIRE(!faces_out || faces_out->n >= B->nface * NPG_NBND, "npg_boundary_compute: faces_out holds %lld doubles, needs NPG_NBND * nface = %lld",
+            (long long)faces_out->n, (long long)(B->nface * NPG_NBND));
+    REQUIRE(full_stress == 0 || full_stress == 1, "npg_boundary_compute: full_stress must be 0 or 1, got %d", full_stress);
+    const HostFaces t{B, fe, B->lay.orig.size()};
+    const int64_t nrows = (int64_t)B->lay.rows.size();
+    double *fo = faces_out ? faces_out->d : nullptr;
+    if (fo) std::fill(fo, fo + B->nface * NPG_NBND, 0.0);      // faces that do not count keep zeros
+#pragma omp parallel for schedule(static)
+    for (int64_t r = 0; r < nrows; ++r) {
+        const npg::BndRow row = B->lay.rows[(size_t)r];
+        double sum[NPG_NBND];
+        for (int a = 0; a < NPG_NBND; ++a) sum[a] = 0.0;
+        for (int64_t f = row.first; f < row.first + row.count; ++f) {
+            double acc[NPG_NBND];
+            for (int a = 0; a < NPG_NBND; ++a) acc[a] = 0.0;
+            if (fe->nb == 10) npg::face_integrals<10>(B->shape, t, x_inv->d, b->d, f, full_stress != 0, B->cl, acc);
+            else npg::face_integrals<4>(B->shape, t, x_inv->d, b->d, f, full_stress != 0, B->cl, acc);
+            for (int a = 0; a < NPG_NBND; ++a) sum[a] += acc[a];
+            if (fo)
+                for (int a = 0; a < NPG_NBND; ++a) fo[(size_t)a * B->nface + B->lay.orig[(size_t)f]] = acc[a];
+        }
+        for (int a = 0; a < NPG_NBND; ++a) B->part[(size_t)r * NPG_NBND + a] = sum[a];
+    }
+    for (int g = 0; g < B->ngroup; ++g)
+        for (int a = 0; a < NPG_NBND; ++a) {
+            double sum = 0.0;
+            for (int64_t r = B->lay.row0[g]; r < B->lay.row0[g + 1]; ++r) sum += B->part[(size_t)r * NPG_NBND + a];
+            out->d[(size_t)g * NPG_NBND + a] = sum;
+        }
+    return NPG_OK;
+}
+
 // ---- the state binned into (latitude band, buoyancy class) (csrc/classes.hip on the host): the per-sample arithmetic and the edge
 // search are the SAME code (csrc/classes_core.h).  Pass 1 in fixed chunks of kClsChunk cells, folded in chunk order; pass 2 adds the
 // quantised terms as 64-bit integers (relaxed atomics on one table, a run of samples in one bin added up first): integer addition is
