@@ -31,34 +31,7 @@ constexpr int kBndBlock = kBndChunk;        // one face per lane, one partial ro
 static_assert(kBndBlock % kWave == 0 && kBndBlock <= 1024, "whole waves");
 constexpr int kBndFoldSlices = kBlock / kPartStride;
 
-// the sorted face tables as face_integrals reads them ([component][face], unit stride over the faces of a workgroup)
-struct BndFaces {
-    FeDev d;
-    int64_t nk;                  // faces that count
-    const int32_t *cell_;
-    const uint8_t *local_;
-    const double *area2_, *normal_, *z_;
-    const double *coef_[kBndNCoef];
-    __device__ __forceinline__ int64_t cell(int64_t f) const { return cell_[f]; }
-    __device__ __forceinline__ int local(int64_t f) const { return local_[f]; }
-    __device__ __forceinline__ double area2(int64_t f) const { return area2_[f]; }
-    __device__ __forceinline__ double n(int a, int64_t f) const { return normal_[(size_t)a * n_() + f]; }
-    __device__ __forceinline__ double z(int j, int64_t f) const { return z_[(size_t)j * n_() + f]; }
-    __device__ __forceinline__ bool has(int i) const { return coef_[i] != nullptr; }
-    __device__ __forceinline__ double coef(int i, int q, int64_t f) const { return coef_[i][(size_t)q * n_() + f]; }
-    __device__ __forceinline__ double G(int k, int64_t c) const { return d.G[(size_t)k * d.ncell + c]; }
-    __device__ __forceinline__ double u(const double *x, int l, int64_t c) const {
-        return field_val(x, d.u_diri, d.cu[(size_t)l * d.ncell + c]);
-    }
-    __device__ __forceinline__ double p(const double *x, int m, int64_t c) const {
-        const int32_t i = d.cp[(size_t)m * d.ncell + c];
-        return i >= 0 ? x[i] : 0.0;                          // the pinned vertex of the zero-mean space
-    }
-    __device__ __forceinline__ double b(const double *x, int i, int64_t c) const {
-        return field_val(x, d.b_diri, d.cb[(size_t)i * d.ncell + c]);
-    }
-    __device__ __forceinline__ size_t n_() const { return (size_t)nk; }
-};
+using BndFaces = FaceTables<DevCells>;
 
 // the face shape tables into LDS, as stage_tables does for the engine's
 __device__ __forceinline__ void stage_face_tables(const BndShape *__restrict__ g, BndShape &t) {
@@ -121,33 +94,21 @@ struct npg_boundary {
     BndLayout lay;                      // host: the sort and the rows
     BndRowRange rr{};
     MixClosure cl{0.0, 0.0, 0.0, 0.0};
-    int32_t *cell = nullptr, *orig = nullptr;      // device, sorted faces
-    uint8_t *local = nullptr;
-    double *area2 = nullptr, *normal = nullptr, *z = nullptr;       // [nkept], [3][nkept], [3][nkept]
-    double *coef[kBndNCoef] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [9][nkept] or null
-    BndShape *shape = nullptr;
-    BndRow *rows = nullptr;
-    double *part = nullptr;             // [nrows][kPartStride]
+    DevBuf<int32_t> cell, orig;         // device, sorted faces
+    DevBuf<uint8_t> local;
+    DevBuf<double> area2, normal, z;    // [nkept], [3][nkept], [3][nkept]
+    DevBuf<double> coef[kBndNCoef];     // [9][nkept] or null
+    DevBuf<BndShape> shape;
+    DevBuf<BndRow> rows;
+    DevBuf<double> part;                // [nrows][kPartStride]
 };
 
 NPG_API int npg_boundary_destroy(npg_boundary *B) {
     if (!B) return NPG_OK;
     hipStreamSynchronize(B->ctx->stream);
-    hipFree(B->cell), hipFree(B->orig), hipFree(B->local), hipFree(B->area2), hipFree(B->normal), hipFree(B->z);
-    for (double *c : B->coef) hipFree(c);
-    hipFree(B->shape), hipFree(B->rows), hipFree(B->part);
     delete B;
     return NPG_OK;
 }
-
-namespace {
-template <class T>
-hipError_t upload(T **dst, const std::vector<T> &src) {
-    if (src.empty()) return hipSuccess;
-    hipError_t e = hipMalloc((void **)dst, src.size() * sizeof(T));
-    return e == hipSuccess ? hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice) : e;
-}
-}  // namespace
 
 NPG_API int npg_boundary_create(npg_fe *fe, int64_t nface, const int32_t *face_cell, const uint8_t *face_local, const uint8_t *face_group,
                                 int ngroup, const double *face_xyz, const double *face_normal, const double *face_area2,
@@ -161,13 +122,9 @@ NPG_API int npg_boundary_create(npg_fe *fe, int64_t nface, const int32_t *face_c
         for (int q = 0; q < fe->d.nq; ++q) flat = flat && n1[(size_t)q * 4 + 3] == 0.0;
         NPG_REQUIRE(!flat, "npg_boundary_create: an embedded 2-D engine is refused (its boundary is made of segments, not of faces)");
     }
-    npg_boundary *B = new npg_boundary();
-    const std::string err = bnd_build_layout(fe->d.ncell, nface, face_cell, face_local, face_group, ngroup, face_xyz, face_normal, face_area2,
-                                             face_mask, B->lay);
-    if (!err.empty()) {
-        delete B;
-        NPG_REQUIRE(false, "%s", err.c_str());
-    }
+    std::unique_ptr<npg_boundary> B(new npg_boundary());
+    NPG_REQUIRE_OK(bnd_build_layout(fe->d.ncell, nface, face_cell, face_local, face_group, ngroup, face_xyz, face_normal, face_area2, face_mask,
+                                    B->lay));
     B->ctx = fe->ctx;
     B->fe = fe;
     B->nface = nface;
@@ -186,20 +143,16 @@ NPG_API int npg_boundary_create(npg_fe *fe, int64_t nface, const int32_t *face_c
     }
     std::vector<BndShape> shape(1);
     bnd_shape_tables(shape[0]);
-    hipError_t e = upload(&B->cell, cell);
-    if (e == hipSuccess) e = upload(&B->orig, B->lay.orig);
-    if (e == hipSuccess) e = upload(&B->local, local);
-    if (e == hipSuccess) e = upload(&B->area2, area2);
-    if (e == hipSuccess) e = upload(&B->normal, normal);
-    if (e == hipSuccess) e = upload(&B->z, z);
-    if (e == hipSuccess) e = upload(&B->shape, shape);
-    if (e == hipSuccess) e = upload(&B->rows, B->lay.rows);
-    if (e == hipSuccess && B->nrows) e = hipMalloc((void **)&B->part, (size_t)B->nrows * kPartStride * sizeof(double));
-    if (e != hipSuccess) {
-        npg_boundary_destroy(B);
-        NPG_HIP(e);
-    }
-    *out = B;
+    NPG_HIP(B->cell.upload(cell));
+    NPG_HIP(B->orig.upload(B->lay.orig));
+    NPG_HIP(B->local.upload(local));
+    NPG_HIP(B->area2.upload(area2));
+    NPG_HIP(B->normal.upload(normal));
+    NPG_HIP(B->z.upload(z));
+    NPG_HIP(B->shape.upload(shape));
+    NPG_HIP(B->rows.upload(B->lay.rows));
+    NPG_HIP(B->part.alloc((size_t)B->nrows * kPartStride));
+    *out = B.release();
     return NPG_OK;
 }
 
@@ -219,9 +172,7 @@ NPG_API int npg_boundary_set_coeff(npg_boundary *B, int which, const double *tab
     }
     NPG_HIP(hipSetDevice(B->ctx->device));
     NPG_HIP(hipStreamSynchronize(B->ctx->stream));          // a compute still in flight reads the table this call replaces
-    hipFree(B->coef[which]);
-    B->coef[which] = nullptr;
-    NPG_HIP(upload(&B->coef[which], t));
+    NPG_HIP(B->coef[which].upload(t));
     return NPG_OK;
 }
 
@@ -237,10 +188,7 @@ NPG_API int npg_boundary_set_closure(npg_boundary *B, double kappa_c, double N2m
 NPG_API int npg_boundary_compute(npg_boundary *B, const npg_vec *x_inv, const npg_vec *b, int full_stress, npg_vec *out, npg_vec *faces_out) {
     NPG_REQUIRE(B && x_inv && b && out, "npg_boundary_compute: NULL argument");
     npg_fe *fe = B->fe;
-    NPG_REQUIRE(x_inv->n == fe->n_inv, "npg_boundary_compute: the flow vector has %lld entries, expected %lld", (long long)x_inv->n,
-                (long long)fe->n_inv);
-    NPG_REQUIRE(b->n == fe->n_b, "npg_boundary_compute: the buoyancy vector has %lld entries, expected %lld", (long long)b->n,
-                (long long)fe->n_b);
+    NPG_REQUIRE_OK(check_state_vectors("npg_boundary_compute", fe->n_inv, fe->n_b, x_inv->n, b->n));
     NPG_REQUIRE(out->n >= (int64_t)B->ngroup * NPG_NBND, "npg_boundary_compute: out holds %lld doubles, needs ngroup * NPG_NBND = %d",
                 (long long)out->n, B->ngroup * NPG_NBND);
     NPG_REQUIRE(!faces_out || faces_out->n >= B->nface * NPG_NBND, "npg_boundary_compute: faces_out holds %lld doubles, needs NPG_NBND * nface = %lld",
@@ -253,19 +201,19 @@ NPG_API int npg_boundary_compute(npg_boundary *B, const npg_vec *x_inv, const np
     if (faces_out && B->nface > 0)      // faces that do not count keep zeros
         NPG_HIP(hipMemsetAsync(faces_out->d, 0, (size_t)B->nface * NPG_NBND * sizeof(double), st));
     if (B->nrows > 0) {
-        BndFaces t{fe->d, B->nkept, B->cell, B->local, B->area2, B->normal, B->z, {}};
+        BndFaces t{cell_view(fe->d), B->nkept, B->cell, B->local, B->area2, B->normal, B->z, {}};
         for (int i = 0; i < kBndNCoef; ++i) t.coef_[i] = B->coef[i];
         const dim3 grid((unsigned)B->nrows), block(kBndBlock);
         double *fo = faces_out ? faces_out->d : nullptr;
         if (fe->d.nb == 10)
-            hipLaunchKernelGGL(k_boundary_faces<10>, grid, block, 0, st, t, B->shape, B->rows, B->orig, x_inv->d, b->d, full_stress, B->cl,
-                               B->part, fo, B->nface);
+            hipLaunchKernelGGL(k_boundary_faces<10>, grid, block, 0, st, t, B->shape.p, B->rows.p, B->orig.p, x_inv->d, b->d, full_stress, B->cl,
+                               B->part.p, fo, B->nface);
         else
-            hipLaunchKernelGGL(k_boundary_faces<4>, grid, block, 0, st, t, B->shape, B->rows, B->orig, x_inv->d, b->d, full_stress, B->cl,
-                               B->part, fo, B->nface);
+            hipLaunchKernelGGL(k_boundary_faces<4>, grid, block, 0, st, t, B->shape.p, B->rows.p, B->orig.p, x_inv->d, b->d, full_stress, B->cl,
+                               B->part.p, fo, B->nface);
         NPG_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_boundary_fold, dim3((unsigned)B->ngroup), dim3(kBlock), 0, st, B->part, B->rr, out->d);
+    hipLaunchKernelGGL(k_boundary_fold, dim3((unsigned)B->ngroup), dim3(kBlock), 0, st, B->part.p, B->rr, out->d);
     NPG_HIP(hipGetLastError());
     return NPG_OK;
 }

@@ -94,6 +94,23 @@ inline void bnd_shape_tables(BndShape &s) {
         }
 }
 
+// the engine's cell tables and the sorted face tables ([component][face] in both libraries, unit stride over the faces of a row)
+template <class View>
+struct FaceTables : View {
+    int64_t nk;                  // faces that count
+    const int32_t *cell_;
+    const uint8_t *local_;
+    const double *area2_, *normal_, *z_;       // [nk], [3][nk], [3][nk]
+    const double *coef_[kBndNCoef];            // [9][nk] or null
+    NPG_HD int64_t cell(int64_t f) const { return cell_[f]; }
+    NPG_HD int local(int64_t f) const { return local_[f]; }
+    NPG_HD double area2(int64_t f) const { return area2_[f]; }
+    NPG_HD double n(int a, int64_t f) const { return normal_[(size_t)a * (size_t)nk + f]; }
+    NPG_HD double z(int j, int64_t f) const { return z_[(size_t)j * (size_t)nk + f]; }
+    NPG_HD bool has(int i) const { return coef_[i] != nullptr; }
+    NPG_HD double coef(int i, int q, int64_t f) const { return coef_[i][(size_t)q * (size_t)nk + f]; }
+};
+
 template <int NB, class S, class T>
 NPG_HD void face_integrals(const S &s, const T &t, const double *xu, const double *xb, int64_t f, bool full_stress, const MixClosure &cl,
                            double acc[kNBnd]) {

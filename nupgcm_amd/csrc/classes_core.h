@@ -120,11 +120,84 @@ NPG_UNROLL
 // a term in units of 1 / scale, rounded to nearest (ties to even, the default mode); scale = 0 (class_scale of a non-finite sum): 0
 NPG_HD int64_t class_quantise(double term, double scale) { return scale != 0.0 ? (int64_t)llrint(term * scale) : 0; }
 
+// the rule and the edges: lam[ns][4], wq[ns] = w[s] qsum, y_edges[ny], b_edges[nb]
+struct ClsRule {
+    const double *lam, *wq, *y_edges, *b_edges;
+    int ns;
+    int64_t ny, nb;
+};
+
+// A SAMPLER is what the two passes of a class table (classes.hip: k_class_scan / k_class_bin; the host library: class_cell) are
+// written over: the nodal values Cell<NB> of one cell, load() that fills them from the cell tables t, and sample<NB, QUANT>() that
+// gives the terms of sample s of cell c and - QUANT - its band and class, or false (dropped).  It carries its own inputs.
+// The census: the flow, the buoyancy and the binning N2.
+struct CensusSampler {
+    const double *xu, *xb;
+    double N2;
+    template <int NB>
+    using Cell = ClassCell<NB>;
+    template <int NB, class T>
+    NPG_HD void load(const T &t, int64_t c, ClassCell<NB> &n) const {
+        class_cell_load<NB>(t, xu, xb, c, n);
+    }
+    template <int NB, bool QUANT, class T>
+    NPG_HD bool sample(const T &, const ClassCell<NB> &n, const ClsRule &r, int s, int64_t, int64_t *band, int64_t *cls,
+                       double term[kNCls]) const {
+        return class_sample<NB, QUANT>(n, r.lam + 4 * s, r.wq[s], N2, r.y_edges, r.ny, r.b_edges, r.nb, band, cls, term);
+    }
+};
+
 // nullptr if e[0 .. n) is usable as bin edges: finite and strictly increasing (n = 0 is: one open bin)
 inline const char *check_edges(const double *e, int64_t n) {
     for (int64_t i = 0; i < n; ++i)
         if (!std::isfinite(e[i]) || (i > 0 && !(e[i] > e[i - 1]))) return "must be finite and strictly increasing";
     return nullptr;
+}
+
+// The argument checks of the entry points, for both libraries (the message, empty: fine).  handles = "fe and out are not NULL".
+inline std::string check_classes_create(bool handles, int64_t ncell, const double *cell_y, const double *cell_z, const double *rule_lam,
+                                        const double *rule_w, int ns, const double *y_edges, int64_t ny, const double *b_edges, int64_t nb) {
+    if (!handles) return "npg_classes_create: NULL argument";
+    if (!(cell_y && cell_z)) return "npg_classes_create: cell_y or cell_z is NULL";
+    if (!(ns >= 1 && ns <= kClsMaxSamples)) return msgf("npg_classes_create: 1 .. %d samples per cell, got %d", kClsMaxSamples, ns);
+    if (!(rule_lam && rule_w)) return "npg_classes_create: rule_lam or rule_w is NULL";
+    if (!(ny >= 0 && nb >= 0 && (ny == 0 || y_edges) && (nb == 0 || b_edges))) return "npg_classes_create: edges missing or a negative count";
+    if (!(ny < kClsMaxBins && nb < kClsMaxBins && (ny + 1) * (nb + 1) <= kClsMaxBins))
+        return msgf("npg_classes_create: ny = %lld and nb = %lld give more than 2^22 bins (ny + 1)(nb + 1)", (long long)ny, (long long)nb);
+    const char *err = check_edges(y_edges, ny);
+    if (err) return msgf("npg_classes_create: y_edges %s", err);
+    err = check_edges(b_edges, nb);
+    if (err) return msgf("npg_classes_create: b_edges %s", err);
+    double wsum = 0.0;
+    for (int s = 0; s < ns; ++s) {
+        if (!(rule_w[s] > 0.0 && std::isfinite(rule_w[s]))) return msgf("npg_classes_create: weight %d of the rule is not > 0", s);
+        wsum += rule_w[s];
+        const double *l = rule_lam + 4 * s;
+        if (!(std::fabs((l[0] + l[1]) + (l[2] + l[3]) - 1.0) <= 1e-12)) return msgf("npg_classes_create: lam row %d of the rule does not sum to 1", s);
+    }
+    if (!(std::fabs(wsum - 1.0) <= 1e-12)) return msgf("npg_classes_create: the weights of the rule sum to %.17g, not 1", wsum);
+    for (int64_t k = 0; k < ncell * 4; ++k) {
+        if (!std::isfinite(cell_y[k])) return msgf("npg_classes_create: cell_y[%lld][%d] is not finite", (long long)(k / 4), (int)(k % 4));
+        if (!std::isfinite(cell_z[k])) return msgf("npg_classes_create: cell_z[%lld][%d] is not finite", (long long)(k / 4), (int)(k % 4));
+    }
+    return "";
+}
+
+// K: the handle (nbins, its engine fe with n_inv, n_b, ctx); the vectors carry n and ctx
+template <class H, class V>
+std::string check_classes_compute(const H *K, const V *x_inv, const V *b, double N2, const V *table, const V *info) {
+    if (!(K && x_inv && b && table && info)) return "npg_classes_compute: NULL argument";
+    const auto *fe = K->fe;
+    const std::string err = check_state_vectors("npg_classes_compute", fe->n_inv, fe->n_b, x_inv->n, b->n);
+    if (!err.empty()) return err;
+    if (table->n < K->nbins * kNCls)
+        return msgf("npg_classes_compute: table holds %lld doubles, needs (ny + 1)(nb + 1) NPG_NCLS = %lld", (long long)table->n,
+                    (long long)(K->nbins * kNCls));
+    if (info->n < 1 + kNCls) return msgf("npg_classes_compute: info holds %lld doubles, needs 1 + NPG_NCLS = %d", (long long)info->n, 1 + kNCls);
+    if (!std::isfinite(N2)) return "npg_classes_compute: N2 is not finite";
+    if (!(x_inv->ctx == fe->ctx && b->ctx == fe->ctx && table->ctx == fe->ctx && info->ctx == fe->ctx))
+        return "npg_classes_compute: arguments of different contexts";
+    return "";
 }
 
 }  // namespace npg

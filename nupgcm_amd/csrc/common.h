@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -36,6 +37,43 @@ NPG_SHARED void set_error(const char *fmt, ...);
             return NPG_EINVAL;              \
         }                                   \
     } while (0)
+
+// report the message of a shared argument check (the *_core.h check_* functions; empty: fine)
+#define NPG_REQUIRE_OK(msg)                              \
+    do {                                                 \
+        const std::string m_ = (msg);                    \
+        NPG_REQUIRE(m_.empty(), "%s", m_.c_str());       \
+    } while (0)
+
+// A device array owned by a diagnostic's handle: freed with the handle, never copied.  Every call returns the HIP error, so a
+// create is a straight line of NPG_HIP(...) over a handle held by a std::unique_ptr.  n = 0 allocates nothing (null pointer).
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { hipFree(p); }
+    operator T *() const { return p; }
+    void reset() {
+        hipFree(p);
+        p = nullptr;
+    }
+    void swap(DevBuf &o) { std::swap(p, o.p); }
+    hipError_t alloc(size_t n) {
+        reset();
+        return n ? hipMalloc((void **)&p, n * sizeof(T)) : hipSuccess;
+    }
+    hipError_t zeros(size_t n) {
+        const hipError_t e = alloc(n);
+        return e == hipSuccess && n ? hipMemset(p, 0, n * sizeof(T)) : e;
+    }
+    hipError_t upload(const T *src, size_t n) {
+        const hipError_t e = alloc(n);
+        return e == hipSuccess && n ? hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice) : e;
+    }
+    hipError_t upload(const std::vector<T> &src) { return upload(src.data(), src.size()); }
+};
 
 // environment switches: the integer value of `name`, `dflt` where it is not set
 inline int env_int(const char *name, int dflt) {

@@ -1,6 +1,7 @@
 // The element engine's device tables and handle, shared by the translation units that read them (fe.hip: assembly; sample.hip:
 // point evaluation of the state; integrals.hip: quadrature integrals of the state), and the shape tables they stage in LDS.
 #pragma once
+#include "cell_view.h"
 #include "common.h"
 
 namespace npg {
@@ -46,8 +47,10 @@ __device__ __forceinline__ void stage_tables(const FeDev &d, FeTablesT<R> &t) {
     __syncthreads();
 }
 
-__device__ __forceinline__ double field_val(const double *x, const double *diri, int32_t idx) {
-    return idx >= 0 ? x[idx] : diri[-1 - idx];
+// the engine's cell tables as the diagnostics read them (cell_view.h)
+using DevCells = CellView<CompMajor>;
+__host__ __device__ __forceinline__ DevCells cell_view(const FeDev &d) {
+    return DevCells{d.cu, d.cp, d.cb, d.G, d.u_diri, d.b_diri, d.ncell, d.nb, d.wdet, d.nu, d.kh, d.kv, d.nq};
 }
 
 }  // namespace npg

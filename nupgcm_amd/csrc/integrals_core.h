@@ -26,15 +26,10 @@
 // at point q).  T: the cell tables - G(k, c) (component 3 vertex + axis of grad lambda), wdet(c), z(i, c), u(x, l, c) / b(x, i, c)
 // (nodal values, Dirichlet nodes included), nu / kh / kv (q, c) behind has_nu / has_kh / has_kv.
 #pragma once
+#include <cmath>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define NPG_HD __host__ __device__ __forceinline__
-#define NPG_UNROLL _Pragma("unroll")
-#else
-#define NPG_HD inline
-#define NPG_UNROLL
-#endif
+#include "cell_view.h"
 
 namespace npg {
 
@@ -82,7 +77,7 @@ NPG_UNROLL
         }
         const double div = gu[0] + gu[4] + gu[8];
         acc[14] += w * (div * div);
-        const double nu = t.has_nu ? t.nu(q, c) : 0.0;
+        const double nu = t.has_nu() ? t.nu(q, c) : 0.0;
         double gg = 0.0;
 NPG_UNROLL
         for (int k = 0; k < 9; ++k) gg += gu[k] * gu[k];
@@ -109,11 +104,33 @@ NPG_UNROLL
         acc[5] += w * (uz * bq);
         acc[8] += w * (zq * bq);
         acc[9] += w * (ux * gx + uy * gy + uz * gz);
-        const double kh = t.has_kh ? t.kh(q, c) : 0.0, kv = t.has_kv ? t.kv(q, c) : 0.0;
+        const double kh = t.has_kh() ? t.kh(q, c) : 0.0, kv = t.has_kv() ? t.kv(q, c) : 0.0;
         acc[11] += w * (kh * (gx * gx + gy * gy) + kv * (gz * gz));
         acc[12] += w * (kv * gz);
         acc[13] += w * kv;
     }
+}
+
+// The argument checks of the entry points, for both libraries (the message, empty: fine).  handles = "fe and out are not NULL".
+inline std::string check_integrals_create(bool handles, const double *cell_z, int64_t ncell) {
+    if (!handles) return "npg_integrals_create: NULL argument";
+    if (!cell_z) return "npg_integrals_create: cell_z is NULL";
+    for (int64_t k = 0; k < ncell * 4; ++k)
+        if (!std::isfinite(cell_z[k])) return msgf("npg_integrals_create: cell_z[%lld][%d] is not finite", (long long)(k / 4), (int)(k % 4));
+    return "";
+}
+
+// I: the handle (its engine fe with n_inv, n_b, ctx); the vectors carry n and ctx
+template <class H, class V>
+std::string check_integrals_compute(const H *I, const V *x_inv, const V *b, int full_stress, const V *out) {
+    if (!(I && x_inv && b && out)) return "npg_integrals_compute: NULL argument";
+    const auto *fe = I->fe;
+    const std::string err = check_state_vectors("npg_integrals_compute", fe->n_inv, fe->n_b, x_inv->n, b->n);
+    if (!err.empty()) return err;
+    if (out->n < kNInt) return msgf("npg_integrals_compute: out holds %lld doubles, needs NPG_NINT = %d", (long long)out->n, kNInt);
+    if (full_stress != 0 && full_stress != 1) return msgf("npg_integrals_compute: full_stress must be 0 or 1, got %d", full_stress);
+    if (!(x_inv->ctx == fe->ctx && b->ctx == fe->ctx && out->ctx == fe->ctx)) return "npg_integrals_compute: arguments of different contexts";
+    return "";
 }
 
 }  // namespace npg

@@ -1,6 +1,6 @@
 // Water-mass transformation by mixing (npg_classes_mixing): what ONE sample of ONE cell adds to the NPG_NMIX diffusivity-weighted
-// channels of its (latitude band, buoyancy class) bin.  The arithmetic shared by the device kernels (classes.hip: k_mixing_scan /
-// k_mixing_bin) and the host library (csrc_host/nupgcm_host.cpp), as classes_core.h is for the census: the sample rule, the measure,
+// channels of its (latitude band, buoyancy class) bin.  The arithmetic shared by the device kernels (classes.hip: k_class_scan /
+// k_class_bin with the MixSampler below) and the host library (csrc_host/nupgcm_host.cpp), as classes_core.h is for the census: the sample rule, the measure,
 // the edges, the bin search and the expressions for y, z, B and grad B are class_sample's, in its order - without the velocity.
 //
 // At a sample (lam, measure w = wq wdet):
@@ -102,7 +102,69 @@ NPG_UNROLL
     return true;
 }
 
+// The mixing SAMPLER (classes_core.h: CensusSampler): the buoyancy, the binning N2, the diffusivities of the samples - tables kh / kv0
+// of ns values per cell in the layout of the cell tables (t.at(s, ns, c), cell_view.h), or, where a table is null, the scalar - and the
+// closure.
+struct MixSampler {
+    const double *kh, *kv0;
+    double kh_s, kv0_s;
+    MixClosure cl;
+    const double *xb;
+    double N2;
+    template <int NB>
+    using Cell = MixCell<NB>;
+    template <int NB, class T>
+    NPG_HD void load(const T &t, int64_t c, MixCell<NB> &n) const {
+        mix_cell_load<NB>(t, xb, c, n);
+    }
+    template <int NB, bool QUANT, class T>
+    NPG_HD bool sample(const T &t, const MixCell<NB> &n, const ClsRule &r, int s, int64_t c, int64_t *band, int64_t *cls,
+                       double term[kNMix]) const {
+        const size_t i = t.at(s, r.ns, c);
+        const double h = kh ? kh[i] : kh_s, v0 = kv0 ? kv0[i] : kv0_s;
+        return mix_sample<NB, QUANT>(n, r.lam + 4 * s, r.wq[s], N2, h, v0, cl, r.y_edges, r.ny, r.b_edges, r.nb, band, cls, term);
+    }
+};
+
 // nullptr if v is usable as a diffusivity: finite and >= 0
 inline const char *check_diffusivity(double v) { return std::isfinite(v) && v >= 0.0 ? nullptr : "must be finite and >= 0"; }
+
+// The argument checks of the entry points, for both libraries (the message, empty: fine).  n = ncell ns, the entries of a table.
+inline std::string check_classes_set_diffusivity(bool handle, int64_t n, int ns, const double *kappa_h, double kappa_h_scalar,
+                                                 const double *kappa_v0, double kappa_v0_scalar) {
+    if (!handle) return "npg_classes_set_diffusivity: NULL argument";
+    const char *err = kappa_h ? nullptr : check_diffusivity(kappa_h_scalar);
+    if (err) return msgf("npg_classes_set_diffusivity: the scalar kappa_h %s, got %.17g", err, kappa_h_scalar);
+    err = kappa_v0 ? nullptr : check_diffusivity(kappa_v0_scalar);
+    if (err) return msgf("npg_classes_set_diffusivity: the scalar kappa_v0 %s, got %.17g", err, kappa_v0_scalar);
+    const double *src[2] = {kappa_h, kappa_v0};
+    for (int t = 0; t < 2; ++t)
+        for (int64_t i = 0; src[t] && i < n; ++i)
+            if (check_diffusivity(src[t][i]))
+                return msgf("npg_classes_set_diffusivity: %s[%lld][%d] must be finite and >= 0, got %.17g", t ? "kappa_v0" : "kappa_h",
+                            (long long)(i / ns), (int)(i % ns), src[t][i]);
+    return "";
+}
+
+// K: the handle (kap_set, nbins, its engine fe with n_b, ctx); the vectors carry n and ctx
+template <class H, class V>
+std::string check_classes_mixing(const H *K, const V *b, double N2, const MixClosure &cl, const V *table, const V *info) {
+    if (!(K && b && table && info)) return "npg_classes_mixing: NULL argument";
+    if (!K->kap_set) return "npg_classes_mixing: no diffusivities: call npg_classes_set_diffusivity first";
+    const auto *fe = K->fe;
+    const std::string err = check_state_vectors("npg_classes_mixing", fe->n_inv, fe->n_b, fe->n_inv, b->n);       // no flow vector
+    if (!err.empty()) return err;
+    if (table->n < K->nbins * kNMix)
+        return msgf("npg_classes_mixing: table holds %lld doubles, needs (ny + 1)(nb + 1) NPG_NMIX = %lld", (long long)table->n,
+                    (long long)(K->nbins * kNMix));
+    if (info->n < 1 + kNMix) return msgf("npg_classes_mixing: info holds %lld doubles, needs 1 + NPG_NMIX = %d", (long long)info->n, 1 + kNMix);
+    if (check_diffusivity(N2)) return msgf("npg_classes_mixing: N2 must be finite and >= 0, got %.17g", N2);
+    if (check_diffusivity(cl.kappa_c)) return msgf("npg_classes_mixing: kappa_c must be finite and >= 0, got %.17g", cl.kappa_c);
+    if (check_diffusivity(cl.alpha)) return msgf("npg_classes_mixing: alpha must be finite and >= 0, got %.17g", cl.alpha);
+    if (check_diffusivity(cl.N2c)) return msgf("npg_classes_mixing: N2c must be finite and >= 0, got %.17g", cl.N2c);
+    if (cl.kappa_c > 0.0 && !(cl.N2min > 0.0)) return msgf("npg_classes_mixing: kappa_c > 0 needs N2min > 0, got %.17g", cl.N2min);
+    if (!(b->ctx == fe->ctx && table->ctx == fe->ctx && info->ctx == fe->ctx)) return "npg_classes_mixing: arguments of different contexts";
+    return "";
+}
 
 }  // namespace npg

@@ -24,7 +24,7 @@
 namespace npg {
 
 template <bool BLEND>
-__global__ void __launch_bounds__(kBlock) k_particles_advance(ParticleMesh m, DevTables t, const double *__restrict__ xa,
+__global__ void __launch_bounds__(kBlock) k_particles_advance(ParticleMesh m, DevCells t, const double *__restrict__ xa,
                                                               const double *__restrict__ xb, ParticleCall call, int64_t nsub,
                                                               int64_t n, double *__restrict__ xyz, int32_t *__restrict__ cell,
                                                               int32_t *__restrict__ status, int32_t *__restrict__ wind,
@@ -48,7 +48,7 @@ __global__ void __launch_bounds__(kBlock) k_particles_advance(ParticleMesh m, De
 }
 
 template <bool BLEND, bool DIFFUSE>
-__global__ void __launch_bounds__(kBlock) k_particles_walk(ParticleMesh m, WalkTables w, DevTables t, const double *__restrict__ xa,
+__global__ void __launch_bounds__(kBlock) k_particles_walk(ParticleMesh m, WalkTables w, DevCells t, const double *__restrict__ xa,
                                                            const double *__restrict__ xb, ParticleCall call, int64_t nsub,
                                                            uint64_t step0, int64_t n, double *__restrict__ xyz,
                                                            int32_t *__restrict__ cell, int32_t *__restrict__ status,
@@ -93,18 +93,18 @@ struct npg_particles {
     int64_t n = 0;
     double t = 0.0;              // the time the particles are at
     double L[3] = {0.0, 0.0, 0.0};
-    double *xyz = nullptr;       // [n][3]
-    double *t_lost = nullptr;    // [n], NaN while alive
-    int32_t *cell = nullptr;     // [n] the remembered cell, -1 = none
-    int32_t *status = nullptr;   // [n] 0 alive, 1 lost
-    int32_t *wind = nullptr;     // [n][3]
+    DevBuf<double> xyz;          // [n][3]
+    DevBuf<double> t_lost;       // [n], NaN while alive
+    DevBuf<int32_t> cell;        // [n] the remembered cell, -1 = none
+    DevBuf<int32_t> status;      // [n] 0 alive, 1 lost
+    DevBuf<int32_t> wind;        // [n][3]
     // npg_particles_walk: the wall tables, the diffusivities, the generator's key and the count of steps since npg_particles_set
     int64_t wall_ncell = -1, kappa_ncell = -1;       // -1 = not set
     bool wall_axis[3] = {false, false, false};       // some face carries a translation on this axis
-    int32_t *nbr = nullptr;      // [ncell][4]
-    int8_t *shift = nullptr;     // [ncell][4][3]
-    double *kappa = nullptr;     // [2][ncell][4]: kappa_h, kappa_v
-    int32_t *nreflect = nullptr; // [n], allocated with the walls
+    DevBuf<int32_t> nbr;         // [ncell][4]
+    DevBuf<int8_t> shift;        // [ncell][4][3]
+    DevBuf<double> kappa;        // [2][ncell][4]: kappa_h, kappa_v
+    DevBuf<int32_t> nreflect;    // [n], allocated with the walls
     double cd = 0.0;
     uint64_t seed = 0, step = 0;
 };
@@ -112,15 +112,6 @@ struct npg_particles {
 NPG_API int npg_particles_destroy(npg_particles *P) {
     if (!P) return NPG_OK;
     hipStreamSynchronize(P->ctx->stream);
-    hipFree(P->xyz);
-    hipFree(P->t_lost);
-    hipFree(P->cell);
-    hipFree(P->status);
-    hipFree(P->wind);
-    hipFree(P->nbr);
-    hipFree(P->shift);
-    hipFree(P->kappa);
-    hipFree(P->nreflect);
     delete P;
     return NPG_OK;
 }
@@ -129,22 +120,18 @@ NPG_API int npg_particles_create(npg_ctx *ctx, int64_t n, npg_particles **out) {
     NPG_REQUIRE(ctx && out, "npg_particles_create: NULL argument");
     NPG_REQUIRE(n >= 0 && n <= ((int64_t)1 << 32), "npg_particles_create: 0 .. 2^32 particles, got %lld", (long long)n);
     NPG_HIP(hipSetDevice(ctx->device));
-    npg_particles *P = new npg_particles();
+    std::unique_ptr<npg_particles> P(new npg_particles());
     P->ctx = ctx;
     P->n = n;
     const size_t m = std::max<size_t>(1, (size_t)n);
-    hipError_t e = hipMalloc((void **)&P->xyz, m * 3 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&P->t_lost, m * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&P->cell, m * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&P->status, m * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&P->wind, m * 3 * sizeof(int32_t));
-    if (e != hipSuccess) {
-        npg_particles_destroy(P);
-        NPG_HIP(e);
-    }
-    *out = P;
+    NPG_HIP(P->xyz.alloc(m * 3));
+    NPG_HIP(P->t_lost.alloc(m));
+    NPG_HIP(P->cell.alloc(m));
+    NPG_HIP(P->status.alloc(m));
+    NPG_HIP(P->wind.alloc(m * 3));
+    *out = P.release();
     const std::vector<double> zero(m * 3, 0.0);
-    return npg_particles_set(P, zero.data(), 0.0);
+    return npg_particles_set(*out, zero.data(), 0.0);
 }
 
 NPG_API int npg_particles_set(npg_particles *P, const double *xyz, double t0) {
@@ -195,7 +182,7 @@ NPG_API int npg_particles_advance(npg_particles *P, npg_fe *fe, npg_locator *loc
     }
     NPG_HIP(hipSetDevice(P->ctx->device));
     const FeDev &d = fe->d;
-    const DevTables t{d.cu, d.cp, d.cb, d.G, d.u_diri, d.b_diri, d.ncell, d.nb};
+    const DevCells t = cell_view(d);
     const ParticleMesh m{loc->grid, loc->bin_ptr, loc->bin_cells, loc->geo, {P->L[0], P->L[1], P->L[2]}};
     const dim3 grid((unsigned)((P->n + kBlock - 1) / kBlock)), block(kBlock);
     hipStream_t st = P->ctx->stream;
@@ -218,26 +205,15 @@ NPG_API int npg_particles_set_walls(npg_particles *P, const int32_t *nbr, const 
     NPG_REQUIRE(!err, "npg_particles_set_walls: %s", err);
     NPG_HIP(hipSetDevice(P->ctx->device));
     NPG_HIP(hipStreamSynchronize(P->ctx->stream));
-    int32_t *d_nbr = nullptr, *d_refl = P->nreflect;
-    int8_t *d_shift = nullptr;
-    const size_t n = std::max<size_t>(1, (size_t)P->n);
-    hipError_t e = hipMalloc((void **)&d_nbr, (size_t)ncell * 4 * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_shift, (size_t)ncell * 12);
-    if (e == hipSuccess && !d_refl) {
-        e = hipMalloc((void **)&d_refl, n * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMemset(d_refl, 0, n * sizeof(int32_t));
+    DevBuf<int32_t> d_nbr, d_refl;               // the handle keeps its tables unless every step succeeds
+    DevBuf<int8_t> d_shift;
+    NPG_HIP(d_nbr.upload(nbr, (size_t)ncell * 4));
+    NPG_HIP(d_shift.upload(shift, (size_t)ncell * 12));
+    if (!P->nreflect) {
+        NPG_HIP(d_refl.zeros(std::max<size_t>(1, (size_t)P->n)));
+        P->nreflect.swap(d_refl);
     }
-    if (e == hipSuccess) e = hipMemcpy(d_nbr, nbr, (size_t)ncell * 4 * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_shift, shift, (size_t)ncell * 12, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        hipFree(d_nbr);
-        hipFree(d_shift);
-        if (!P->nreflect) hipFree(d_refl);
-        NPG_HIP(e);
-    }
-    hipFree(P->nbr);
-    hipFree(P->shift);
-    P->nbr = d_nbr, P->shift = d_shift, P->nreflect = d_refl, P->wall_ncell = ncell;
+    P->nbr.swap(d_nbr), P->shift.swap(d_shift), P->wall_ncell = ncell;
     for (int a = 0; a < 3; ++a) P->wall_axis[a] = has[a];
     return NPG_OK;
 }
@@ -248,8 +224,7 @@ NPG_API int npg_particles_set_diffusion(npg_particles *P, const double *kappa_h,
     NPG_HIP(hipSetDevice(P->ctx->device));
     if (!kappa_h && !kappa_v) {              // diffusion off
         NPG_HIP(hipStreamSynchronize(P->ctx->stream));
-        hipFree(P->kappa);
-        P->kappa = nullptr, P->kappa_ncell = -1;
+        P->kappa.reset(), P->kappa_ncell = -1;
         return NPG_OK;
     }
     NPG_REQUIRE(kappa_h && kappa_v, "npg_particles_set_diffusion: NULL argument (kappa_h and kappa_v are given together)");
@@ -259,17 +234,12 @@ NPG_API int npg_particles_set_diffusion(npg_particles *P, const double *kappa_h,
     const char *err = check_kappa_tables(kappa_h, kappa_v, ncell, c_d);
     NPG_REQUIRE(!err, "npg_particles_set_diffusion: %s", err);
     NPG_HIP(hipStreamSynchronize(P->ctx->stream));
-    double *d = nullptr;
+    DevBuf<double> d;
     const size_t bytes = (size_t)ncell * 4 * sizeof(double);
-    hipError_t e = hipMalloc((void **)&d, 2 * bytes);
-    if (e == hipSuccess) e = hipMemcpy(d, kappa_h, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + (size_t)ncell * 4, kappa_v, bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        hipFree(d);
-        NPG_HIP(e);
-    }
-    hipFree(P->kappa);
-    P->kappa = d, P->kappa_ncell = ncell, P->cd = c_d, P->seed = seed;
+    NPG_HIP(d.alloc((size_t)ncell * 8));
+    NPG_HIP(hipMemcpy(d, kappa_h, bytes, hipMemcpyHostToDevice));
+    NPG_HIP(hipMemcpy(d + (size_t)ncell * 4, kappa_v, bytes, hipMemcpyHostToDevice));
+    P->kappa.swap(d), P->kappa_ncell = ncell, P->cd = c_d, P->seed = seed;
     return NPG_OK;
 }
 
@@ -302,7 +272,7 @@ NPG_API int npg_particles_walk(npg_particles *P, npg_fe *fe, npg_locator *loc, c
     }
     NPG_HIP(hipSetDevice(P->ctx->device));
     const FeDev &d = fe->d;
-    const DevTables t{d.cu, d.cp, d.cb, d.G, d.u_diri, d.b_diri, d.ncell, d.nb};
+    const DevCells t = cell_view(d);
     const ParticleMesh m{loc->grid, loc->bin_ptr, loc->bin_cells, loc->geo, {P->L[0], P->L[1], P->L[2]}};
     const bool diffuse = P->kappa_ncell >= 0;
     const WalkTables w{P->nbr, P->shift, P->kappa, diffuse ? P->kappa + (size_t)P->kappa_ncell * 4 : nullptr, P->cd,

@@ -39,7 +39,7 @@ __global__ void __launch_bounds__(kBlock) k_locate(BinGrid g, const int32_t *__r
 }
 
 template <int FIELD, int NB>
-__global__ void __launch_bounds__(kBlock) k_sample(DevTables t, const double *__restrict__ x, const int32_t *__restrict__ cell,
+__global__ void __launch_bounds__(kBlock) k_sample(DevCells t, const double *__restrict__ x, const int32_t *__restrict__ cell,
                                                    const double *__restrict__ lam, int64_t n, double *__restrict__ out) {
     constexpr int NC = FIELD == NPG_SAMPLE_U || FIELD == NPG_SAMPLE_GRAD_B ? 3 : 1;
     const int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x;
@@ -48,7 +48,7 @@ __global__ void __launch_bounds__(kBlock) k_sample(DevTables t, const double *__
     double v[NC];
     if (c >= 0 && c < t.ncell) {             // cell ids may come from the caller (npg_located_upload)
         const double l[4] = {lam[4 * i], lam[4 * i + 1], lam[4 * i + 2], lam[4 * i + 3]};
-        DevTables tn = t;
+        DevCells tn = t;
         tn.nb = NB;                          // a compile-time constant: the P2 / P1 branch folds away
         sample_point(tn, FIELD, x, c, l, v);
     } else {
@@ -65,7 +65,7 @@ __global__ void __launch_bounds__(kBlock) k_sample(DevTables t, const double *__
 template <int NB, bool PART>
 __global__ void __launch_bounds__(kBlock) k_grid_integrals(BinGrid g, const int32_t *__restrict__ bin_ptr,
                                                            const int32_t *__restrict__ bin_cells, const double *__restrict__ geo,
-                                                           DevTables t, const double *__restrict__ xu, const double *__restrict__ xb,
+                                                           DevCells t, const double *__restrict__ xu, const double *__restrict__ xb,
                                                            double N2, const double *__restrict__ axes, int nx, int ny, int nz,
                                                            int nchunk, double *__restrict__ col, double *__restrict__ part) {
     constexpr int NW = kBlock / 64;
@@ -315,7 +315,7 @@ NPG_API int npg_fe_sample(npg_fe *fe, int field, const npg_vec *vec, const npg_l
     NPG_REQUIRE(vec->ctx == fe->ctx && pts->ctx == fe->ctx && out->ctx == fe->ctx, "npg_fe_sample: arguments of different contexts");
     if (n == 0) return NPG_OK;
     const FeDev &d = fe->d;
-    const DevTables t{d.cu, d.cp, d.cb, d.G, d.u_diri, d.b_diri, d.ncell, d.nb};
+    const DevCells t = cell_view(d);
     const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
     hipStream_t st = fe->ctx->stream;
 #define NPG_SAMPLE_LAUNCH(F, NB) \
@@ -340,10 +340,7 @@ NPG_API int npg_fe_grid_integrals(npg_fe *fe, npg_locator *loc, const npg_vec *x
                     zon->ctx == fe->ctx, "npg_fe_grid_integrals: arguments of different contexts");
     NPG_REQUIRE(loc->part ? loc->ncell <= fe->d.ncell : loc->ncell == fe->d.ncell,
                 "npg_fe_grid_integrals: the locator was built for another mesh");
-    NPG_REQUIRE(x_inv->n == fe->n_inv, "npg_fe_grid_integrals: the flow vector has %lld entries, expected %lld", (long long)x_inv->n,
-                (long long)fe->n_inv);
-    NPG_REQUIRE(b->n == fe->n_b, "npg_fe_grid_integrals: the buoyancy vector has %lld entries, expected %lld", (long long)b->n,
-                (long long)fe->n_b);
+    NPG_REQUIRE_OK(check_state_vectors("npg_fe_grid_integrals", fe->n_inv, fe->n_b, x_inv->n, b->n));
     NPG_REQUIRE(axes->n == nx + ny + nz, "npg_fe_grid_integrals: axes must hold nx + ny + nz doubles");
     NPG_REQUIRE(col->n == kGridCol * nx * ny && zon->n == kGridZon * ny * nz,
                 "npg_fe_grid_integrals: col must hold %d nx ny and zon %d ny nz doubles", kGridCol, kGridZon);
@@ -369,7 +366,7 @@ NPG_API int npg_fe_grid_integrals(npg_fe *fe, npg_locator *loc, const npg_vec *x
         loc->grid_part_n = need;
     }
     const FeDev &d = fe->d;
-    const DevTables t{d.cu, d.cp, d.cb, d.G, d.u_diri, d.b_diri, d.ncell, d.nb};
+    const DevCells t = cell_view(d);
     const dim3 grid((unsigned)(ny * nchunk)), block(kBlock);
 #define NPG_GRID_LAUNCH(NB, PART)                                                                                                \
     hipLaunchKernelGGL((k_grid_integrals<NB, PART>), grid, block, 0, st, loc->grid, loc->bin_ptr, loc->bin_cells, loc->geo, t,    \

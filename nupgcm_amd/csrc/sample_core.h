@@ -16,13 +16,7 @@
 #include <limits>
 #include <vector>
 
-#if defined(__HIPCC__)
-#define NPG_HD __host__ __device__ __forceinline__
-#define NPG_UNROLL _Pragma("unroll")
-#else
-#define NPG_HD inline
-#define NPG_UNROLL
-#endif
+#include "cell_view.h"
 
 namespace npg {
 

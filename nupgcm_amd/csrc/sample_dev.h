@@ -1,25 +1,10 @@
-// The locator's and the located points' handles and the engine's tables as sample_point reads them, shared by the translation units
-// that locate and evaluate points (sample.hip: point sampling and grid integrals; particles.hip: particle advection).
+// The locator's and the located points' handles, shared by the translation units that locate and evaluate points (sample.hip: point
+// sampling and grid integrals; particles.hip: particle advection; surfaces.hip).  sample_point reads the engine's tables through the
+// cell view (DevCells, fe_dev.h).
 #pragma once
 #include "common.h"
 #include "fe_dev.h"
 #include "sample_core.h"
-
-namespace npg {
-
-// the engine's tables as sample_point reads them ([component][cell])
-struct DevTables {
-    const int32_t *cu_, *cp_, *cb_;
-    const double *G_, *udiri, *bdiri;
-    int64_t ncell;
-    int nb;
-    __device__ __forceinline__ int32_t cu(int l, int64_t c) const { return cu_[(size_t)l * ncell + c]; }
-    __device__ __forceinline__ int32_t cp(int m, int64_t c) const { return cp_[(size_t)m * ncell + c]; }
-    __device__ __forceinline__ int32_t cb(int i, int64_t c) const { return cb_[(size_t)i * ncell + c]; }
-    __device__ __forceinline__ double G(int k, int64_t c) const { return G_[(size_t)k * ncell + c]; }
-};
-
-}  // namespace npg
 
 struct npg_locator {
     npg_ctx *ctx = nullptr;

@@ -22,7 +22,7 @@ static_assert(NPG_NSURF == npg::kNSurf, "NPG_NSURF of the header and kNSurf of s
 namespace npg {
 
 template <int NB>
-__global__ void __launch_bounds__(kBlock) k_surfaces_scan(SurfaceColumns S, DevTables t, const double *__restrict__ xb, double N2,
+__global__ void __launch_bounds__(kBlock) k_surfaces_scan(SurfaceColumns S, DevCells t, const double *__restrict__ xb, double N2,
                                                           const double *__restrict__ levels, int nlev, double *out,
                                                           int32_t *__restrict__ cross_cell, double *__restrict__ cols) {
     const int64_t j = blockIdx.x * (int64_t)kBlock + threadIdx.x;
@@ -30,7 +30,7 @@ __global__ void __launch_bounds__(kBlock) k_surfaces_scan(SurfaceColumns S, DevT
     column_surfaces<NB>(S, t, xb, N2, levels, nlev, j, out, cross_cell, cols);
 }
 
-__global__ void __launch_bounds__(kBlock) k_surfaces_fields(SurfaceColumns S, DevTables t, const double *__restrict__ xu,
+__global__ void __launch_bounds__(kBlock) k_surfaces_fields(SurfaceColumns S, DevCells t, const double *__restrict__ xu,
                                                             const double *__restrict__ xb, double N2, int nlev,
                                                             const int32_t *__restrict__ cross_cell, double *out) {
     const int64_t o = blockIdx.x * (int64_t)kBlock + threadIdx.x;
@@ -48,12 +48,12 @@ struct npg_surfaces {
     int64_t ncol = 0, nseg = 0, max_per_col = 0, ndry = 0;
     std::vector<int64_t> h_col_ptr;      // kept for npg_surfaces_columns
     std::vector<double> h_ztop, h_zbot;  // per column, NaN where dry
-    int64_t *col_ptr = nullptr;
-    int32_t *seg_cell = nullptr;
-    double *seg_ztop = nullptr, *seg_zbot = nullptr, *xy = nullptr;
+    DevBuf<int64_t> col_ptr;
+    DevBuf<int32_t> seg_cell;
+    DevBuf<double> seg_ztop, seg_zbot, xy;
     const double *geo = nullptr;         // the locator's records (not owned: the locator outlives the handle)
-    double *levels = nullptr;            // the levels of the last call, uploaded again only when they change
-    int32_t *cross_cell = nullptr;       // [nlev][ncol] the cell of the uppermost crossing, grown on demand
+    DevBuf<double> levels;               // the levels of the last call, uploaded again only when they change
+    DevBuf<int32_t> cross_cell;          // [nlev][ncol] the cell of the uppermost crossing, grown on demand
     size_t cross_n = 0;
     std::vector<double> h_levels;
 };
@@ -61,13 +61,6 @@ struct npg_surfaces {
 NPG_API int npg_surfaces_destroy(npg_surfaces *S) {
     if (!S) return NPG_OK;
     hipStreamSynchronize(S->ctx->stream);
-    hipFree(S->col_ptr);
-    hipFree(S->seg_cell);
-    hipFree(S->seg_ztop);
-    hipFree(S->seg_zbot);
-    hipFree(S->xy);
-    hipFree(S->levels);
-    hipFree(S->cross_cell);
     delete S;
     return NPG_OK;
 }
@@ -88,7 +81,7 @@ NPG_API int npg_surfaces_create(npg_fe *fe, npg_locator *loc, const double *xy, 
     ColumnTables ct;
     const char *err = build_columns(geo.data(), ncell, loc->grid.lo[2], loc->grid.hi[2], xy, ncol, ct);
     NPG_REQUIRE(!err, "%s", err);
-    npg_surfaces *S = new npg_surfaces();
+    std::unique_ptr<npg_surfaces> S(new npg_surfaces());
     S->ctx = fe->ctx, S->fe = fe, S->geo = loc->geo;
     S->ncol = ncol, S->nseg = ct.col_ptr[(size_t)ncol], S->max_per_col = ct.max_per_col, S->ndry = ct.ndry;
     S->h_col_ptr = ct.col_ptr;
@@ -97,21 +90,18 @@ NPG_API int npg_surfaces_create(npg_fe *fe, npg_locator *loc, const double *xy, 
         if (ct.col_ptr[(size_t)j + 1] > ct.col_ptr[(size_t)j])
             S->h_ztop[(size_t)j] = ct.seg_ztop[(size_t)ct.col_ptr[(size_t)j]], S->h_zbot[(size_t)j] = ct.seg_zbot[(size_t)ct.col_ptr[(size_t)j + 1] - 1];
     const size_t ns = std::max<size_t>(1, (size_t)S->nseg), nc = std::max<size_t>(1, (size_t)ncol);
-    hipError_t e = hipMalloc((void **)&S->col_ptr, ((size_t)ncol + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&S->seg_cell, ns * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&S->seg_ztop, ns * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&S->seg_zbot, ns * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&S->xy, nc * 2 * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(S->col_ptr, ct.col_ptr.data(), ((size_t)ncol + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && S->nseg) e = hipMemcpy(S->seg_cell, ct.seg_cell.data(), (size_t)S->nseg * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && S->nseg) e = hipMemcpy(S->seg_ztop, ct.seg_ztop.data(), (size_t)S->nseg * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess && S->nseg) e = hipMemcpy(S->seg_zbot, ct.seg_zbot.data(), (size_t)S->nseg * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess && ncol) e = hipMemcpy(S->xy, xy, (size_t)ncol * 2 * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        npg_surfaces_destroy(S);
-        NPG_HIP(e);
+    NPG_HIP(S->col_ptr.upload(ct.col_ptr));
+    NPG_HIP(S->seg_cell.alloc(ns));                  // at least one entry each: never a null table in a kernel's arguments
+    NPG_HIP(S->seg_ztop.alloc(ns));
+    NPG_HIP(S->seg_zbot.alloc(ns));
+    NPG_HIP(S->xy.alloc(nc * 2));
+    if (S->nseg) {
+        NPG_HIP(hipMemcpy(S->seg_cell, ct.seg_cell.data(), (size_t)S->nseg * sizeof(int32_t), hipMemcpyHostToDevice));
+        NPG_HIP(hipMemcpy(S->seg_ztop, ct.seg_ztop.data(), (size_t)S->nseg * sizeof(double), hipMemcpyHostToDevice));
+        NPG_HIP(hipMemcpy(S->seg_zbot, ct.seg_zbot.data(), (size_t)S->nseg * sizeof(double), hipMemcpyHostToDevice));
     }
-    *out = S;
+    if (ncol) NPG_HIP(hipMemcpy(S->xy, xy, (size_t)ncol * 2 * sizeof(double), hipMemcpyHostToDevice));
+    *out = S.release();
     return NPG_OK;
 }
 
@@ -152,10 +142,7 @@ NPG_API int npg_surfaces_compute(npg_surfaces *S, const npg_vec *x_inv, const np
     NPG_REQUIRE(x_inv->ctx == S->ctx && b->ctx == S->ctx && out->ctx == S->ctx && cols->ctx == S->ctx,
                 "npg_surfaces_compute: arguments of different contexts");
     const npg_fe *fe = S->fe;
-    NPG_REQUIRE(x_inv->n == fe->n_inv, "npg_surfaces_compute: the flow vector has %lld entries, expected %lld", (long long)x_inv->n,
-                (long long)fe->n_inv);
-    NPG_REQUIRE(b->n == fe->n_b, "npg_surfaces_compute: the buoyancy vector has %lld entries, expected %lld", (long long)b->n,
-                (long long)fe->n_b);
+    NPG_REQUIRE_OK(check_state_vectors("npg_surfaces_compute", fe->n_inv, fe->n_b, x_inv->n, b->n));
     NPG_REQUIRE(out->n == (int64_t)kNSurf * nlev * S->ncol && cols->n == (int64_t)kNSurfCol * S->ncol,
                 "npg_surfaces_compute: out must hold %d nlev ncol = %lld and cols %d ncol = %lld entries, got %lld and %lld", kNSurf,
                 (long long)kNSurf * nlev * S->ncol, kNSurfCol, (long long)kNSurfCol * S->ncol, (long long)out->n, (long long)cols->n);
@@ -165,9 +152,8 @@ NPG_API int npg_surfaces_compute(npg_surfaces *S, const npg_vec *x_inv, const np
     if ((int)S->h_levels.size() != nlev || std::memcmp(S->h_levels.data(), levels, (size_t)nlev * sizeof(double)) != 0) {
         NPG_HIP(hipStreamSynchronize(st));           // an earlier scan may still read the old levels
         if ((int)S->h_levels.size() != nlev) {
-            hipFree(S->levels);
-            S->levels = nullptr, S->h_levels.clear();
-            NPG_HIP(hipMalloc((void **)&S->levels, (size_t)nlev * sizeof(double)));
+            S->h_levels.clear();
+            NPG_HIP(S->levels.alloc((size_t)nlev));
         }
         NPG_HIP(hipMemcpy(S->levels, levels, (size_t)nlev * sizeof(double), hipMemcpyHostToDevice));
         S->h_levels.assign(levels, levels + nlev);
@@ -175,22 +161,21 @@ NPG_API int npg_surfaces_compute(npg_surfaces *S, const npg_vec *x_inv, const np
     const size_t ntab = (size_t)nlev * (size_t)S->ncol;
     if (S->cross_n < ntab) {
         NPG_HIP(hipStreamSynchronize(st));
-        hipFree(S->cross_cell);
-        S->cross_cell = nullptr, S->cross_n = 0;
-        NPG_HIP(hipMalloc((void **)&S->cross_cell, ntab * sizeof(int32_t)));
+        S->cross_n = 0;
+        NPG_HIP(S->cross_cell.alloc(ntab));
         S->cross_n = ntab;
     }
     const FeDev &d = fe->d;
-    const DevTables t{d.cu, d.cp, d.cb, d.G, d.u_diri, d.b_diri, d.ncell, d.nb};
+    const DevCells t = cell_view(d);
     const SurfaceColumns sc{S->col_ptr, S->seg_cell, S->seg_ztop, S->seg_zbot, S->xy, S->geo, S->ncol};
     const dim3 grid((unsigned)((S->ncol + kBlock - 1) / kBlock)), block(kBlock);
     if (d.nb == 10)
-        hipLaunchKernelGGL(k_surfaces_scan<10>, grid, block, 0, st, sc, t, b->d, N2, S->levels, nlev, out->d, S->cross_cell, cols->d);
+        hipLaunchKernelGGL(k_surfaces_scan<10>, grid, block, 0, st, sc, t, b->d, N2, S->levels.p, nlev, out->d, S->cross_cell.p, cols->d);
     else
-        hipLaunchKernelGGL(k_surfaces_scan<4>, grid, block, 0, st, sc, t, b->d, N2, S->levels, nlev, out->d, S->cross_cell, cols->d);
+        hipLaunchKernelGGL(k_surfaces_scan<4>, grid, block, 0, st, sc, t, b->d, N2, S->levels.p, nlev, out->d, S->cross_cell.p, cols->d);
     NPG_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_surfaces_fields, dim3((unsigned)((ntab + kBlock - 1) / kBlock)), block, 0, st, sc, t, x_inv->d, b->d, N2, nlev,
-                       S->cross_cell, out->d);
+                       S->cross_cell.p, out->d);
     NPG_HIP(hipGetLastError());
     return NPG_OK;
 }

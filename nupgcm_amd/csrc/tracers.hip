@@ -20,20 +20,6 @@ static_assert(npg::kTrMaxQ == npg::kMaxQ, "a lane column holds the engine's larg
 
 namespace npg {
 
-// the engine's cell tables as cell_tracers reads them ([component][cell])
-struct TrCells {
-    FeDev d;
-    __device__ __forceinline__ double G(int k, int64_t c) const { return d.G[(size_t)k * d.ncell + c]; }
-    __device__ __forceinline__ double wdet(int64_t c) const { return d.wdet[c]; }
-    __device__ __forceinline__ double u(const double *x, int l, int64_t c) const {
-        return field_val(x, d.u_diri, d.cu[(size_t)l * d.ncell + c]);
-    }
-    __device__ __forceinline__ int32_t cb(int i, int64_t c) const { return d.cb[(size_t)i * d.ncell + c]; }
-    __device__ __forceinline__ double kh(int q, int64_t c) const { return d.kh[(size_t)q * d.ncell + c]; }
-    __device__ __forceinline__ double kv(int q, int64_t c) const { return d.kv[(size_t)q * d.ncell + c]; }
-    __device__ __forceinline__ size_t loc(int i, int64_t c) const { return (size_t)i * d.ncell + c; }
-};
-
 constexpr int kTrBlock = 128;
 
 // a lane's nq x 3 velocities: column `lane` of uq[3 nq][kTrBlock]
@@ -51,7 +37,7 @@ __global__ void __launch_bounds__(kTrBlock) __attribute__((amdgpu_waves_per_eu(2
     extern __shared__ double uq_lds[];                                   // 3 nq kTrBlock values of R
     const int64_t cell = blockIdx.x * (int64_t)kTrBlock + threadIdx.x;
     if (cell >= d.ncell) return;
-    const TrCells cells{d};
+    const TracerCells<DevCells> cells{cell_view(d)};
     LaneColumn<R> uq{reinterpret_cast<R *>(uq_lds) + threadIdx.x};
     cell_tracers<R, NB>(t, cells, uq, d.nq, bdf2 != 0, dt, theta, xi, xip, ts, cell);
 }
@@ -77,10 +63,10 @@ struct npg_tracers {
     npg_fe *fe = nullptr;
     int ntracer = 0;
     int64_t n_diri = 0;              // Dirichlet values per tracer (at least 1 stored)
-    double *loc = nullptr;           // [ntracer][nb][ncell]
-    double *diri = nullptr;          // [ntracer][max(1, n_b_diri)]
-    double *gamma = nullptr;         // [ntracer]
-    double *source = nullptr;        // [ntracer]
+    DevBuf<double> loc;              // [ntracer][nb][ncell]
+    DevBuf<double> diri;             // [ntracer][max(1, n_b_diri)]
+    DevBuf<double> gamma;            // [ntracer]
+    DevBuf<double> source;           // [ntracer]
     std::vector<double> h_gamma;
     std::vector<uint8_t> h_lift;     // tracer k has a non-zero Dirichlet value
 };
@@ -88,10 +74,6 @@ struct npg_tracers {
 NPG_API int npg_tracers_destroy(npg_tracers *T) {
     if (!T) return NPG_OK;
     hipStreamSynchronize(T->ctx->stream);
-    hipFree(T->loc);
-    hipFree(T->diri);
-    hipFree(T->gamma);
-    hipFree(T->source);
     delete T;
     return NPG_OK;
 }
@@ -101,7 +83,7 @@ NPG_API int npg_tracers_create(npg_fe *fe, int ntracer, npg_tracers **out) {
     NPG_REQUIRE(ntracer >= 1, "npg_tracers_create: ntracer must be at least 1, got %d", ntracer);
     NPG_REQUIRE(ntracer <= 65535, "npg_tracers_create: at most 65535 tracers, got %d", ntracer);
     NPG_HIP(hipSetDevice(fe->ctx->device));
-    npg_tracers *T = new npg_tracers();
+    std::unique_ptr<npg_tracers> T(new npg_tracers());
     T->ctx = fe->ctx;
     T->fe = fe;
     T->ntracer = ntracer;
@@ -109,18 +91,11 @@ NPG_API int npg_tracers_create(npg_fe *fe, int ntracer, npg_tracers **out) {
     T->h_gamma.assign((size_t)ntracer, 0.0);
     T->h_lift.assign((size_t)ntracer, 0);
     const size_t nloc = (size_t)ntracer * fe->d.nb * fe->d.ncell, nd = (size_t)ntracer * T->n_diri;
-    hipError_t e = hipMalloc((void **)&T->loc, nloc * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&T->diri, nd * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(T->diri, 0, nd * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&T->gamma, (size_t)ntracer * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(T->gamma, 0, (size_t)ntracer * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&T->source, (size_t)ntracer * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(T->source, 0, (size_t)ntracer * sizeof(double));
-    if (e != hipSuccess) {
-        npg_tracers_destroy(T);
-        NPG_HIP(e);
-    }
-    *out = T;
+    NPG_HIP(T->loc.alloc(nloc));
+    NPG_HIP(T->diri.zeros(nd));
+    NPG_HIP(T->gamma.zeros((size_t)ntracer));
+    NPG_HIP(T->source.zeros((size_t)ntracer));
+    *out = T.release();
     return NPG_OK;
 }
 

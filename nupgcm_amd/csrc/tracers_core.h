@@ -28,13 +28,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define NPG_HD __host__ __device__ __forceinline__
-#define NPG_UNROLL _Pragma("unroll")
-#else
-#define NPG_HD inline
-#define NPG_UNROLL
-#endif
+#include "cell_view.h"
 
 namespace npg {
 
@@ -50,7 +44,11 @@ struct TracerSet {
     double *loc;                       // [ntracer][loc_stride]
 };
 
-NPG_HD double tracer_val(const double *x, const double *diri, int32_t idx) { return idx >= 0 ? x[idx] : diri[-1 - idx]; }
+// the cell tables and where local entry i of cell c lives within one tracer's local block (the view's layout, nb entries per cell)
+template <class View>
+struct TracerCells : View {
+    NPG_HD size_t loc(int i, int64_t c) const { return this->at(i, this->nb, c); }
+};
 
 template <typename R, int NB, class S, class T, class U>
 NPG_HD void cell_tracers(const S &s, const T &t, U &uq, int nq, bool bdf2, double dt, double theta, const double *xi, const double *xip,
@@ -86,7 +84,7 @@ NPG_UNROLL
 NPG_UNROLL
         for (int i = 0; i < NB; ++i) {
             const int32_t idx = t.cb(i, c);
-            const double v = tracer_val(ck, dk, idx), vp = tracer_val(cpk, dk, idx);
+            const double v = field_val(ck, dk, idx), vp = field_val(cpk, dk, idx);
             bm[i] = (R)(c1 * v + c2 * vp);
             bt[i] = (R)(e1 * v + e2 * vp);
             lift = lift || (idx < 0 && dk[-1 - idx] != 0.0);

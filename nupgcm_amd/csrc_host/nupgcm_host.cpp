@@ -23,6 +23,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -30,6 +31,7 @@
 #include <unistd.h>
 
 #include "../../include/nupgcm_hip.h"
+#include "../csrc/cell_view.h"
 
 #define NPG_API extern "C" __attribute__((visibility("default")))
 
@@ -49,6 +51,12 @@ void set_error(const char *fmt, ...) {
             set_error(__VA_ARGS__); \
             return NPG_EINVAL;      \
         }                           \
+    } while (0)
+// report the message of a shared argument check (the csrc/*_core.h check_* functions; empty: fine)
+#define REQUIRE_OK(msg)                            \
+    do {                                           \
+        const std::string m_ = (msg);              \
+        REQUIRE(m_.empty(), "%s", m_.c_str());     \
     } while (0)
 }  // namespace
 
@@ -751,7 +759,22 @@ struct npg_fe {
     std::vector<int64_t> gidx, iidx;                                              // cell * nb + i   /   cell * 34 + l
     std::vector<double> coef[4], kv0, hcell, loc;                                 // nu, kappa_h, kappa_v, f: [ncell][nq]
 };
-static inline double fval(const double *x, const std::vector<double> &diri, int32_t idx) { return idx >= 0 ? x[idx] : diri[(size_t)(-1 - idx)]; }
+static inline double fval(const double *x, const std::vector<double> &diri, int32_t idx) { return npg::field_val(x, diri.data(), idx); }
+namespace {
+// the engine's tables as the diagnostics read them, cell by cell (csrc/cell_view.h; [cell][component] here)
+using HostView = npg::CellView<npg::CellMajor>;
+inline const double *data_or_null(const std::vector<double> &v) { return v.empty() ? nullptr : v.data(); }
+inline HostView host_view(const npg_fe *fe) {
+    return HostView{fe->cu.data(), fe->cp.data(), fe->cb.data(), fe->G.data(), fe->u_diri.data(), fe->b_diri.data(), fe->ncell, fe->nb,
+                    fe->wdet.data(), data_or_null(fe->coef[0]), data_or_null(fe->coef[1]), data_or_null(fe->coef[2]), fe->nq};
+}
+struct HostShape {       // and its shape tables as cell_integrals and cell_tracers read them
+    const double *qw, *N2, *dN2, *Nb, *dNb, *N1;
+};
+inline HostShape host_shape(const npg_fe *fe) {
+    return HostShape{fe->qw.data(), fe->N2.data(), fe->dN2.data(), fe->Nb.data(), fe->dNb.data(), fe->N1.data()};
+}
+}  // namespace
 
 NPG_API int npg_fe_create(npg_ctx *ctx, const npg_fe_desc *d, npg_fe **out) {
     REQUIRE(ctx && d && out, "npg_fe_create: NULL argument");
@@ -1211,18 +1234,6 @@ struct npg_located {
     std::vector<int32_t> cell;
     std::vector<double> lam;
 };
-namespace {
-struct HostTables {      // the engine's tables as sample_point reads them ([cell][component])
-    const npg_fe *fe;
-    const double *udiri, *bdiri;
-    int nb;
-    int32_t cu(int l, int64_t c) const { return fe->cu[(size_t)c * 30 + l]; }
-    int32_t cp(int m, int64_t c) const { return fe->cp[(size_t)c * 4 + m]; }
-    int32_t cb(int i, int64_t c) const { return fe->cb[(size_t)c * nb + i]; }
-    double G(int k, int64_t c) const { return fe->G[(size_t)c * 12 + k]; }
-};
-}  // namespace
-
 NPG_API int npg_locator_create(npg_fe *fe, const double *anchor, int64_t nbins, npg_locator **out) {
     REQUIRE(fe && anchor && out, "npg_locator_create: NULL argument");
     REQUIRE(nbins >= 0 && nbins <= ((int64_t)1 << 26), "npg_locator_create: nbins must be 0 (automatic) .. 2^26");
@@ -1297,7 +1308,7 @@ NPG_API int npg_fe_sample(npg_fe *fe, int field, const npg_vec *vec, const npg_l
     const int64_t n = pts->n;
     const int nc = npg::sample_ncomp(field);
     REQUIRE(out->n == n * nc, "npg_fe_sample: out must hold %d values per point", nc);
-    const HostTables t{fe, fe->u_diri.data(), fe->b_diri.data(), fe->nb};
+    const HostView t = host_view(fe);
 #pragma omp parallel for schedule(static)
     for (int64_t i = 0; i < n; ++i) {
         const int32_t c = pts->cell[(size_t)i];
@@ -1316,10 +1327,7 @@ NPG_API int npg_fe_grid_integrals(npg_fe *fe, npg_locator *loc, const npg_vec *x
     REQUIRE(loc->ctx == fe->ctx && x_inv->ctx == fe->ctx && b->ctx == fe->ctx && axes->ctx == fe->ctx && col->ctx == fe->ctx &&
                 zon->ctx == fe->ctx, "npg_fe_grid_integrals: arguments of different contexts");
     REQUIRE(loc->ncell == fe->ncell, "npg_fe_grid_integrals: the locator was built for another mesh");
-    REQUIRE(x_inv->n == fe->n_inv, "npg_fe_grid_integrals: the flow vector has %lld entries, expected %lld", (long long)x_inv->n,
-            (long long)fe->n_inv);
-    REQUIRE(b->n == fe->n_b, "npg_fe_grid_integrals: the buoyancy vector has %lld entries, expected %lld", (long long)b->n,
-            (long long)fe->n_b);
+    REQUIRE_OK(npg::check_state_vectors("npg_fe_grid_integrals", fe->n_inv, fe->n_b, x_inv->n, b->n));
     REQUIRE(axes->n == nx + ny + nz, "npg_fe_grid_integrals: axes must hold nx + ny + nz doubles");
     REQUIRE(col->n == npg::kGridCol * nx * ny && zon->n == npg::kGridZon * ny * nz,
             "npg_fe_grid_integrals: col must hold %d nx ny and zon %d ny nz doubles", npg::kGridCol, npg::kGridZon);
@@ -1331,7 +1339,7 @@ NPG_API int npg_fe_grid_integrals(npg_fe *fe, npg_locator *loc, const npg_vec *x
         REQUIRE(!err, "npg_fe_grid_integrals: %s (axis %c)", err, "xyz"[d]);
     }
     const npg::BinTables &bt = loc->t;
-    const HostTables t{fe, fe->u_diri.data(), fe->b_diri.data(), fe->nb};
+    const HostView t = host_view(fe);
     auto values = [&](int64_t i, int64_t j, int64_t k, double v[npg::kGridVal]) {
         const double p[3] = {ax[i], ay[j], az[k]};
         int32_t c;
@@ -1383,31 +1391,9 @@ struct npg_integrals {
     std::vector<uint8_t> mask;       // [ncell] or empty
     std::vector<double> part;        // [nchunk][NPG_NINT]
 };
-namespace {
-struct HostShape {       // the engine's shape tables as cell_integrals reads them
-    const double *qw, *N2, *dN2, *Nb, *dNb, *N1;
-};
-struct HostCells {       // and its cell tables ([cell][component])
-    const npg_fe *fe;
-    const double *cz;
-    bool has_nu, has_kh, has_kv;
-    double G(int k, int64_t c) const { return fe->G[(size_t)c * 12 + k]; }
-    double wdet(int64_t c) const { return fe->wdet[(size_t)c]; }
-    double z(int i, int64_t c) const { return cz[(size_t)c * 4 + i]; }
-    double u(const double *x, int l, int64_t c) const { return fval(x, fe->u_diri, fe->cu[(size_t)c * 30 + l]); }
-    double b(const double *x, int i, int64_t c) const { return fval(x, fe->b_diri, fe->cb[(size_t)c * fe->nb + i]); }
-    double nu(int q, int64_t c) const { return fe->coef[0][(size_t)c * fe->nq + q]; }
-    double kh(int q, int64_t c) const { return fe->coef[1][(size_t)c * fe->nq + q]; }
-    double kv(int q, int64_t c) const { return fe->coef[2][(size_t)c * fe->nq + q]; }
-};
-}  // namespace
-
 NPG_API int npg_integrals_create(npg_fe *fe, const double *cell_z, const uint8_t *cell_mask, npg_integrals **out) {
-    REQUIRE(fe && out, "npg_integrals_create: NULL argument");
-    REQUIRE(cell_z, "npg_integrals_create: cell_z is NULL");
+    REQUIRE_OK(npg::check_integrals_create(fe && out, cell_z, fe ? fe->ncell : 0));
     const int64_t nc = fe->ncell;
-    for (int64_t k = 0; k < nc * 4; ++k)
-        REQUIRE(std::isfinite(cell_z[k]), "npg_integrals_create: cell_z[%lld][%d] is not finite", (long long)(k / 4), (int)(k % 4));
     npg_integrals *I = new npg_integrals();
     I->fe = fe;
     I->cz.assign(cell_z, cell_z + nc * 4);
@@ -1421,16 +1407,11 @@ NPG_API int npg_integrals_destroy(npg_integrals *I) {
     return NPG_OK;
 }
 NPG_API int npg_integrals_compute(npg_integrals *I, const npg_vec *x_inv, const npg_vec *b, int full_stress, npg_vec *out) {
-    REQUIRE(I && x_inv && b && out, "npg_integrals_compute: NULL argument");
+    REQUIRE_OK(npg::check_integrals_compute(I, x_inv, b, full_stress, (const npg_vec *)out));
     const npg_fe *fe = I->fe;
-    REQUIRE(x_inv->n == fe->n_inv, "npg_integrals_compute: the flow vector has %lld entries, expected %lld", (long long)x_inv->n,
-            (long long)fe->n_inv);
-    REQUIRE(b->n == fe->n_b, "npg_integrals_compute: the buoyancy vector has %lld entries, expected %lld", (long long)b->n, (long long)fe->n_b);
-    REQUIRE(out->n >= NPG_NINT, "npg_integrals_compute: out holds %lld doubles, needs NPG_NINT = %d", (long long)out->n, NPG_NINT);
-    REQUIRE(full_stress == 0 || full_stress == 1, "npg_integrals_compute: full_stress must be 0 or 1, got %d", full_stress);
     const int64_t nc = fe->ncell, nchunk = (nc + npg::kIntChunk - 1) / npg::kIntChunk;
-    const HostShape s{fe->qw.data(), fe->N2.data(), fe->dN2.data(), fe->Nb.data(), fe->dNb.data(), fe->N1.data()};
-    const HostCells t{fe, I->cz.data(), !fe->coef[0].empty(), !fe->coef[1].empty(), !fe->coef[2].empty()};
+    const HostShape s = host_shape(fe);
+    const npg::CellsYZ<HostView> t{host_view(fe), nullptr, I->cz.data()};
     const uint8_t *mask = I->mask.empty() ? nullptr : I->mask.data();
 #pragma omp parallel for schedule(static)
     for (int64_t k = 0; k < nchunk; ++k) {
@@ -1473,28 +1454,6 @@ struct npg_boundary {
     std::vector<double> coef[npg::kBndNCoef];   // [9][nkept] or empty
     std::vector<double> part;                // [nrows][NPG_NBND]
 };
-namespace {
-struct HostFaces {       // the sorted face tables and the engine's cell tables as face_integrals reads them
-    const npg_boundary *B;
-    const npg_fe *fe;
-    size_t nk;           // faces that count
-    int64_t cell(int64_t f) const { return B->cell[(size_t)f]; }
-    int local(int64_t f) const { return B->local[(size_t)f]; }
-    double area2(int64_t f) const { return B->area2[(size_t)f]; }
-    double n(int a, int64_t f) const { return B->normal[(size_t)a * nk + f]; }
-    double z(int j, int64_t f) const { return B->z[(size_t)j * nk + f]; }
-    bool has(int i) const { return !B->coef[i].empty(); }
-    double coef(int i, int q, int64_t f) const { return B->coef[i][(size_t)q * nk + f]; }
-    double G(int k, int64_t c) const { return fe->G[(size_t)c * 12 + k]; }
-    double u(const double *x, int l, int64_t c) const { return fval(x, fe->u_diri, fe->cu[(size_t)c * 30 + l]); }
-    double p(const double *x, int m, int64_t c) const {
-        const int32_t i = fe->cp[(size_t)c * 4 + m];
-        return i >= 0 ? x[i] : 0.0;          // the pinned vertex of the zero-mean space
-    }
-    double b(const double *x, int i, int64_t c) const { return fval(x, fe->b_diri, fe->cb[(size_t)c * fe->nb + i]); }
-};
-}  // namespace
-
 NPG_API int npg_boundary_create(npg_fe *fe, int64_t nface, const int32_t *face_cell, const uint8_t *face_local, const uint8_t *face_group,
                                 int ngroup, const double *face_xyz, const double *face_normal, const double *face_area2,
                                 const uint8_t *face_mask, npg_boundary **out) {
@@ -1504,13 +1463,9 @@ NPG_API int npg_boundary_create(npg_fe *fe, int64_t nface, const int32_t *face_c
         for (int q = 0; q < fe->nq; ++q) flat = flat && fe->N1[(size_t)q * 4 + 3] == 0.0;
         REQUIRE(!flat, "npg_boundary_create: an embedded 2-D engine is refused (its boundary is made of segments, not of faces)");
     }
-    npg_boundary *B = new npg_boundary();
-    const std::string err = npg::bnd_build_layout(fe->ncell, nface, face_cell, face_local, face_group, ngroup, face_xyz, face_normal,
-                                                  face_area2, face_mask, B->lay);
-    if (!err.empty()) {
-        delete B;
-        REQUIRE(false, "%s", err.c_str());
-    }
+    std::unique_ptr<npg_boundary> B(new npg_boundary());
+    REQUIRE_OK(npg::bnd_build_layout(fe->ncell, nface, face_cell, face_local, face_group, ngroup, face_xyz, face_normal, face_area2, face_mask,
+                                     B->lay));
     B->fe = fe;
     B->nface = nface;
     B->ngroup = ngroup;
@@ -1524,7 +1479,7 @@ NPG_API int npg_boundary_create(npg_fe *fe, int64_t nface, const int32_t *face_c
             B->normal[a * n + i] = face_normal[(size_t)a * nface + f], B->z[a * n + i] = face_xyz[(size_t)(3 * a + 2) * nface + f];
     }
     B->part.assign(B->lay.rows.size() * NPG_NBND, 0.0);
-    *out = B;
+    *out = B.release();
     return NPG_OK;
 }
 NPG_API int npg_boundary_destroy(npg_boundary *B) {
@@ -1559,15 +1514,15 @@ NPG_API int npg_boundary_set_closure(npg_boundary *B, double kappa_c, double N2m
 NPG_API int npg_boundary_compute(npg_boundary *B, const npg_vec *x_inv, const npg_vec *b, int full_stress, npg_vec *out, npg_vec *faces_out) {
     REQUIRE(B && x_inv && b && out, "npg_boundary_compute: NULL argument");
     const npg_fe *fe = B->fe;
-    REQUIRE(x_inv->n == fe->n_inv, "npg_boundary_compute: the flow vector has %lld entries, expected %lld", (long long)x_inv->n,
-            (long long)fe->n_inv);
-    REQUIRE(b->n == fe->n_b, "npg_boundary_compute: the buoyancy vector has %lld entries, expected %lld", (long long)b->n, (long long)fe->n_b);
+    REQUIRE_OK(npg::check_state_vectors("npg_boundary_compute", fe->n_inv, fe->n_b, x_inv->n, b->n));
     REQUIRE(out->n >= (int64_t)B->ngroup * NPG_NBND, "npg_boundary_compute: out holds %lld doubles, needs ngroup * NPG_NBND = %d",
             (long long)out->n, B->ngroup * NPG_NBND);
     REQUIRE(!faces_out || faces_out->n >= B->nface * NPG_NBND, "npg_boundary_compute: faces_out holds %lld doubles, needs NPG_NBND * nface = %lld",
             (long long)faces_out->n, (long long)(B->nface * NPG_NBND));
     REQUIRE(full_stress == 0 || full_stress == 1, "npg_boundary_compute: full_stress must be 0 or 1, got %d", full_stress);
-    const HostFaces t{B, fe, B->lay.orig.size()};
+    npg::FaceTables<HostView> t{host_view(fe), (int64_t)B->lay.orig.size(), B->cell.data(), B->local.data(), B->area2.data(), B->normal.data(),
+                                B->z.data(), {}};
+    for (int i = 0; i < npg::kBndNCoef; ++i) t.coef_[i] = data_or_null(B->coef[i]);
     const int64_t nrows = (int64_t)B->lay.rows.size();
     double *fo = faces_out ? faces_out->d : nullptr;
     if (fo) std::fill(fo, fo + B->nface * NPG_NBND, 0.0);      // faces that do not count keep zeros
@@ -1601,6 +1556,8 @@ NPG_API int npg_boundary_compute(npg_boundary *B, const npg_vec *x_inv, const np
 // quantised terms as 64-bit integers (relaxed atomics on one table, a run of samples in one bin added up first): integer addition is
 // associative, so the table does not depend on the number of threads. ------------------------------------------------------------------
 #include "../csrc/classes_core.h"
+#include "../csrc/mixing_core.h"
+static_assert(NPG_NMIX == npg::kNMix, "NPG_NMIX of the header and kNMix of mixing_core.h must agree");
 static_assert(NPG_NCLS == npg::kNCls, "NPG_NCLS of the header and kNCls of classes_core.h must agree");
 
 struct npg_classes {
@@ -1618,39 +1575,27 @@ struct npg_classes {
     bool kap_set = false;
 };
 namespace {
-struct HostClsCells {    // the engine's cell tables as class_cell_load reads them ([cell][component])
-    const npg_fe *fe;
-    const double *cy, *cz;
-    double G(int k, int64_t c) const { return fe->G[(size_t)c * 12 + k]; }
-    double wdet(int64_t c) const { return fe->wdet[(size_t)c]; }
-    double y(int i, int64_t c) const { return cy[(size_t)c * 4 + i]; }
-    double z(int i, int64_t c) const { return cz[(size_t)c * 4 + i]; }
-    double u(const double *x, int l, int64_t c) const { return fval(x, fe->u_diri, fe->cu[(size_t)c * 30 + l]); }
-    double b(const double *x, int i, int64_t c) const { return fval(x, fe->b_diri, fe->cb[(size_t)c * fe->nb + i]); }
-};
 inline void classes_flush(int64_t *itab, int64_t bin, const int64_t run[NPG_NCLS]) {
     for (int k = 0; k < NPG_NCLS; ++k)
         if (run[k] != 0) __atomic_fetch_add(&itab[bin * NPG_NCLS + k], run[k], __ATOMIC_RELAXED);
 }
-// PASS 1: acc += {|term|, dropped} of cell c; PASS 2: the cell's quantised terms into itab, run by run
-template <int NB, int PASS>
-inline void classes_cell(const npg_classes *K, const HostClsCells &t, const double *xu, const double *xb, double N2, int64_t c, double *acc,
-                         const double *scale, int64_t *itab) {
-    npg::ClassCell<NB> n;
-    npg::class_cell_load<NB>(t, xu, xb, c, n);
-    const int ns = (int)K->wq.size();
-    const int64_t ny = (int64_t)K->y_edges.size(), nb = (int64_t)K->b_edges.size();
+// PASS 1: acc += {|term|, dropped} of cell c; PASS 2: the cell's quantised terms into itab, run by run.  sm: the sampler
+// (csrc/classes_core.h: CensusSampler; csrc/mixing_core.h: MixSampler)
+template <int NB, int PASS, class Sampler>
+inline void class_cell(const npg::ClsRule &r, const npg::CellsYZ<HostView> &t, const Sampler &sm, int64_t c, double *acc, const double *scale,
+                       int64_t *itab) {
+    typename Sampler::template Cell<NB> n;
+    sm.template load<NB>(t, c, n);
     int64_t run[NPG_NCLS] = {0, 0, 0, 0, 0, 0, 0, 0}, cur = -1;
-    for (int s = 0; s < ns; ++s) {
+    for (int s = 0; s < r.ns; ++s) {
         double term[NPG_NCLS];
         int64_t band = 0, cls = 0;
-        const bool ok = npg::class_sample<NB, PASS == 2>(n, &K->lam[(size_t)4 * s], K->wq[(size_t)s], N2, K->y_edges.data(), ny,
-                                                         K->b_edges.data(), nb, &band, &cls, term);
+        const bool ok = sm.template sample<NB, PASS == 2>(t, n, r, s, c, &band, &cls, term);
         if (PASS == 1) {
             if (ok) for (int k = 0; k < NPG_NCLS; ++k) acc[k] += std::fabs(term[k]);
             else acc[NPG_NCLS] += 1.0;
         } else if (ok) {
-            const int64_t bin = band * (nb + 1) + cls;
+            const int64_t bin = band * (r.nb + 1) + cls;
             if (bin != cur) {
                 if (cur >= 0) classes_flush(itab, cur, run);
                 cur = bin;
@@ -1661,35 +1606,53 @@ inline void classes_cell(const npg_classes *K, const HostClsCells &t, const doub
     }
     if (PASS == 2 && cur >= 0) classes_flush(itab, cur, run);
 }
+// the two passes of a class table with the sampler sm: zero, sum per chunk, fold, scale, bin, convert
+template <class Sampler>
+int class_passes(npg_classes *K, const Sampler &sm, npg_vec *table, npg_vec *info) {
+    const npg_fe *fe = K->fe;
+    const int64_t nc = fe->ncell, nchunk = (nc + npg::kClsChunk - 1) / npg::kClsChunk, nent = K->nbins * NPG_NCLS;
+    const npg::ClsRule r{K->lam.data(), K->wq.data(), K->y_edges.data(), K->b_edges.data(), (int)K->wq.size(), (int64_t)K->y_edges.size(),
+                         (int64_t)K->b_edges.size()};
+    const npg::CellsYZ<HostView> t{host_view(fe), K->cy.data(), K->cz.data()};
+    const uint8_t *mask = K->mask.empty() ? nullptr : K->mask.data();
+    int64_t *itab = K->itab.data();
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < nent; ++i) itab[i] = 0;
+#pragma omp parallel for schedule(static)
+    for (int64_t k = 0; k < nchunk; ++k) {
+        double acc[npg::kClsInfo];
+        for (int a = 0; a < npg::kClsInfo; ++a) acc[a] = 0.0;
+        for (int64_t c = k * npg::kClsChunk; c < std::min(nc, (k + 1) * npg::kClsChunk); ++c) {
+            if (mask && !mask[c]) continue;
+            if (fe->nb == 10) class_cell<10, 1>(r, t, sm, c, acc, nullptr, nullptr);
+            else class_cell<4, 1>(r, t, sm, c, acc, nullptr, nullptr);
+        }
+        for (int a = 0; a < npg::kClsInfo; ++a) K->part[(size_t)k * npg::kClsInfo + a] = acc[a];
+    }
+    double scale[NPG_NCLS];
+    for (int a = 0; a < npg::kClsInfo; ++a) {
+        double sum = 0.0;
+        for (int64_t k = 0; k < nchunk; ++k) sum += K->part[(size_t)k * npg::kClsInfo + a];
+        if (a < NPG_NCLS) info->d[1 + a] = sum, scale[a] = npg::class_scale(sum);
+        else info->d[0] = sum;
+    }
+#pragma omp parallel for schedule(static)
+    for (int64_t c = 0; c < nc; ++c) {
+        if (mask && !mask[c]) continue;
+        if (fe->nb == 10) class_cell<10, 2>(r, t, sm, c, nullptr, scale, itab);
+        else class_cell<4, 2>(r, t, sm, c, nullptr, scale, itab);
+    }
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < nent; ++i) table->d[i] = (double)itab[i] / scale[i % NPG_NCLS];
+    return NPG_OK;
+}
 }  // namespace
 
 NPG_API int npg_classes_create(npg_fe *fe, const double *cell_y, const double *cell_z, const uint8_t *cell_mask, const double *rule_lam,
                                const double *rule_w, int ns, const double *y_edges, int64_t ny, const double *b_edges, int64_t nb,
                                npg_classes **out) {
-    REQUIRE(fe && out, "npg_classes_create: NULL argument");
-    REQUIRE(cell_y && cell_z, "npg_classes_create: cell_y or cell_z is NULL");
-    REQUIRE(ns >= 1 && ns <= npg::kClsMaxSamples, "npg_classes_create: 1 .. %d samples per cell, got %d", npg::kClsMaxSamples, ns);
-    REQUIRE(rule_lam && rule_w, "npg_classes_create: rule_lam or rule_w is NULL");
-    REQUIRE(ny >= 0 && nb >= 0 && (ny == 0 || y_edges) && (nb == 0 || b_edges), "npg_classes_create: edges missing or a negative count");
-    REQUIRE(ny < npg::kClsMaxBins && nb < npg::kClsMaxBins && (ny + 1) * (nb + 1) <= npg::kClsMaxBins,
-            "npg_classes_create: ny = %lld and nb = %lld give more than 2^22 bins (ny + 1)(nb + 1)", (long long)ny, (long long)nb);
-    const char *err = npg::check_edges(y_edges, ny);
-    REQUIRE(!err, "npg_classes_create: y_edges %s", err);
-    err = npg::check_edges(b_edges, nb);
-    REQUIRE(!err, "npg_classes_create: b_edges %s", err);
-    double wsum = 0.0;
-    for (int s = 0; s < ns; ++s) {
-        REQUIRE(rule_w[s] > 0.0 && std::isfinite(rule_w[s]), "npg_classes_create: weight %d of the rule is not > 0", s);
-        wsum += rule_w[s];
-        const double *l = rule_lam + 4 * s;
-        REQUIRE(std::fabs((l[0] + l[1]) + (l[2] + l[3]) - 1.0) <= 1e-12, "npg_classes_create: lam row %d of the rule does not sum to 1", s);
-    }
-    REQUIRE(std::fabs(wsum - 1.0) <= 1e-12, "npg_classes_create: the weights of the rule sum to %.17g, not 1", wsum);
+    REQUIRE_OK(npg::check_classes_create(fe && out, fe ? fe->ncell : 0, cell_y, cell_z, rule_lam, rule_w, ns, y_edges, ny, b_edges, nb));
     const int64_t nc = fe->ncell;
-    for (int64_t k = 0; k < nc * 4; ++k) {
-        REQUIRE(std::isfinite(cell_y[k]), "npg_classes_create: cell_y[%lld][%d] is not finite", (long long)(k / 4), (int)(k % 4));
-        REQUIRE(std::isfinite(cell_z[k]), "npg_classes_create: cell_z[%lld][%d] is not finite", (long long)(k / 4), (int)(k % 4));
-    }
     double qsum = 0.0;                       // the measure of a sample is w[s] wdet qsum, qsum from the engine's own weights
     for (double w : fe->qw) qsum += w;
     npg_classes *K = new npg_classes();
@@ -1713,101 +1676,17 @@ NPG_API int npg_classes_destroy(npg_classes *K) {
     return NPG_OK;
 }
 NPG_API int npg_classes_compute(npg_classes *K, const npg_vec *x_inv, const npg_vec *b, double N2, npg_vec *table, npg_vec *info) {
-    REQUIRE(K && x_inv && b && table && info, "npg_classes_compute: NULL argument");
-    const npg_fe *fe = K->fe;
-    REQUIRE(x_inv->n == fe->n_inv, "npg_classes_compute: the flow vector has %lld entries, expected %lld", (long long)x_inv->n,
-            (long long)fe->n_inv);
-    REQUIRE(b->n == fe->n_b, "npg_classes_compute: the buoyancy vector has %lld entries, expected %lld", (long long)b->n, (long long)fe->n_b);
-    REQUIRE(table->n >= K->nbins * NPG_NCLS, "npg_classes_compute: table holds %lld doubles, needs (ny + 1)(nb + 1) NPG_NCLS = %lld",
-            (long long)table->n, (long long)(K->nbins * NPG_NCLS));
-    REQUIRE(info->n >= 1 + NPG_NCLS, "npg_classes_compute: info holds %lld doubles, needs 1 + NPG_NCLS = %d", (long long)info->n, 1 + NPG_NCLS);
-    REQUIRE(std::isfinite(N2), "npg_classes_compute: N2 is not finite");
-    const int64_t nc = fe->ncell, nchunk = (nc + npg::kClsChunk - 1) / npg::kClsChunk, nent = K->nbins * NPG_NCLS;
-    const HostClsCells t{fe, K->cy.data(), K->cz.data()};
-    const uint8_t *mask = K->mask.empty() ? nullptr : K->mask.data();
-    const double *xu = x_inv->d, *xb = b->d;
-    int64_t *itab = K->itab.data();
-#pragma omp parallel for schedule(static)
-    for (int64_t i = 0; i < nent; ++i) itab[i] = 0;
-#pragma omp parallel for schedule(static)
-    for (int64_t k = 0; k < nchunk; ++k) {
-        double acc[npg::kClsInfo];
-        for (int a = 0; a < npg::kClsInfo; ++a) acc[a] = 0.0;
-        for (int64_t c = k * npg::kClsChunk; c < std::min(nc, (k + 1) * npg::kClsChunk); ++c) {
-            if (mask && !mask[c]) continue;
-            if (fe->nb == 10) classes_cell<10, 1>(K, t, xu, xb, N2, c, acc, nullptr, nullptr);
-            else classes_cell<4, 1>(K, t, xu, xb, N2, c, acc, nullptr, nullptr);
-        }
-        for (int a = 0; a < npg::kClsInfo; ++a) K->part[(size_t)k * npg::kClsInfo + a] = acc[a];
-    }
-    double scale[NPG_NCLS];
-    for (int a = 0; a < npg::kClsInfo; ++a) {
-        double sum = 0.0;
-        for (int64_t k = 0; k < nchunk; ++k) sum += K->part[(size_t)k * npg::kClsInfo + a];
-        if (a < NPG_NCLS) info->d[1 + a] = sum, scale[a] = npg::class_scale(sum);
-        else info->d[0] = sum;
-    }
-#pragma omp parallel for schedule(static)
-    for (int64_t c = 0; c < nc; ++c) {
-        if (mask && !mask[c]) continue;
-        if (fe->nb == 10) classes_cell<10, 2>(K, t, xu, xb, N2, c, nullptr, scale, itab);
-        else classes_cell<4, 2>(K, t, xu, xb, N2, c, nullptr, scale, itab);
-    }
-#pragma omp parallel for schedule(static)
-    for (int64_t i = 0; i < nent; ++i) table->d[i] = (double)itab[i] / scale[i % NPG_NCLS];
-    return NPG_OK;
+    REQUIRE_OK(npg::check_classes_compute(K, x_inv, b, N2, (const npg_vec *)table, (const npg_vec *)info));
+    return class_passes(K, npg::CensusSampler{x_inv->d, b->d, N2}, table, info);
 }
 
-// ---- water-mass transformation by mixing (csrc/classes.hip: k_mixing_scan / k_mixing_bin on the host): the per-sample arithmetic is
-// the SAME code (csrc/mixing_core.h); the passes, the chunks, the scales and the integer table are those of npg_classes_compute ------
-#include "../csrc/mixing_core.h"
-static_assert(NPG_NMIX == npg::kNMix, "NPG_NMIX of the header and kNMix of mixing_core.h must agree");
-namespace {
-template <int NB, int PASS>
-inline void mixing_cell(const npg_classes *K, const HostClsCells &t, const double *xb, double N2, const npg::MixClosure &cl, int64_t c,
-                        double *acc, const double *scale, int64_t *itab) {
-    npg::MixCell<NB> n;
-    npg::mix_cell_load<NB>(t, xb, c, n);
-    const int ns = (int)K->wq.size();
-    const int64_t ny = (int64_t)K->y_edges.size(), nb = (int64_t)K->b_edges.size();
-    int64_t run[NPG_NMIX] = {0, 0, 0, 0, 0, 0, 0, 0}, cur = -1;
-    for (int s = 0; s < ns; ++s) {
-        double term[NPG_NMIX];
-        int64_t band = 0, cls = 0;
-        const double kh = K->kh.empty() ? K->kh_s : K->kh[(size_t)c * ns + s], kv0 = K->kv0.empty() ? K->kv0_s : K->kv0[(size_t)c * ns + s];
-        const bool ok = npg::mix_sample<NB, PASS == 2>(n, &K->lam[(size_t)4 * s], K->wq[(size_t)s], N2, kh, kv0, cl, K->y_edges.data(), ny,
-                                                       K->b_edges.data(), nb, &band, &cls, term);
-        if (PASS == 1) {
-            if (ok) for (int k = 0; k < NPG_NMIX; ++k) acc[k] += std::fabs(term[k]);
-            else acc[NPG_NMIX] += 1.0;
-        } else if (ok) {
-            const int64_t bin = band * (nb + 1) + cls;
-            if (bin != cur) {
-                if (cur >= 0) classes_flush(itab, cur, run);
-                cur = bin;
-                for (int k = 0; k < NPG_NMIX; ++k) run[k] = 0;
-            }
-            for (int k = 0; k < NPG_NMIX; ++k) run[k] += npg::class_quantise(term[k], scale[k]);
-        }
-    }
-    if (PASS == 2 && cur >= 0) classes_flush(itab, cur, run);
-}
-}  // namespace
-
+// ---- water-mass transformation by mixing (csrc/classes.hip with the mixing sampler): the per-sample arithmetic is the SAME code
+// (csrc/mixing_core.h); the passes, the chunks, the scales and the integer table are those of npg_classes_compute (class_passes) ------
 NPG_API int npg_classes_set_diffusivity(npg_classes *K, const double *kappa_h, double kappa_h_scalar, const double *kappa_v0,
                                         double kappa_v0_scalar) {
-    REQUIRE(K, "npg_classes_set_diffusivity: NULL argument");
-    const int64_t nc = K->fe->ncell;
-    const int ns = (int)K->wq.size();
-    const char *err = kappa_h ? nullptr : npg::check_diffusivity(kappa_h_scalar);
-    REQUIRE(!err, "npg_classes_set_diffusivity: the scalar kappa_h %s, got %.17g", err, kappa_h_scalar);
-    err = kappa_v0 ? nullptr : npg::check_diffusivity(kappa_v0_scalar);
-    REQUIRE(!err, "npg_classes_set_diffusivity: the scalar kappa_v0 %s, got %.17g", err, kappa_v0_scalar);
-    const double *src[2] = {kappa_h, kappa_v0};
-    for (int t = 0; t < 2; ++t)
-        for (int64_t i = 0; src[t] && i < nc * ns; ++i)
-            REQUIRE(!npg::check_diffusivity(src[t][i]), "npg_classes_set_diffusivity: %s[%lld][%d] must be finite and >= 0, got %.17g",
-                    t ? "kappa_v0" : "kappa_h", (long long)(i / ns), (int)(i % ns), src[t][i]);
+    const int ns = K ? (int)K->wq.size() : 1;
+    const int64_t nc = K ? K->fe->ncell : 0;
+    REQUIRE_OK(npg::check_classes_set_diffusivity(K != nullptr, nc * ns, ns, kappa_h, kappa_h_scalar, kappa_v0, kappa_v0_scalar));
     if (kappa_h) K->kh.assign(kappa_h, kappa_h + nc * ns);
     else K->kh.clear();
     if (kappa_v0) K->kv0.assign(kappa_v0, kappa_v0 + nc * ns);
@@ -1819,54 +1698,10 @@ NPG_API int npg_classes_set_diffusivity(npg_classes *K, const double *kappa_h, d
 
 NPG_API int npg_classes_mixing(npg_classes *K, const npg_vec *b, double N2, double kappa_c, double N2min, double alpha, double N2c,
                                npg_vec *table, npg_vec *info) {
-    REQUIRE(K && b && table && info, "npg_classes_mixing: NULL argument");
-    REQUIRE(K->kap_set, "npg_classes_mixing: no diffusivities: call npg_classes_set_diffusivity first");
-    const npg_fe *fe = K->fe;
-    REQUIRE(b->n == fe->n_b, "npg_classes_mixing: the buoyancy vector has %lld entries, expected %lld", (long long)b->n, (long long)fe->n_b);
-    REQUIRE(table->n >= K->nbins * NPG_NMIX, "npg_classes_mixing: table holds %lld doubles, needs (ny + 1)(nb + 1) NPG_NMIX = %lld",
-            (long long)table->n, (long long)(K->nbins * NPG_NMIX));
-    REQUIRE(info->n >= 1 + NPG_NMIX, "npg_classes_mixing: info holds %lld doubles, needs 1 + NPG_NMIX = %d", (long long)info->n, 1 + NPG_NMIX);
-    REQUIRE(!npg::check_diffusivity(N2), "npg_classes_mixing: N2 must be finite and >= 0, got %.17g", N2);
-    REQUIRE(!npg::check_diffusivity(kappa_c), "npg_classes_mixing: kappa_c must be finite and >= 0, got %.17g", kappa_c);
-    REQUIRE(!npg::check_diffusivity(alpha), "npg_classes_mixing: alpha must be finite and >= 0, got %.17g", alpha);
-    REQUIRE(!npg::check_diffusivity(N2c), "npg_classes_mixing: N2c must be finite and >= 0, got %.17g", N2c);
-    REQUIRE(!(kappa_c > 0.0) || N2min > 0.0, "npg_classes_mixing: kappa_c > 0 needs N2min > 0, got %.17g", N2min);
-    REQUIRE(b->ctx == fe->ctx && table->ctx == fe->ctx && info->ctx == fe->ctx, "npg_classes_mixing: arguments of different contexts");
     const npg::MixClosure cl{kappa_c, N2min, alpha, N2c};
-    const int64_t nc = fe->ncell, nchunk = (nc + npg::kClsChunk - 1) / npg::kClsChunk, nent = K->nbins * NPG_NMIX;
-    const HostClsCells t{fe, K->cy.data(), K->cz.data()};
-    const uint8_t *mask = K->mask.empty() ? nullptr : K->mask.data();
-    const double *xb = b->d;
-    int64_t *itab = K->itab.data();
-#pragma omp parallel for schedule(static)
-    for (int64_t i = 0; i < nent; ++i) itab[i] = 0;
-#pragma omp parallel for schedule(static)
-    for (int64_t k = 0; k < nchunk; ++k) {
-        double acc[npg::kClsInfo];
-        for (int a = 0; a < npg::kClsInfo; ++a) acc[a] = 0.0;
-        for (int64_t c = k * npg::kClsChunk; c < std::min(nc, (k + 1) * npg::kClsChunk); ++c) {
-            if (mask && !mask[c]) continue;
-            if (fe->nb == 10) mixing_cell<10, 1>(K, t, xb, N2, cl, c, acc, nullptr, nullptr);
-            else mixing_cell<4, 1>(K, t, xb, N2, cl, c, acc, nullptr, nullptr);
-        }
-        for (int a = 0; a < npg::kClsInfo; ++a) K->part[(size_t)k * npg::kClsInfo + a] = acc[a];
-    }
-    double scale[NPG_NMIX];
-    for (int a = 0; a < npg::kClsInfo; ++a) {
-        double sum = 0.0;
-        for (int64_t k = 0; k < nchunk; ++k) sum += K->part[(size_t)k * npg::kClsInfo + a];
-        if (a < NPG_NMIX) info->d[1 + a] = sum, scale[a] = npg::class_scale(sum);
-        else info->d[0] = sum;
-    }
-#pragma omp parallel for schedule(static)
-    for (int64_t c = 0; c < nc; ++c) {
-        if (mask && !mask[c]) continue;
-        if (fe->nb == 10) mixing_cell<10, 2>(K, t, xb, N2, cl, c, nullptr, scale, itab);
-        else mixing_cell<4, 2>(K, t, xb, N2, cl, c, nullptr, scale, itab);
-    }
-#pragma omp parallel for schedule(static)
-    for (int64_t i = 0; i < nent; ++i) table->d[i] = (double)itab[i] / scale[i % NPG_NMIX];
-    return NPG_OK;
+    REQUIRE_OK(npg::check_classes_mixing(K, b, N2, cl, (const npg_vec *)table, (const npg_vec *)info));
+    const npg::MixSampler sm{data_or_null(K->kh), data_or_null(K->kv0), K->kh_s, K->kv0_s, cl, b->d, N2};
+    return class_passes(K, sm, table, info);
 }
 
 // ---- Lagrangian particles in the flow (csrc/particles.hip on the host): the RK4 step, the remembered cell, the periodic wrap and the
@@ -1941,7 +1776,7 @@ NPG_API int npg_particles_advance(npg_particles *P, npg_fe *fe, npg_locator *loc
     const char *err = npg::check_particle_call(s0, s1, dt, nsub);
     REQUIRE(!err, "npg_particles_advance: %s", err);
     const npg::ParticleCall call = npg::make_particle_call(P->t, s0, s1, dt, nsub);
-    const HostTables t{fe, fe->u_diri.data(), fe->b_diri.data(), fe->nb};
+    const HostView t = host_view(fe);
     const npg::BinTables &bt = loc->t;
     const npg::ParticleMesh m{bt.grid, bt.bin_ptr.data(), bt.bin_cells.data(), bt.geo.data(), {P->L[0], P->L[1], P->L[2]}};
     const bool blend = x_a->d != x_b->d;
@@ -2016,7 +1851,7 @@ NPG_API int npg_particles_walk(npg_particles *P, npg_fe *fe, npg_locator *loc, c
                 "shift on it - a walked particle crosses a seam through the table", a, P->L[a], P->wall_axis[a] ? "a" : "no");
     const npg::ParticleCall call = npg::make_particle_call(P->t, s0, s1, dt, nsub);
     const uint64_t step0 = P->step;
-    const HostTables t{fe, fe->u_diri.data(), fe->b_diri.data(), fe->nb};
+    const HostView t = host_view(fe);
     const npg::BinTables &bt = loc->t;
     const npg::ParticleMesh m{bt.grid, bt.bin_ptr.data(), bt.bin_cells.data(), bt.geo.data(), {P->L[0], P->L[1], P->L[2]}};
     const bool blend = x_a->d != x_b->d, diffuse = P->kappa_ncell >= 0;
@@ -2148,15 +1983,12 @@ NPG_API int npg_surfaces_compute(npg_surfaces *S, const npg_vec *x_inv, const np
     REQUIRE(x_inv->ctx == S->ctx && b->ctx == S->ctx && out->ctx == S->ctx && cols->ctx == S->ctx,
             "npg_surfaces_compute: arguments of different contexts");
     const npg_fe *fe = S->fe;
-    REQUIRE(x_inv->n == fe->n_inv, "npg_surfaces_compute: the flow vector has %lld entries, expected %lld", (long long)x_inv->n,
-            (long long)fe->n_inv);
-    REQUIRE(b->n == fe->n_b, "npg_surfaces_compute: the buoyancy vector has %lld entries, expected %lld", (long long)b->n,
-            (long long)fe->n_b);
+    REQUIRE_OK(npg::check_state_vectors("npg_surfaces_compute", fe->n_inv, fe->n_b, x_inv->n, b->n));
     REQUIRE(out->n == (int64_t)npg::kNSurf * nlev * S->ncol && cols->n == (int64_t)npg::kNSurfCol * S->ncol,
             "npg_surfaces_compute: out must hold %d nlev ncol = %lld and cols %d ncol = %lld entries, got %lld and %lld", npg::kNSurf,
             (long long)npg::kNSurf * nlev * S->ncol, npg::kNSurfCol, (long long)npg::kNSurfCol * S->ncol, (long long)out->n,
             (long long)cols->n);
-    const HostTables t{fe, fe->u_diri.data(), fe->b_diri.data(), fe->nb};
+    const HostView t = host_view(fe);
     const npg::SurfaceColumns sc{S->t.col_ptr.data(), S->t.seg_cell.data(), S->t.seg_ztop.data(), S->t.seg_zbot.data(), S->xy.data(),
                                  S->loc->t.geo.data(), S->ncol};
     std::vector<int32_t> cross((size_t)nlev * (size_t)S->ncol);
@@ -2182,19 +2014,6 @@ struct npg_tracers {
     std::vector<uint8_t> lift;
 };
 namespace {
-struct HostTrShape {     // the engine's shape tables as cell_tracers reads them
-    const double *qw, *N2, *Nb, *dNb;
-};
-struct HostTrCells {     // and its cell tables ([cell][component])
-    const npg_fe *fe;
-    double G(int k, int64_t c) const { return fe->G[(size_t)c * 12 + k]; }
-    double wdet(int64_t c) const { return fe->wdet[(size_t)c]; }
-    double u(const double *x, int l, int64_t c) const { return fval(x, fe->u_diri, fe->cu[(size_t)c * 30 + l]); }
-    int32_t cb(int i, int64_t c) const { return fe->cb[(size_t)c * fe->nb + i]; }
-    double kh(int q, int64_t c) const { return fe->coef[1][(size_t)c * fe->nq + q]; }
-    double kv(int q, int64_t c) const { return fe->coef[2][(size_t)c * fe->nq + q]; }
-    size_t loc(int i, int64_t c) const { return (size_t)c * fe->nb + i; }
-};
 struct HostTrVel {       // a cell's velocities at the quadrature points
     double a[3 * npg::kTrMaxQ];
     double &operator()(int j) { return a[j]; }
@@ -2261,8 +2080,8 @@ NPG_API int npg_tracers_rhs(npg_tracers *T, int scheme, double dt, double theta,
     }
     REQUIRE(!lift || (!fe->coef[1].empty() && !fe->coef[2].empty()),
             "npg_tracers_rhs: a tracer has non-zero Dirichlet values but the coefficients kappa_h / kappa_v have not been set");
-    const HostTrShape s{fe->qw.data(), fe->N2.data(), fe->Nb.data(), fe->dNb.data()};
-    const HostTrCells t{fe};
+    const HostShape s = host_shape(fe);
+    const npg::TracerCells<HostView> t{host_view(fe)};
     const npg::TracerSet ts{K, nb, T->n_diri, nc * fe->nb, c->d, c_prev->d, T->diri.data(), T->gamma.data(), T->source.data(), T->loc.data()};
     const bool bdf2 = scheme == NPG_BDF2;
 #pragma omp parallel for schedule(static)

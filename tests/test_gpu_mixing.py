@@ -1,8 +1,8 @@
-"""Water-mass transformation by mixing (BuoyancyClasses.mixing) on the GPU (libnupgcm_hip.so: k_mixing_scan / k_classes_fold /
-k_mixing_bin / k_classes_convert): the restatement, the bounds and the cases of tests/test_mixing.py through the device library, and in
+"""Water-mass transformation by mixing (BuoyancyClasses.mixing) on the GPU (libnupgcm_hip.so: k_class_scan / k_classes_fold /
+k_class_bin / k_classes_convert with the MixSampler): the restatement, the bounds and the cases of tests/test_mixing.py through the device library, and in
 addition the device table against the host library's on the same state.  bowl3D h = 0.1 has 4259 = 16 x 256 + 163 cells (several
 workgroups, a ragged last one), the 2-D bowl 173 (fewer than one workgroup).  Not reached at these sizes: the grid-stride wrap (more
-than 1024 workgroups' worth of cells); the loop text is k_classes_scan's."""
+than 1024 workgroups' worth of cells); the loop text is the census's (one kernel template for both samplers)."""
 import pytest
 
 import nupgcm_amd as npg

@@ -1,5 +1,5 @@
-"""The flow binned into (latitude band, buoyancy class) (nupgcm_amd.watermass) on the GPU (libnupgcm_hip.so: k_classes_scan /
-k_classes_fold / k_classes_bin / k_classes_convert): the restatement, the bounds and the cases of tests/test_watermass.py through the
+"""The flow binned into (latitude band, buoyancy class) (nupgcm_amd.watermass) on the GPU (libnupgcm_hip.so: k_class_scan /
+k_classes_fold / k_class_bin / k_classes_convert with the CensusSampler): the restatement, the bounds and the cases of tests/test_watermass.py through the
 device library, and in addition the device table against the host library's on the same state.  bowl3D h = 0.1 has 4259 = 16 x 256 + 163
 cells (several workgroups, a ragged last one), the 2-D bowl 173 (fewer than one workgroup)."""
 import pytest

@@ -1,5 +1,5 @@
 """Times of the (latitude band, buoyancy class) table on the bench mesh (bowl3D h = 0.02), 64 x 64 bins, level = 1, after a warm-up call:
-  * npg_classes_compute (memset + k_classes_scan + k_classes_fold + k_classes_bin + k_classes_convert) by device events, and the wall
+  * npg_classes_compute (memset + k_class_scan + k_classes_fold + k_class_bin + k_classes_convert) by device events, and the wall
     time of BuoyancyClasses.compute() (the launches and the download of the table);
   * next to it, in the same process and on the same state, npg_integrals_compute by events: the yardstick (11 points x 15 channels
     against 8 samples x 8 channels, one pass against two);

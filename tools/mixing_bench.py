@@ -1,6 +1,6 @@
 """Times of the mixing table (npg_classes_mixing) on the bench mesh (bowl3D h = 0.02), 64 x 64 bins, level = 1, after a warm-up
 call, by device events, best and median of --reps:
-  * npg_classes_mixing (memset + k_mixing_scan + k_classes_fold + k_mixing_bin + k_classes_convert) with the closure off and with it on
+  * npg_classes_mixing (memset + k_class_scan + k_classes_fold + k_class_bin + k_classes_convert) with the closure off and with it on
     (the difference is the cost of the tanh and the arithmetic around it), the diffusivities the model's own functions as tables;
   * the closure-off call with scalar diffusivities: what reading the two [ns][ncell] tables costs;
   * npg_classes_compute in the same process and on the same state: the yardstick.  The expectation to confirm or refute: the
