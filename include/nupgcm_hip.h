@@ -111,6 +111,8 @@ int npg_csr_zero_values(npg_csr *A);
 /* out = a*X + b*(Y + Z) on identical patterns: `A = M + theta*(Kh + Kv)` (src/evolution.jl:144,162; src/model.jl:254)
  * done on the device instead of a host SparseMatrixCSC add + re-upload */
 int npg_csr_combine(npg_csr *out, double a, const npg_csr *X, double b, const npg_csr *Y, const npg_csr *Z);
+/* out += a*X on identical patterns (plain CSR): the restoring term `A += dt*S` of the evolution's left-hand side */
+int npg_csr_axpy(npg_csr *out, double a, const npg_csr *X);
 /* Store the velocity block of A_inversion node by node.  With constant viscosity node q couples to node c through one
  * friction number K (the x-x, y-y and z-z entries) and one Coriolis number C (x-y entry, -C for y-x)
  * (src/inversion.jl:183-192).  The ordering of nupgcm_amd.fe puts first the n_full nodes with all three components free
@@ -615,6 +617,40 @@ int npg_boundary_set_coeff(npg_boundary *B, int which, const double *table);
 int npg_boundary_set_closure(npg_boundary *B, double kappa_c, double N2min, double alpha, double N2c);
 int npg_boundary_compute(npg_boundary *B, const npg_vec *x_inv, const npg_vec *b, int full_stress, npg_vec *out, npg_vec *faces_out);
 int npg_boundary_destroy(npg_boundary *B);
+
+/* ---- time-dependent surface forcing and a restoring buoyancy condition (new work: the reference's forcings are set-up constants) --
+ * The wind part of the inversion's right-hand side and the flux vector of the evolution, recomputed on the device for the time level
+ * being solved, and the surface mass matrix of a restoring condition flux = gamma (b* - b) (csrc/forcing_core.h).
+ * The handle holds the forced faces (cell, local face, twice the area from the face's own nodes - as npg_boundary_create takes
+ * them), keyframe tables [nkey][9][nface] per series (NPG_FRC_TAUX, _TAUY, _FLUX, _TARGET) at the nine points of the face rule of
+ * npg_boundary_compute, and a static table gamma [9][nface] (>= 0).  Tables are copied; NULL removes one; every value is finite.
+ *   npg_forcing_apply: the value of series c at a point is (1 - w[c]) table[key[c]] + w[c] table[key[c] + 1] (behind the last
+ *   keyframe: table[0]); w[c] = 0 reads one keyframe and returns its bits.  key and w have NPG_FRC_NSERIES entries; those of a
+ *   series that is not set are ignored.  Then
+ *       b_inv_out[r]    = b_inv_base[r] + alpha int (tau_x | tau_y) phi_r dGamma     on the u_x | u_y rows the faces touch, else b_inv_base[r]
+ *       rhs_flux_out[r] = alpha int (F + gamma b*) phi_r dGamma                      on the buoyancy rows the faces touch, else 0
+ *   with the face functions of the space (P2 velocity; P2 or P1 buoyancy) and Dirichlet DoFs skipped.  Two launches, sums in one
+ *   fixed order, no atomics: the same bits on every call.  nface = 0 is legal: the outputs are the base and zeros.
+ *   npg_forcing_surface_matrix: S = scale int gamma phi_i phi_j dGamma on the pattern given at create (entries no face touches: 0);
+ *   S is symmetric to the bits.  A position missing in the pattern is an error of create.
+ * Validation (NPG_EINVAL + message) happens before anything is launched.  The engine must outlive the handle; an embedded 2-D
+ * engine is refused. */
+typedef struct npg_forcing npg_forcing;
+#define NPG_FRC_NSERIES 4
+#define NPG_FRC_TAUX 0
+#define NPG_FRC_TAUY 1
+#define NPG_FRC_FLUX 2
+#define NPG_FRC_TARGET 3
+int npg_forcing_create(npg_fe *fe, int64_t nface, const int32_t *face_cell, const uint8_t *face_local, const double *face_area2,
+                       const npg_csr *pattern, npg_forcing **out);
+int npg_forcing_set_series(npg_forcing *F, int which, int nkey, const double *tables);
+int npg_forcing_set_gamma(npg_forcing *F, const double *table);
+int npg_forcing_apply(npg_forcing *F, const int32_t *key, const double *w, double alpha, const npg_vec *b_inv_base, npg_vec *b_inv_out,
+                      npg_vec *rhs_flux_out);
+int npg_forcing_surface_matrix(npg_forcing *F, double scale, npg_csr *S);
+int npg_forcing_info(const npg_forcing *F, int64_t *nface, int64_t *wind_slots, int64_t *flux_slots, int64_t *matrix_entries,
+                     int64_t *matrix_slots);
+int npg_forcing_destroy(npg_forcing *F);
 
 /* ---- the state binned into (latitude band, buoyancy class) (new work: the reference overlays isopycnals on a z-coordinate psi) --
  * A joint table [ny + 1][nb + 1][NPG_NCLS] over the cells of the mesh (csrc/classes_core.h).

@@ -7,6 +7,7 @@ from .architectures import (CPU, GPU, AbstractArchitecture, DeviceCSR, DeviceILU
                             print_memory_status, vector_type)
 from .boundary import BoundaryFluxes, BoundaryIntegrals, BoundaryMaps, BoundaryRecorder
 from .evolution import EvolutionToolkit, collect_evolution_LHS, evolution_parameter
+from .forcing import ForcingSeries, SurfaceForcing, series_key_weight
 from .fe import DoFHandler, FEData, Mesh, Spaces, get_n_dofs
 from .inputs import (ConvectionParameterization, EddyParameterization, Forcings, Parameters, SurfaceDirichletBC,
                      SurfaceFluxBC)

@@ -164,6 +164,9 @@ def _declare(L, partial=False):
         "npg_boundary_create": [P, I64, VP, VP, VP, C.c_int, VP, VP, VP, VP, PP], "npg_boundary_destroy": [P],
         "npg_boundary_set_coeff": [P, C.c_int, VP], "npg_boundary_set_closure": [P, D, D, D, D],
         "npg_boundary_compute": [P, P, P, C.c_int, P, P],
+        "npg_forcing_create": [P, I64, VP, VP, VP, P, PP], "npg_forcing_destroy": [P], "npg_forcing_set_series": [P, C.c_int, C.c_int, VP],
+        "npg_forcing_set_gamma": [P, VP], "npg_forcing_apply": [P, VP, VP, D, P, P, P], "npg_forcing_surface_matrix": [P, D, P],
+        "npg_forcing_info": [P] + [C.POINTER(I64)] * 5, "npg_csr_axpy": [P, D, P],
         "npg_classes_create": [P, VP, VP, VP, VP, VP, C.c_int, VP, I64, VP, I64, PP], "npg_classes_destroy": [P],
         "npg_classes_compute": [P, P, P, D, P, P],
         "npg_classes_set_diffusivity": [P, VP, D, VP, D], "npg_classes_mixing": [P, P, D, D, D, D, D, P, P],
@@ -238,6 +241,8 @@ NPG_SAMPLE_U, NPG_SAMPLE_P, NPG_SAMPLE_B, NPG_SAMPLE_GRAD_B = 1, 2, 3, 4
 NPG_NINT = 15
 NPG_NBND = 24
 NPG_BND_NU, NPG_BND_KH, NPG_BND_KV, NPG_BND_TAUX, NPG_BND_TAUY, NPG_BND_FLUX = range(6)
+NPG_FRC_NSERIES = 4
+NPG_FRC_TAUX, NPG_FRC_TAUY, NPG_FRC_FLUX, NPG_FRC_TARGET = range(4)
 NPG_NCLS = 8
 NPG_NMIX = 8
 NPG_NSURF = 9

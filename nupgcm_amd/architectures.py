@@ -476,6 +476,11 @@ class DeviceCSR:
         L.check(L.lib().npg_csr_combine(self.h, float(a), X.h, float(b), Y.h, Z.h))
         return self
 
+    def axpy(self, a, X):
+        """self += a X on a shared pattern (npg_csr_axpy)"""
+        L.check(L.lib().npg_csr_axpy(self.h, float(a), X.h))
+        return self
+
     def gather_values(self, src, index):
         """self.val[k] = src.val[index[k]] (npg_csr_gather_values): this matrix holds a fixed subset of src's entries"""
         L.check(L.lib().npg_csr_gather_values(self.h, src.h, index.h))

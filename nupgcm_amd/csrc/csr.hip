@@ -646,6 +646,10 @@ __global__ void k_combine(double *out, double a, const double *X, double b, cons
         out[i] = a * X[i] + b * (Y[i] + Z[i]);
 }
 
+__global__ void k_axpy_values(double *__restrict__ out, double a, const double *__restrict__ X, int64_t n) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = out[i] + a * X[i];
+}
+
 __global__ void k_gather_values(double *__restrict__ dst, const double *__restrict__ src, const int64_t *__restrict__ idx,
                                 int64_t n) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
@@ -1661,6 +1665,20 @@ NPG_API int npg_csr_combine(npg_csr *out, double a, const npg_csr *X, double b, 
     const int grid = (int)std::min<int64_t>(2048, (out->nnz + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(k_combine, dim3(std::max(grid, 1)), dim3(kBlock), 0, out->ctx->stream, out->val, a, X->val, b,
                        Y->val, Z->val, out->nnz);
+    NPG_HIP(hipGetLastError());
+    return csr_repack(out);
+}
+
+// out += a X on identical patterns (the restoring term dt S of the evolution's left-hand side)
+NPG_API int npg_csr_axpy(npg_csr *out, double a, const npg_csr *X) {
+    NPG_REQUIRE(out && X, "npg_csr_axpy: NULL argument");
+    NPG_REQUIRE(out != X && out->val != X->val, "npg_csr_axpy: out must not be X");
+    NPG_REQUIRE(out->ctx == X->ctx && out->nnz == X->nnz && out->m == X->m && out->n == X->n, "npg_csr_axpy: operands must share one sparsity pattern");
+    NPG_REQUIRE_PLAIN(out, "npg_csr_axpy");
+    NPG_REQUIRE_NO_PACKS(out, "npg_csr_axpy");
+    NPG_REQUIRE_PLAIN(X, "npg_csr_axpy");
+    const int grid = (int)std::min<int64_t>(2048, (out->nnz + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_axpy_values, dim3(std::max(grid, 1)), dim3(kBlock), 0, out->ctx->stream, out->val, a, X->val, out->nnz);
     NPG_HIP(hipGetLastError());
     return csr_repack(out);
 }

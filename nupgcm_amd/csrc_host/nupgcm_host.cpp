@@ -392,6 +392,13 @@ NPG_API int npg_csr_combine(npg_csr *out, double a, const npg_csr *X, double b, 
     for (int64_t k = 0; k < out->nnz; ++k) out->val[(size_t)k] = a * X->val[(size_t)k] + b * (Y->val[(size_t)k] + Z->val[(size_t)k]);
     return NPG_OK;
 }
+NPG_API int npg_csr_axpy(npg_csr *out, double a, const npg_csr *X) {
+    REQUIRE(out && X, "npg_csr_axpy: NULL argument");
+    REQUIRE(out != X, "npg_csr_axpy: out must not be X");
+    REQUIRE(out->ctx == X->ctx && out->nnz == X->nnz && out->m == X->m && out->n == X->n, "npg_csr_axpy: operands must share one sparsity pattern");
+    for (int64_t k = 0; k < out->nnz; ++k) out->val[(size_t)k] = out->val[(size_t)k] + a * X->val[(size_t)k];
+    return NPG_OK;
+}
 NPG_API int npg_csr_inv_diag(const npg_csr *A, npg_vec *d) {
     REQUIRE(A && d && A->m <= A->n && d->n == A->m, "npg_csr_inv_diag: shape mismatch");
     for (int64_t r = 0; r < A->m; ++r) {
@@ -1548,6 +1555,121 @@ NPG_API int npg_boundary_compute(npg_boundary *B, const npg_vec *x_inv, const np
             for (int64_t r = B->lay.row0[g]; r < B->lay.row0[g + 1]; ++r) sum += B->part[(size_t)r * NPG_NBND + a];
             out->d[(size_t)g * NPG_NBND + a] = sum;
         }
+    return NPG_OK;
+}
+
+// ---- time-dependent surface forcing (csrc/forcing.hip on the host): the per-face arithmetic, the row and entry gathers, the plan and
+// the argument checks are the SAME code (csrc/forcing_core.h); every row and every entry is one thread's own sum. ------------------------
+#include "../csrc/forcing_core.h"
+static_assert(NPG_FRC_NSERIES == npg::kFrcNSeries, "NPG_FRC_NSERIES of the header and kFrcNSeries of forcing_core.h must agree");
+
+struct npg_forcing {
+    npg_fe *fe = nullptr;
+    int64_t nface = 0;
+    npg::FrcPlan plan;
+    int32_t nkey[npg::kFrcNSeries] = {0, 0, 0, 0};
+    bool has_ser[npg::kFrcNSeries] = {false, false, false, false}, has_gamma = false;
+    std::vector<double> area2, ser[npg::kFrcNSeries], gamma, loc;
+};
+static npg::FrcFaces frc_faces(const npg_forcing *F) {
+    npg::FrcFaces t{};
+    t.nface = F->nface;
+    t.area2 = F->area2.data();
+    for (int c = 0; c < npg::kFrcNSeries; ++c) t.ser[c] = F->has_ser[c] ? F->ser[c].data() : nullptr, t.nkey[c] = F->nkey[c];
+    t.gamma = F->has_gamma ? F->gamma.data() : nullptr;
+    return t;
+}
+NPG_API int npg_forcing_create(npg_fe *fe, int64_t nface, const int32_t *face_cell, const uint8_t *face_local, const double *face_area2,
+                               const npg_csr *pattern, npg_forcing **out) {
+    REQUIRE(fe && out, "npg_forcing_create: NULL argument");
+    REQUIRE(!pattern || pattern->ctx == fe->ctx, "npg_forcing_create: the pattern must be a plain-CSR matrix of the engine's context");
+    {
+        bool flat = true;
+        for (int q = 0; q < fe->nq; ++q) flat = flat && fe->N1[(size_t)q * 4 + 3] == 0.0;
+        REQUIRE(!flat, "npg_forcing_create: an embedded 2-D engine is refused (its boundary is made of segments, not of faces)");
+    }
+    std::unique_ptr<npg_forcing> F(new npg_forcing());
+    REQUIRE_OK(npg::frc_build_plan(host_view(fe), fe->n_inv, fe->n_b, nface, face_cell, face_local, face_area2, pattern ? pattern->m : 0,
+                                   pattern ? pattern->rowptr.data() : nullptr, pattern ? pattern->col.data() : nullptr, F->plan));
+    F->fe = fe;
+    F->nface = nface;
+    F->area2.assign(face_area2, face_area2 + nface);
+    F->loc.assign((size_t)npg::kFrcNLoad * npg::kFrcK * (size_t)nface + 1, 0.0);
+    *out = F.release();
+    return NPG_OK;
+}
+NPG_API int npg_forcing_destroy(npg_forcing *F) {
+    delete F;
+    return NPG_OK;
+}
+NPG_API int npg_forcing_set_series(npg_forcing *F, int which, int nkey, const double *tables) {
+    REQUIRE(F, "npg_forcing_set_series: NULL argument");
+    REQUIRE(which >= 0 && which < npg::kFrcNSeries, "npg_forcing_set_series: which must be NPG_FRC_TAUX .. NPG_FRC_TARGET, got %d", which);
+    REQUIRE(!tables || nkey >= 1, "npg_forcing_set_series: nkey must be >= 1, got %d", nkey);
+    if (tables) REQUIRE_OK(npg::frc_check_table("npg_forcing_set_series", tables, nkey, F->nface, false));
+    F->ser[which].assign(1, 0.0);
+    if (tables && F->nface > 0) F->ser[which].assign(tables, tables + (size_t)nkey * npg::kBndQ * (size_t)F->nface);
+    F->has_ser[which] = tables != nullptr;
+    F->nkey[which] = tables ? nkey : 0;
+    return NPG_OK;
+}
+NPG_API int npg_forcing_set_gamma(npg_forcing *F, const double *table) {
+    REQUIRE(F, "npg_forcing_set_gamma: NULL argument");
+    if (table) REQUIRE_OK(npg::frc_check_table("npg_forcing_set_gamma", table, 1, F->nface, true));
+    F->gamma.assign(1, 0.0);
+    if (table && F->nface > 0) F->gamma.assign(table, table + npg::kBndQ * (size_t)F->nface);
+    F->has_gamma = table != nullptr;
+    return NPG_OK;
+}
+NPG_API int npg_forcing_apply(npg_forcing *F, const int32_t *key, const double *w, double alpha, const npg_vec *b_inv_base, npg_vec *b_inv_out,
+                              npg_vec *rhs_flux_out) {
+    REQUIRE(F, "npg_forcing_apply: NULL argument");
+    const npg_fe *fe = F->fe;
+    const bool all = b_inv_base && b_inv_out && rhs_flux_out;
+    REQUIRE_OK(npg::frc_check_apply(key, w, alpha, F->nkey, fe->n_inv, fe->n_b, all, all ? b_inv_base->n : 0, all ? b_inv_out->n : 0,
+                                    all ? rhs_flux_out->n : 0, all && b_inv_base->d == b_inv_out->d,
+                                    all && b_inv_base->ctx == fe->ctx && b_inv_out->ctx == fe->ctx && rhs_flux_out->ctx == fe->ctx));
+    npg::FrcFaces t = frc_faces(F);
+    for (int c = 0; c < npg::kFrcNSeries; ++c) t.key[c] = F->nkey[c] ? key[c] : 0, t.w[c] = F->nkey[c] ? w[c] : 0.0;
+    const int64_t nf = F->nface, nrow = fe->n_inv + fe->n_b;
+    double *loc = F->loc.data();
+#pragma omp parallel for schedule(static)
+    for (int64_t f = 0; f < nf; ++f) {
+        if (F->plan.kb == 6) npg::frc_face_loads<6>(t, f, loc);
+        else npg::frc_face_loads<3>(t, f, loc);
+    }
+    const int32_t *ptr = F->plan.gptr.data(), *slot = F->plan.gslot.data();
+#pragma omp parallel for schedule(static)
+    for (int64_t r = 0; r < nrow; ++r) npg::frc_gather_row(r, fe->n_inv, ptr, slot, loc, alpha, b_inv_base->d, b_inv_out->d, rhs_flux_out->d);
+    return NPG_OK;
+}
+NPG_API int npg_forcing_surface_matrix(npg_forcing *F, double scale, npg_csr *S) {
+    REQUIRE(F && S, "npg_forcing_surface_matrix: NULL argument");
+    REQUIRE(std::isfinite(scale), "npg_forcing_surface_matrix: scale is not finite");
+    REQUIRE(F->plan.has_pattern, "npg_forcing_surface_matrix: the handle was created without a pattern");
+    REQUIRE(F->has_gamma, "npg_forcing_surface_matrix: no gamma table (npg_forcing_set_gamma)");
+    REQUIRE(S->ctx == F->fe->ctx && S->m == F->plan.pat_m && S->nnz == F->plan.pat_nnz,
+            "npg_forcing_surface_matrix: S must be a plain-CSR matrix with the pattern given at create");
+    std::fill(S->val.begin(), S->val.end(), 0.0);
+    const npg::FrcFaces t = frc_faces(F);
+    const npg::FrcPlan &pl = F->plan;
+    const int64_t nent = (int64_t)pl.epos.size();
+#pragma omp parallel for schedule(static)
+    for (int64_t e = 0; e < nent; ++e) {
+        const double s = pl.kb == 6 ? npg::frc_matrix_entry<6>(t, pl.eptr.data(), pl.eface.data(), pl.ecode.data(), e)
+                                    : npg::frc_matrix_entry<3>(t, pl.eptr.data(), pl.eface.data(), pl.ecode.data(), e);
+        S->val[(size_t)pl.epos[(size_t)e]] = scale * s;
+    }
+    return NPG_OK;
+}
+NPG_API int npg_forcing_info(const npg_forcing *F, int64_t *nface, int64_t *wind_slots, int64_t *flux_slots, int64_t *matrix_entries,
+                             int64_t *matrix_slots) {
+    REQUIRE(F, "npg_forcing_info: NULL argument");
+    if (nface) *nface = F->nface;
+    if (wind_slots) *wind_slots = F->plan.wind_slots;
+    if (flux_slots) *flux_slots = F->plan.flux_slots;
+    if (matrix_entries) *matrix_entries = (int64_t)F->plan.epos.size();
+    if (matrix_slots) *matrix_slots = (int64_t)F->plan.eface.size();
     return NPG_OK;
 }
 

@@ -4,7 +4,8 @@
     (M + theta (Kh + Kv)) b^{n+1} = rhs,   Jacobi-preconditioned CG
 
 M, Kh, Kv and their Dirichlet lift vectors, rhs_diff, and the combination A = M + theta (Kh + Kv) with its Jacobi
-diagonal are all produced on the device in p_b order; rhs_flux (a surface integral, set-up constant) comes from the host."""
+diagonal are all produced on the device in p_b order; rhs_flux (a surface integral, set-up constant) comes from the host - unless a
+forcing.SurfaceForcing is attached, which recomputes it on the device for every time level and may add dt S to A."""
 from __future__ import annotations
 
 import numpy as np
@@ -47,6 +48,8 @@ class EvolutionToolkit:
         if not isinstance(arch, (GPU, CPU)):
             raise TypeError("EvolutionToolkit: arch must be GPU() or CPU()")
         self.arch, self.fe_data, self.params, self.forcings = arch, fe_data, params, forcings
+        self.first_step_lhs = first_step_lhs
+        self.S = None               # the surface matrix of an attached restoring condition (forcing.SurfaceForcing): A += dt S
         fe = self.fe = device_fe(arch, fe_data)
         ctx, nb = arch.ctx, fe_data.dofs.nb
         fe.set_coeff("kappa_h", forcings.kappa_h)
@@ -82,22 +85,33 @@ def _cpu_factorisation(arch, forcings, ts, A, P):
     return P
 
 
-def collect_evolution_LHS_into(A, P, params, ts, M, Kh, Kv):
-    """A = M + theta (Kh + Kv); P = Diagonal(1 ./ diag(A)) - src/evolution.jl:143-177, as two device kernels on the shared
-    pattern instead of a host sparse add + upload."""
+def collect_evolution_LHS_into(A, P, params, ts, M, Kh, Kv, S=None):
+    """A = M + theta (Kh + Kv) [+ dt S]; P = Diagonal(1 ./ diag(A)) - src/evolution.jl:143-177, as two device kernels on the shared
+    pattern instead of a host sparse add + upload.  S: the surface matrix of a restoring condition (forcing.SurfaceForcing); its
+    factor dt is the one that multiplies rhs_flux in npg_fe_evolution_rhs in both schemes.  P = None: no Jacobi vector is wanted."""
     theta = evolution_parameter(params, ts)
     A.combine(1.0, M, theta, Kh, Kv)
-    A.inv_diag(P.diag)
+    if S is not None:
+        A.axpy(ts.dt, S)
+    if P is not None:
+        A.inv_diag(P.diag)
     return A, P
+
+
+def lhs_timestepper(evolution: EvolutionToolkit, ts, step_index):
+    """the timestepper whose left-hand side the solver holds at step `step_index`: a BDF1 one for the first step (src/evolution.jl:110-111)
+    unless the toolkit was built with first_step_lhs="bdf2", the model's own from the second step on"""
+    if step_index <= 1 and getattr(evolution, "first_step_lhs", "bdf1") == "bdf1" and not isinstance(ts, BDF1):
+        return BDF1(t_start=ts.t_start, t_stop=ts.t_stop, dt=ts.dt)
+    return ts
 
 
 def collect_evolution_LHS(evolution: EvolutionToolkit, params, forcings, ts):
     """collect_evolution_LHS! - src/evolution.jl:133-142"""
     s = evolution.solver
     if isinstance(s.P, LU):             # CPU(): the Jacobi vector was replaced by the factorisation - combine, then factorise anew
-        theta = evolution_parameter(params, ts)
-        s.A.combine(1.0, evolution.M, theta, evolution.Kh, evolution.Kv)
+        collect_evolution_LHS_into(s.A, None, params, ts, evolution.M, evolution.Kh, evolution.Kv, getattr(evolution, "S", None))
         s.P = LU(s.A)
         return evolution
-    collect_evolution_LHS_into(s.A, s.P, params, ts, evolution.M, evolution.Kh, evolution.Kv)
+    collect_evolution_LHS_into(s.A, s.P, params, ts, evolution.M, evolution.Kh, evolution.Kv, getattr(evolution, "S", None))
     return evolution

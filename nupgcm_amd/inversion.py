@@ -107,6 +107,7 @@ class InversionToolkit:
                 # follows every re-assembly; A itself stays plain (assembly target)
                 A.pack_nodes(fe_data.dofs.n_full, fe_data.dofs.n_surf)
             B = build_B_inversion(arch, fe_data, params, lift=b0)
+            self.b_lift = b0.copy()                     # the Dirichlet lift alone: forcing.SurfaceForcing adds the wind of each time level to it
             b0 = build_b_inversion(arch, fe_data, params, forcings, b0)
             # GPU preconditioner: Diagonal(1/h^dim) with the median edge length (src/inversion.jl:42-54)
             h = fe_data.mesh.median_edge_length()

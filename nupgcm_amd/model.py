@@ -68,6 +68,7 @@ class Model:
         self.extrapolate_guess = False
         self.stats = []
         self.tracers = None         # tracers.PassiveTracers(model, ...): run() steps them directly after evolve()
+        self.surface_forcing = None # forcing.SurfaceForcing(model, ...): run() applies it at t_{n+1} before evolve()
         self._prev = None
         self._u_view = inversion.solver.x.view(0, fe_data.dofs.nu)     # x[1:nu] = u (p_inversion = [p_u; nu + p_p])
 
@@ -117,7 +118,8 @@ def evolve(model: Model, x_inv_prev: DeviceVector, b_prev: DeviceVector):
             fe.assemble(L.NPG_MAT_KV, ev.Kv, lift=ev.rhs_v)                                    # src/model.jl:235
         fe.rhs_diff(prm.N2, ev.rhs_diff)                                                       # src/model.jl:237
     if frc.conv_param.is_on or ts.adaptive:
-        collect_evolution_LHS_into(solver.A, solver.P, prm, ts, ev.M, ev.Kh, ev.Kv)            # src/model.jl:251-261
+        # src/model.jl:251-261 (with the S of an attached restoring condition; CPU(): a factorisation is renewed, not read as a Jacobi vector)
+        collect_evolution_LHS(ev, prm, frc, ts)
     x_inv = model.inversion.solver.x
     # (mesh-partitioned models: the element kernels write every local row, the solver reads the owned ones - a view)
     fe.evolution_rhs(_scheme(ts), ts.dt, prm.N2, theta, model.b_vec, b_prev, x_inv, x_inv_prev, ev.rhs_diff,
@@ -155,6 +157,8 @@ def run(model: Model, n_info=10, n_save=float("inf"), n_plot=float("inf"), advec
                 ts.dt = comm.min(ts.dt)                           # partitioned mesh: every rank saw its own cells only
         if i == 2 and isinstance(ts, BDF2):
             collect_evolution_LHS(model.evolution, prm, frc, ts)                                # src/model.jl:134-137
+        if getattr(model, "surface_forcing", None):
+            model.surface_forcing.apply(model, ts.t + ts.dt)      # both solves of the step produce level n + 1: the forcing at t_{n+1}
         pv["x_curr"].copy_from(inv_x)                                                           # src/model.jl:140-141
         pv["b_curr"].copy_from(b)
         evolve(model, pv["x_prev"], pv["b_prev"])                                               # src/model.jl:144
