@@ -652,6 +652,25 @@ int npg_forcing_info(const npg_forcing *F, int64_t *nface, int64_t *wind_slots, 
                      int64_t *matrix_slots);
 int npg_forcing_destroy(npg_forcing *F);
 
+/* ---- time means and eddy co-moments of the running state (new work: the reference has no time averaging) ------------------------------
+ * A weighted running mean of [u; p] and b and the ten co-moments uu uv uw vv vw ww ub vb wb bb of the mesh nodes, updated once per
+ * time step on the device (csrc/tavg_core.h).  The handle owns the node table only: iu[3][nnode] the position of each
+ * velocity component of a node in x_inv, ib[2][nnode] two positions in b - equal for a P2 node or a vertex, the edge's two vertices
+ * for a mid-node of a P1 buoyancy (its delta is half their sum); -1 is a Dirichlet DoF (delta = 0).  The accumulators are the caller's
+ * vectors, zero before the first sample.
+ *   npg_tavg_accumulate: for a sample of weight w the caller forms W' = W + w, r = w / W', q = w (W / W') and the call does, with the
+ *   OLD means and exactly this association (add, subtract, multiply; no contraction, no division),
+ *       delta_a = a - mu_a;   comom[pair][node] += (q delta_a) delta_b;   mu_a += r delta_a
+ *   comom = NULL: the means only.  Two launches on the context's stream (co-moments first), no atomics: the bits of the host library.
+ * Validation (NPG_EINVAL + message: vector lengths, r in (0, 1], q >= 0, both finite, index ranges at create) happens before anything
+ * is launched: a failed call leaves the accumulators untouched. */
+typedef struct npg_tavg npg_tavg;
+int npg_tavg_create(npg_ctx *ctx, int64_t n_inv, int64_t n_b, int64_t nnode, const int32_t *iu, const int32_t *ib, npg_tavg **out);
+int npg_tavg_accumulate(npg_tavg *T, double r, double q, const npg_vec *x_inv, const npg_vec *b, npg_vec *mean_x, npg_vec *mean_b,
+                        npg_vec *comom);
+int npg_tavg_info(const npg_tavg *T, int64_t *nnode, int64_t *n_inv, int64_t *n_b);
+int npg_tavg_destroy(npg_tavg *T);
+
 /* ---- the state binned into (latitude band, buoyancy class) (new work: the reference overlays isopycnals on a z-coordinate psi) --
  * A joint table [ny + 1][nb + 1][NPG_NCLS] over the cells of the mesh (csrc/classes_core.h).
  * Sample rule - NOT the engine's quadrature (Keast's rule has a negative weight): ns barycentric points rule_lam[ns][4] with weights

@@ -5,6 +5,7 @@ BASELINE configs[0]): the same C ABI built for the host (libnupgcm_host.so, plai
 branches (sparse LU / backslash / host Krylov) - an architecture chosen explicitly, one per process, never a stand-in for GPU()."""
 from .architectures import (CPU, GPU, AbstractArchitecture, DeviceCSR, DeviceILU0, DeviceVector, architecture, on_architecture,
                             print_memory_status, vector_type)
+from .averages import Covariance, TimeAverages, phase_bin
 from .boundary import BoundaryFluxes, BoundaryIntegrals, BoundaryMaps, BoundaryRecorder
 from .evolution import EvolutionToolkit, collect_evolution_LHS, evolution_parameter
 from .forcing import ForcingSeries, SurfaceForcing, series_key_weight

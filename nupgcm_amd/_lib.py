@@ -167,6 +167,8 @@ def _declare(L, partial=False):
         "npg_forcing_create": [P, I64, VP, VP, VP, P, PP], "npg_forcing_destroy": [P], "npg_forcing_set_series": [P, C.c_int, C.c_int, VP],
         "npg_forcing_set_gamma": [P, VP], "npg_forcing_apply": [P, VP, VP, D, P, P, P], "npg_forcing_surface_matrix": [P, D, P],
         "npg_forcing_info": [P] + [C.POINTER(I64)] * 5, "npg_csr_axpy": [P, D, P],
+        "npg_tavg_create": [P, I64, I64, I64, VP, VP, PP], "npg_tavg_destroy": [P], "npg_tavg_accumulate": [P, D, D, P, P, P, P, P],
+        "npg_tavg_info": [P] + [C.POINTER(I64)] * 3,
         "npg_classes_create": [P, VP, VP, VP, VP, VP, C.c_int, VP, I64, VP, I64, PP], "npg_classes_destroy": [P],
         "npg_classes_compute": [P, P, P, D, P, P],
         "npg_classes_set_diffusivity": [P, VP, D, VP, D], "npg_classes_mixing": [P, P, D, D, D, D, D, P, P],

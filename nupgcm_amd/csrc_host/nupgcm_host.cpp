@@ -1673,6 +1673,57 @@ NPG_API int npg_forcing_info(const npg_forcing *F, int64_t *nface, int64_t *wind
     return NPG_OK;
 }
 
+// ---- time means and co-moments of the running state (csrc/tavg.hip on the host): the per-node and per-entry arithmetic and the argument
+// checks are the SAME code (csrc/tavg_core.h); every node and every entry is one thread's own. -------------------------------------------
+#include "../csrc/tavg_core.h"
+
+struct npg_tavg {
+    npg_ctx *ctx = nullptr;
+    int64_t n_inv = 0, n_b = 0, nnode = 0;
+    std::vector<int32_t> iu, ib;
+};
+NPG_API int npg_tavg_create(npg_ctx *ctx, int64_t n_inv, int64_t n_b, int64_t nnode, const int32_t *iu, const int32_t *ib, npg_tavg **out) {
+    REQUIRE(ctx && out, "npg_tavg_create: NULL argument");
+    REQUIRE_OK(npg::tavg_check_create(n_inv, n_b, nnode, iu, ib));
+    std::unique_ptr<npg_tavg> T(new npg_tavg());
+    T->ctx = ctx;
+    T->n_inv = n_inv, T->n_b = n_b, T->nnode = nnode;
+    if (nnode > 0) T->iu.assign(iu, iu + 3 * nnode), T->ib.assign(ib, ib + 2 * nnode);
+    *out = T.release();
+    return NPG_OK;
+}
+NPG_API int npg_tavg_destroy(npg_tavg *T) {
+    delete T;
+    return NPG_OK;
+}
+NPG_API int npg_tavg_info(const npg_tavg *T, int64_t *nnode, int64_t *n_inv, int64_t *n_b) {
+    REQUIRE(T, "npg_tavg_info: NULL argument");
+    if (nnode) *nnode = T->nnode;
+    if (n_inv) *n_inv = T->n_inv;
+    if (n_b) *n_b = T->n_b;
+    return NPG_OK;
+}
+NPG_API int npg_tavg_accumulate(npg_tavg *T, double r, double q, const npg_vec *x_inv, const npg_vec *b, npg_vec *mean_x, npg_vec *mean_b,
+                                npg_vec *comom) {
+    REQUIRE(T, "npg_tavg_accumulate: NULL argument");
+    const bool all = x_inv && b && mean_x && mean_b;
+    const bool aliased = all && (mean_x->d == x_inv->d || mean_b->d == b->d || mean_x->d == mean_b->d ||
+                                 (comom && (comom->d == x_inv->d || comom->d == b->d || comom->d == mean_x->d || comom->d == mean_b->d)));
+    const bool one_ctx = all && x_inv->ctx == T->ctx && b->ctx == T->ctx && mean_x->ctx == T->ctx && mean_b->ctx == T->ctx &&
+                         (!comom || comom->ctx == T->ctx);
+    REQUIRE_OK(npg::tavg_check_accumulate(r, q, T->n_inv, T->n_b, T->nnode, all, all ? x_inv->n : 0, all ? b->n : 0, all ? mean_x->n : 0,
+                                          all ? mean_b->n : 0, comom ? comom->n : -1, aliased, one_ctx));
+    const int64_t nnode = T->nnode, n_inv = T->n_inv, n = T->n_inv + T->n_b;
+    if (comom && nnode > 0) {
+        const npg::TavgTable t{nnode, T->iu.data(), T->ib.data()};
+#pragma omp parallel for schedule(static)
+        for (int64_t j = 0; j < nnode; ++j) npg::tavg_node(t, j, q, x_inv->d, b->d, mean_x->d, mean_b->d, comom->d);
+    }
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; ++i) npg::tavg_mean(i, n_inv, r, x_inv->d, b->d, mean_x->d, mean_b->d);
+    return NPG_OK;
+}
+
 // ---- the state binned into (latitude band, buoyancy class) (csrc/classes.hip on the host): the per-sample arithmetic and the edge
 // search are the SAME code (csrc/classes_core.h).  Pass 1 in fixed chunks of kClsChunk cells, folded in chunk order; pass 2 adds the
 // quantised terms as 64-bit integers (relaxed atomics on one table, a run of samples in one bin added up first): integer addition is

@@ -69,6 +69,7 @@ class Model:
         self.stats = []
         self.tracers = None         # tracers.PassiveTracers(model, ...): run() steps them directly after evolve()
         self.surface_forcing = None # forcing.SurfaceForcing(model, ...): run() applies it at t_{n+1} before evolve()
+        self.averages = None        # averages.TimeAverages(model, ...): run() folds every new level into it
         self._prev = None
         self._u_view = inversion.solver.x.view(0, fe_data.dofs.nu)     # x[1:nu] = u (p_inversion = [p_u; nu + p_p])
 
@@ -192,6 +193,8 @@ def run(model: Model, n_info=10, n_save=float("inf"), n_plot=float("inf"), advec
             blow = comm.any(blow)                                 # every rank leaves the loop together
         if blow:
             raise BlowUp("Blow-up detected, stopping simulation")
+        if getattr(model, "averages", None):
+            model.averages.accumulate(model, ts.t, ts.dt)         # the level t_{n+1}, weighted by the step that produced it
         if int(getattr(model, "extrapolate_guess", 0) or 0) >= 2:         # x_{n-2} of this step is x_{n-3} of the next
             if "x_prev2" not in pv:
                 pv["x_prev2"] = pv["x_prev"].copy()
