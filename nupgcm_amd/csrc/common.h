@@ -45,14 +45,22 @@ NPG_SHARED void set_error(const char *fmt, ...);
         NPG_REQUIRE(m_.empty(), "%s", m_.c_str());       \
     } while (0)
 
-// A device array owned by a diagnostic's handle: freed with the handle, never copied.  Every call returns the HIP error, so a
-// create is a straight line of NPG_HIP(...) over a handle held by a std::unique_ptr.  n = 0 allocates nothing (null pointer).
+// A device array owned by a handle: freed with the handle, moved or swapped but never copied.  Every call returns the HIP error, so
+// a create is a straight line of NPG_HIP(...) over a handle held by a std::unique_ptr.  n = 0 allocates nothing (null pointer).
 template <class T>
 struct DevBuf {
     T *p = nullptr;
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) {
+            reset();
+            std::swap(p, o.p);
+        }
+        return *this;
+    }
     ~DevBuf() { hipFree(p); }
     operator T *() const { return p; }
     void reset() {
@@ -60,6 +68,10 @@ struct DevBuf {
         p = nullptr;
     }
     void swap(DevBuf &o) { std::swap(p, o.p); }
+    void adopt(T *q) {           // take over an array allocated elsewhere (hipExtMallocWithFlags)
+        reset();
+        p = q;
+    }
     hipError_t alloc(size_t n) {
         reset();
         return n ? hipMalloc((void **)&p, n * sizeof(T)) : hipSuccess;
@@ -149,7 +161,7 @@ struct npg_csr {
     int64_t m = 0, n = 0, nnz = 0;
     int64_t *rowptr = nullptr;   // device, m+1
     int32_t *col = nullptr;      // device, nnz
-    double *val = nullptr;       // device, nnz
+    npg::DevBuf<double> val;     // device, nnz
     bool owns_pattern = true;
     // nnz-balanced row tiles for the tiled SpMV kernels (device + host copy)
     npg::TileDesc *tile_ptr = nullptr; // device, ntiles descriptors
@@ -165,24 +177,24 @@ struct npg_csr {
     // the matrix, `rnnz` counts what is left in col/val
     int64_t rnnz = 0;
     int32_t nfull = 0, nsurf = 0;
-    int64_t *prow = nullptr;     // device, nfull + nsurf + 1
-    int32_t *pcol = nullptr;     // device, column node of a record
-    double *pkc = nullptr;       // device, {K, C} per record
+    npg::DevBuf<int64_t> prow;   // device, nfull + nsurf + 1
+    npg::DevBuf<int32_t> pcol;   // device, column node of a record
+    npg::DevBuf<double> pkc;     // device, {K, C} per record
     std::vector<int64_t> h_prow;
     // coupling records of the rows behind the block rows (the pressure rows of A_inversion; spmv_device.h): what such a row
     // holds in the block COLUMNS is stored as one record {c, d_x, d_y, d_z} per column node; rowptr/col/val keep the rest
-    int64_t *drow = nullptr;     // device, (m - block_rows) + 1 record offsets; null without coupling records
-    int32_t *dcol = nullptr;     // device, column node of a record
-    double *dval = nullptr;      // device, [2 ndrec] (d_x, d_y) pairs followed by [ndrec] d_z
-    float *dval32 = nullptr;     // optional fp32 copy, same layout
+    npg::DevBuf<int64_t> drow;   // device, (m - block_rows) + 1 record offsets; null without coupling records
+    npg::DevBuf<int32_t> dcol;   // device, column node of a record
+    npg::DevBuf<double> dval;    // device, [2 ndrec] (d_x, d_y) pairs followed by [ndrec] d_z
+    npg::DevBuf<float> dval32;   // optional fp32 copy, same layout
     int64_t ndrec = 0;
     std::vector<int64_t> h_drow;
     // column records of the block rows (spmv_device.h): what node q's rows hold OUTSIDE the block columns, one record
     // {m, a_x, a_y, a_z} per distinct column; the block rows then have no entries left in rowptr/col/val
-    int64_t *grow = nullptr;     // device, nfull + nsurf + 1 record offsets; null without column records
-    int32_t *gcol = nullptr;     // device, column of a record
-    double *gval = nullptr;      // device, [2 ngrec] (a_x, a_y) pairs followed by [ngrec] a_z
-    float *gval32 = nullptr;     // optional fp32 copy, same layout
+    npg::DevBuf<int64_t> grow;   // device, nfull + nsurf + 1 record offsets; null without column records
+    npg::DevBuf<int32_t> gcol;   // device, column of a record
+    npg::DevBuf<double> gval;    // device, [2 ngrec] (a_x, a_y) pairs followed by [ngrec] a_z
+    npg::DevBuf<float> gval32;   // optional fp32 copy, same layout
     int64_t ngrec = 0;
     std::vector<int64_t> h_grow;
     // FULL node records (npg_csr_pack_nodes: function-valued viscosity, all nine component pairs per node pair): a SEPARATE
@@ -190,63 +202,67 @@ struct npg_csr {
     // holds, beside the record arrays, for every stored value the position in the plain matrix's `val` it is refreshed from
     // (-1: structural zero) - csr_repack() after every change of the plain values.  SpMV-side code goes through spmv_form().
     npg_csr *packed = nullptr;
-    double *pk9 = nullptr;       // device, [9][npk9]: a_rs of record e at (3 r + s) npk9 + e (prow / pcol index the records)
-    float *pk9_32 = nullptr;
+    npg::DevBuf<double> pk9;     // device, [9][npk9]: a_rs of record e at (3 r + s) npk9 + e (prow / pcol index the records)
+    npg::DevBuf<float> pk9_32;
     int64_t npk9 = 0;
-    int64_t *map9 = nullptr, *mapd = nullptr, *mapg = nullptr, *maprem = nullptr;   // device, same layouts as pk9 / dval / gval / val
-    // windowed tile set of the block rows (spmv_window.h, build_window_tiles): a SECOND tiling of the same matrix for the
-    // kernels that gather from the fp32 gather-layout copy of their input - every node's record list padded to an even
-    // count (zero records), 16-bit window indices beside pcol / gcol, per-tile lists of distinct columns
-    npg::WTileDesc *wtile_ptr = nullptr; // device, nwtiles descriptors: windowed block tiles, then the ordinary tiles of the other rows
-    int32_t nwtiles = 0, nwtiles_interior = 0;
-    int32_t wlanes = 8;
-    uint16_t *widx = nullptr;    // device, window index of every node record (same indexing as pcol)
-    uint16_t *gidx = nullptr;    // device, window index of every column record (same indexing as gcol)
-    int32_t *wlist = nullptr;    // device, concatenated per-tile lists of distinct column nodes (ascending per tile)
-    int32_t *vlist = nullptr;    // device, concatenated per-tile lists of distinct columns of the column records
+    npg::DevBuf<int64_t> map9, mapd, mapg, maprem;   // device, same layouts as pk9 / dval / gval / val
     // GHOST NODES of a rank's row block (npg_csr_set_ghost_nodes, round 5): ghost columns [gn_col[g], gn_col[g] + gn_ncomp[g]) are the
     // (x, y[, z]) components of ONE velocity node owned by a neighbour.  The windowed tile set then stores a row node's coupling to
     // such a node as ONE {c, K, C} node record with c = nnode() + g (its window entry is the node's 4-float slot behind the owned
     // nodes' slots in the gather-layout copy) instead of three column records - which is what kept a rank's boundary tiles at a
     // fifth of their size.  The ordinary tiles and the fp64 kernels keep the column records.
     std::vector<int32_t> gn_col, gn_ncomp;
-    int32_t *gslot = nullptr;    // device, per ghost column (n - m entries): float position of its slot in the gather-layout copy, -1: none
-    double *wgval = nullptr;     // device, the WINDOWED set's own column-record values when it differs from gval: [2 nw_grec] (a_x, a_y), [nw_grec] a_z
-    int64_t nw_grec = 0, nw_rec = 0;   // column records / padded node records of the windowed set (= ngrec / h_prow[nnode] without ghost nodes)
-    double *wdz = nullptr;       // device, d_z of the windowed set's own coupling records (rows behind the block rows, ghost nodes included)
-    int64_t nw_drec = 0;         // its padded coupling records
     int64_t ngn() const { return (int64_t)gn_col.size(); }
-    double *pkc2 = nullptr;      // device, the {K, C} values split by position in the record pair: [npairs] firsts, [npairs] seconds
-    int64_t npairs = 0;
-    double *dxy2 = nullptr;      // device, the (d_x, d_y) of the coupling records split the same way: [ndpairs] firsts, [ndpairs] seconds
-    int64_t ndpairs = 0;
-    int32_t *wbk = nullptr;      // device, [nnode][2]: tile-local end offsets of node q's column records / record pairs
-    uint16_t *dwidx = nullptr;   // device, window index of every coupling record (windowed tiles of the rows behind the block rows)
-    int32_t *dbk = nullptr;      // device, per row behind the block rows: tile-local end offset of its coupling record PAIRS
-    int32_t nwrow_tiles = 0;     // windowed tiles of the rows behind the block rows (0: those rows keep their ordinary tiles)
+    // windowed tile set of the block rows (spmv_window.h, plan_window_tiles): a SECOND tiling of the same matrix for the
+    // kernels that gather from the fp32 gather-layout copy of their input - every node's record list padded to an even
+    // count (zero records), 16-bit window indices beside pcol / gcol, per-tile lists of distinct columns.  All device arrays.
+    struct WindowSet {
+        npg::DevBuf<npg::WTileDesc> wtile_ptr;  // nwtiles descriptors: windowed block tiles and the tiles of the other rows; null: no windowed set
+        int32_t nwtiles = 0, nwtiles_interior = 0;
+        int32_t wlanes = 8;
+        npg::DevBuf<uint16_t> widx;  // window index of every node record (same indexing as pcol)
+        npg::DevBuf<uint16_t> gidx;  // window index of every column record (same indexing as gcol)
+        npg::DevBuf<int32_t> wlist;  // concatenated per-tile lists of distinct column nodes (ascending per tile)
+        npg::DevBuf<int32_t> vlist;  // concatenated per-tile lists of distinct columns of the column records
+        npg::DevBuf<int32_t> gslot;  // per ghost column (n - m entries): float position of its slot in the gather-layout copy, -1: none
+        npg::DevBuf<double> wgval;   // the set's own column-record values where ghost nodes were converted: [2 nw_grec] (a_x, a_y), [nw_grec] a_z
+        int64_t nw_grec = 0, nw_rec = 0;   // column records / padded node records of the set (= ngrec / h_prow[nnode] without ghost nodes)
+        npg::DevBuf<double> wdz;     // d_z of the set's own coupling records (rows behind the block rows, ghost nodes included)
+        int64_t nw_drec = 0;         // its padded coupling records
+        npg::DevBuf<double> pkc2;    // the {K, C} values split by position in the record pair: [npairs] firsts, [npairs] seconds
+        int64_t npairs = 0;
+        npg::DevBuf<double> dxy2;    // the (d_x, d_y) of the coupling records split the same way: [ndpairs] firsts, [ndpairs] seconds
+        int64_t ndpairs = 0;
+        npg::DevBuf<int32_t> wbk;    // [nnode][2]: tile-local end offsets of node q's column records / record pairs
+        npg::DevBuf<uint16_t> dwidx; // window index of every coupling record (windowed tiles of the rows behind the block rows)
+        npg::DevBuf<int32_t> dbk;    // per row behind the block rows: tile-local end offset of its coupling record PAIRS
+        int32_t nwrow_tiles = 0;     // windowed tiles of the rows behind the block rows (0: those rows keep their ordinary tiles)
+        int64_t nwlist = 0, nvlist = 0;
+    } win;
     // block-diagonal matrix with arbitrary index sets as blocks (npg_csr_line_block_inverse): the blocks also packed DENSE,
     // column-major, one after the other - what products with it stream instead of the CSR arrays (k_line_apply, csr.hip)
-    int64_t lb_nblocks = 0;
-    int64_t *lb_ptr = nullptr;   // device, [nblocks + 1] offsets into lb_dofs
-    int64_t *lb_dofs = nullptr;  // device, the blocks' rows / columns, ascending per block
-    int64_t *lb_off = nullptr;   // device, [nblocks + 1] offsets of the dense blocks (sum of n^2)
-    double *lb_val = nullptr;    // device, the dense blocks
-    float *lb_val32 = nullptr;   //         and rounded to fp32 (products that ask for fp32 operator values)
-    _Float16 *lb_val16 = nullptr; //        and to fp16, every column of a block divided by lb_scale[its unknown] = its largest magnitude
-    double *lb_scale = nullptr;  // device, [nu] (what fp32-asking products read with NPG_LINE_FP16=1)
+    struct LineBlocks {
+        int64_t nblocks = 0;
+        npg::DevBuf<int64_t> ptr;    // [nblocks + 1] offsets into dofs
+        npg::DevBuf<int64_t> dofs;   // the blocks' rows / columns, ascending per block
+        npg::DevBuf<int64_t> off;    // [nblocks + 1] offsets of the dense blocks (sum of n^2)
+        npg::DevBuf<double> val;     // the dense blocks
+        npg::DevBuf<float> val32;    //   and rounded to fp32 (products that ask for fp32 operator values)
+        npg::DevBuf<_Float16> val16; //   and to fp16, every column of a block divided by scale[its unknown] = its largest magnitude
+        npg::DevBuf<double> scale;   // [nu] (what fp32-asking products read with NPG_LINE_FP16=1)
+    } lb;
     int64_t ndrec_real = 0;      // coupling records without the zero records that pad a row's list to an even count
-    int64_t nwlist = 0, nvlist = 0;
     int64_t nrec_real = 0;       // node records without the zero records that pad a node's list to an even count
     std::vector<npg::TileDesc> h_tiles;   // host copy of tile_ptr (final order)
     // npg_csr_block_nodes_dofs: the matrix was handed over in the CALLER's DoF order and is stored in the library's node-block
     // order; uperm[i] = caller index of internal row / column i.  npg_spmv and npg_gmres_solve take and return vectors in the
     // caller's order (one gather / scatter pass each way through the three scratch vectors); every other entry point refuses it
-    int32_t *uperm = nullptr;    // device, m entries; null: no internal renumbering
-    double *uvec[3] = {nullptr, nullptr, nullptr};      // device scratch, m doubles each: right-hand side, iterate, diagonal
+    npg::DevBuf<int32_t> uperm;  // device, m entries; null: no internal renumbering
+    npg::DevBuf<double> uvec[3]; // device scratch, m doubles each: right-hand side, iterate, diagonal
     bool uperm_active = false;   // set while npg_gmres_solve runs on the internally ordered vectors
     // optional fp32 copies of the values (csr_refresh_fp32): read instead of val / pkc by SpMVs that ask for them
     // (SpmvEpi::f32 - the multigrid preconditioner's; results are still accumulated and returned in fp64)
-    float *val32 = nullptr, *pkc32 = nullptr;
+    npg::DevBuf<float> val32, pkc32;
     // bumped whenever a pointer or count that kernels (and hence captured hipGraphs) bake in changes: build_tiles,
     // npg_csr_block_nodes, the first csr_refresh_fp32.  Holders of captured graphs compare it (mg.hip).
     uint64_t gen = 0;
@@ -303,8 +319,12 @@ int build_tiles(npg_csr *A);
 // the form the SpMV kernels read: the record-form companion of a plain matrix if it has one (npg_csr_pack_nodes)
 inline const npg_csr *spmv_form(const npg_csr *A) { return (A && A->packed) ? A->packed : A; }
 // Host-side consistency of what a tile kernel is about to index (O(1), before every launch that takes the matrix): the arrays its
-// record loops read must exist and agree in length.  A kernel instance WITHOUT full-node-record support reading a companion
-// (whose {K, C} array is null) is what the two memory faults of round 3 were - profiles/r04_round3_faults.txt.
+// record loops read must exist and agree in length.  Which pointers are null in which state is what the kernels key on:
+//   prow, pcol   non-null when nnode() > 0 (even with zero records: empty arrays get a minimum allocation, upload_min in csr.hip)
+//   pkc | pk9    exactly one of them non-null when nnode() > 0 ({K, C} records | full node records of a companion)
+//   grow         null without column records          drow   null without coupling records
+//   win.wtile_ptr  null without a windowed set        win.wgval, win.wdz   null unless ghost nodes were converted
+// A kernel instance WITHOUT full-node-record support reading a companion (whose {K, C} array is null) is what the two memory faults of round 3 were - profiles/r04_round3_faults.txt.
 inline int check_record_view(const npg_csr *A, bool n9_capable, const char *who) {
     if (!A) return NPG_OK;
     if (A->nnode() > 0) {

@@ -2,49 +2,36 @@
 #include <algorithm>
 
 #include "common.h"
+#include "csr_records_core.h"
 #include "spmv_device.h"
 #include "spmv_window.h"
 
 namespace npg {
 
-// Row tiles for the CSR-stream kernels: consecutive whole rows, at most kTileNnz stored entries and kTileRows rows per
-// tile; small matrices get about one tile per CU.  A row longer than kTileNnz becomes a tile of its own.
+static_assert(RecordCaps().tile_slots == kTileNnz && RecordCaps().tile_rows == kTileRows && RecordCaps().win_pairs == kWinPairs &&
+                  RecordCaps().win_cols == kWinCols && RecordCaps().win_nodes == kWinNodes,
+              "csr_records_core.h plans with the kernels' tile limits");
+
+static NodeOrder node_order(const npg_csr *A) { return NodeOrder{A->nfull, A->nsurf}; }
+
+static TileInput tile_input(const npg_csr *A) {
+    TileInput in;
+    in.m = A->m;
+    in.order = node_order(A);
+    in.rowptr = A->h_rowptr.data();
+    in.prow = A->nnode() ? A->h_prow.data() : nullptr;
+    in.grow = A->grow ? A->h_grow.data() : nullptr;          // column records of the block rows
+    in.drow = A->drow ? A->h_drow.data() : nullptr;          // coupling records of the rows behind the block rows
+    in.num_cu = A->ctx->num_cu;
+    return in;
+}
+
+// Row tiles for the CSR-stream kernels (plan_tile_boundaries): consecutive whole rows, at most kTileNnz stored entries and
+// kTileRows rows per tile; small matrices get about one tile per CU.  A row longer than kTileNnz becomes a tile of its own.
 int tile_boundaries(const npg_csr *A, int tile_slots, std::vector<int32_t> &tp, int max_rows) {
-    const int64_t m = A->m;
-    const int64_t *rp = A->h_rowptr.data();
-    const int64_t *pp = A->nnode() ? A->h_prow.data() : nullptr;
-    const int64_t nf3 = 3 * (int64_t)A->nfull, nbr = A->block_rows();
-    auto node = [&](int64_t r) { return r < nf3 ? r / 3 : A->nfull + (r - nf3) / 2; };      // r starts a node
-    const int64_t *dp = A->drow ? A->h_drow.data() : nullptr;          // coupling records of the rows behind the block rows
-    const int64_t *gp = A->grow ? A->h_grow.data() : nullptr;          // column records of the block rows
-    const int64_t slots_total = rp[m] + (pp ? 3 * pp[A->nfull] + 2 * (pp[A->nnode()] - pp[A->nfull]) : 0) + (dp ? dp[m - nbr] : 0) +
-                                (gp ? 3 * gp[A->nfull] + 2 * (gp[A->nnode()] - gp[A->nfull]) : 0);
-    int64_t target = slots_total / (int64_t)A->ctx->num_cu;
-    target = std::min<int64_t>(tile_slots, std::max<int64_t>(1024, target)); // >= 1 tile per CU on small matrices
-    // LDS product slots of rows [a, b): their CSR entries + one per component per record (a, b on node boundaries of
-    // one kind inside the block rows)
-    auto slots = [&](int64_t a, int64_t b) {
-        int64_t s = rp[b] - rp[a];
-        if (pp && a < nbr) s += (a < nf3 ? 3 : 2) * (pp[node(b)] - pp[node(a)]);
-        if (gp && a < nbr) s += (a < nf3 ? 3 : 2) * (gp[node(b)] - gp[node(a)]);
-        if (dp && a >= nbr) s += dp[b - nbr] - dp[a - nbr];
-        return s;
-    };
-    const int64_t max_rows_rec = std::min<int64_t>(max_rows, kTileRows / 2);      // TileLds::prp
-    tp.clear();
-    tp.push_back(0);
-    int64_t r = 0;
-    while (r < m) {
-        const bool inblk = r < nbr;
-        const int64_t step = !inblk ? 1 : (r < nf3 ? 3 : 2), lim = !inblk ? m : (r < nf3 ? nf3 : nbr);
-        int64_t r1 = r + step;
-        const int64_t mr = (!inblk && dp) ? max_rows_rec : max_rows;
-        while (r1 < lim && r1 + step - r <= mr && slots(r, r1 + step) <= target) r1 += step;
-        NPG_REQUIRE(!inblk || slots(r, r1) <= tile_slots, "build_tiles: the rows of one node do not fit one tile");
-        NPG_REQUIRE(inblk || !dp || slots(r, r1) <= tile_slots, "build_tiles: a row with coupling records does not fit one tile");
-        tp.push_back((int32_t)r1);
-        r = r1;
-    }
+    const PlanOutcome fit = plan_tile_boundaries(tile_input(A), tile_slots, max_rows, kTileRows, tp);
+    NPG_REQUIRE(fit != PlanOutcome::node_does_not_fit, "build_tiles: the rows of one node do not fit one tile");
+    NPG_REQUIRE(fit != PlanOutcome::row_does_not_fit, "build_tiles: a row with coupling records does not fit one tile");
     return NPG_OK;
 }
 
@@ -74,32 +61,11 @@ int build_tiles(npg_csr *A) {
     A->lanes_default = mean <= 12 ? 4 : mean <= 64 ? 8 : mean <= 256 ? 16 : 32;
     if (getenv("NPG_SPMV_LANES")) A->lanes_default = atoi(getenv("NPG_SPMV_LANES"));      // tuning override: 4, 8, 16 or 32
     if (!A->lanes_set) A->lanes = A->lanes_default;
-    const int64_t *rp = A->h_rowptr.data();
-    const int64_t nf3 = 3 * (int64_t)A->nfull, nbr = A->block_rows();
-    auto node = [&](int64_t r) { return r < nf3 ? r / 3 : A->nfull + (r - nf3) / 2; };
-    std::vector<TileDesc> td((size_t)A->ntiles);
-    for (int t = 0; t < A->ntiles; ++t) {
-        const int64_t r0 = tp[t], r1 = tp[t + 1];
-        TileDesc &q = td[t];
-        q.r0 = (int32_t)r0;
-        q.nrows = (int32_t)(r1 - r0);
-        q.base = rp[r0];
-        q.n = (int32_t)(rp[r1] - rp[r0]);
-        q.pbase = 0;
-        q.npe = 0;
-        if (r0 < nbr) {
-            q.pbase = A->h_prow[node(r0)];
-            q.npe = (int32_t)(A->h_prow[node(r1)] - q.pbase);
-            if (A->grow) {          // (base, n) of a block tile describe its column records
-                q.base = A->h_grow[node(r0)];
-                q.n = (int32_t)(A->h_grow[node(r1)] - q.base);
-            }
-        } else if (A->drow) {
-            q.pbase = A->h_drow[r0 - nbr];
-            q.npe = (int32_t)(A->h_drow[r1 - nbr] - q.pbase);
-        }
-    }
+    std::vector<TileDesc> td;
+    td.reserve((size_t)A->ntiles);
+    for (const PlanTile &t : plan_tiles(tile_input(A), tp)) td.push_back(TileDesc{t.base, t.pbase, t.r0, t.nrows, t.n, t.npe});
     if (A->tile_ptr) NPG_HIP(hipFree(A->tile_ptr));
+    A->tile_ptr = nullptr;
     A->gen++;
     NPG_HIP(hipMalloc((void **)&A->tile_ptr, std::max<size_t>(1, td.size()) * sizeof(TileDesc)));
     NPG_HIP(hipMemcpy(A->tile_ptr, td.data(), td.size() * sizeof(TileDesc), hipMemcpyHostToDevice));
@@ -108,15 +74,14 @@ int build_tiles(npg_csr *A) {
     if (A->n > A->m && A->ntiles > 0 && (A->rnnz > 0 || A->ngrec > 0)) {
         // row block of a distributed matrix: tiles that read no ghost column come first, so that a solver can run them
         // while the halo exchange is in flight (record columns are owned nodes by construction: only the CSR part counts)
-        int32_t *dflag;
+        DevBuf<int32_t> dflag;
         std::vector<int32_t> flag((size_t)A->ntiles, 0);
-        NPG_HIP(hipMalloc((void **)&dflag, flag.size() * sizeof(int32_t)));
-        NPG_HIP(hipMemsetAsync(dflag, 0, flag.size() * sizeof(int32_t), A->ctx->stream));
+        NPG_HIP(dflag.alloc(flag.size()));
+        NPG_HIP(hipMemsetAsync(dflag.p, 0, flag.size() * sizeof(int32_t), A->ctx->stream));
         hipLaunchKernelGGL(k_tile_ghost_flags, dim3(std::min<int>(A->ntiles, 4096)), dim3(64), 0, A->ctx->stream, A->tile_ptr,
-                           A->ntiles, A->col, (const int32_t *)A->gcol, (int32_t)A->block_rows(), (int32_t)A->m, dflag);
+                           A->ntiles, A->col, (const int32_t *)A->gcol, (int32_t)A->block_rows(), (int32_t)A->m, dflag.p);
         NPG_HIP(hipMemcpyAsync(flag.data(), dflag, flag.size() * sizeof(int32_t), hipMemcpyDeviceToHost, A->ctx->stream));
         NPG_HIP(hipStreamSynchronize(A->ctx->stream));
-        NPG_HIP(hipFree(dflag));
         std::vector<TileDesc> ord;
         ord.reserve(td.size());
         for (int pass = 0; pass < 2; ++pass) {
@@ -130,464 +95,99 @@ int build_tiles(npg_csr *A) {
     return NPG_OK;
 }
 
-static void free_window_tiles(npg_csr *A) {
-    for (void *p : {(void *)A->wtile_ptr, (void *)A->widx, (void *)A->gidx, (void *)A->wlist, (void *)A->vlist, (void *)A->wbk, (void *)A->dwidx, (void *)A->dbk, (void *)A->pkc2, (void *)A->dxy2,
-                    (void *)A->gslot, (void *)A->wgval, (void *)A->wdz})
-        if (p) hipFree(p);
-    A->gslot = nullptr;
-    A->wgval = nullptr;
-    A->wdz = nullptr;
-    A->nw_grec = A->nw_rec = A->nw_drec = 0;
-    A->wtile_ptr = nullptr;
-    A->widx = A->gidx = nullptr;
-    A->wlist = A->vlist = nullptr;
-    A->wbk = A->dbk = nullptr;
-    A->pkc2 = A->dxy2 = nullptr;
-    A->dwidx = nullptr;
-    A->nwrow_tiles = 0;
-    A->nwtiles = A->nwtiles_interior = 0;
-    A->nwlist = A->nvlist = 0;
+// ---- a plan (csr_records_core.h) onto the device: into a CANDIDATE handle, which replaces the caller's only when it stands ----------
+// Upload into an owned array.  An empty array still gets 16 bytes, so that a non-null pointer keeps meaning "this kind of record
+// exists" (table at check_record_view, common.h) and a kernel's idle 16-byte load has something to read.
+// once_read: the record streams of the windowed set go to uncached device memory with NPG_WIN_UNCACHED=1 (experiment: they then do
+// not displace the Krylov basis and the gather-layout copy from L2 / the Infinity Cache); that switch is read ONCE PER PROCESS.
+static bool win_uncached() {
+    static const bool on = env_int("NPG_WIN_UNCACHED", 0) != 0;
+    return on;
 }
-
-// The windowed tile set of a node-blocked matrix in all-record form (spmv_window.h): a second tiling of the block rows whose
-// tiles are sized by what they need in LDS - pair-summed products, column-record products, the window of distinct column
-// nodes (16 B each) and of distinct other columns (4 B each) - followed by the ordinary tiles of the rows behind the block
-// rows.  pcol / gcol: host copies of the record columns (every node's list already padded to an even count).
-// Leaves the matrix without a windowed set (no error) when some node's rows would not fit a tile.
-static int build_window_tiles_scaled(npg_csr *A, const std::vector<int32_t> &pcol_in, const std::vector<int32_t> &gcol_in,
-                                     const std::vector<int32_t> &dcol_in, const std::vector<double> &pkc_in, const std::vector<double> &dxy_in,
-                                     const std::vector<double> &gxy_in, const std::vector<double> &gz_in, const std::vector<double> &dz_in,
-                                     const std::vector<int32_t> &rcol, const std::vector<double> &rval, double scale) {
-    free_window_tiles(A);
-    const int64_t nnode = A->nnode(), nfull = A->nfull, nbr = A->block_rows();
-    if (nnode == 0 || !A->grow || A->pk9) return NPG_OK;
-    // ---- ghost nodes (npg_csr_set_ghost_nodes): the column records of a row node that reference the components of ONE ghost node
-    // and carry the {K, C} structure (A[x_q,x_c] = A[y_q,y_c] = A[z_q,z_c] = K, A[x_q,y_c] = -A[y_q,x_c] = C, nothing else) become a
-    // node record with column node nnode + g in THIS tile set's own record arrays; everything else is carried over unchanged
-    const int64_t ngn = A->ngn();
-    std::vector<int64_t> wprow, wgrow;
-    std::vector<int32_t> wpcol, wgcol;
-    std::vector<double> wpkc, wgxy, wgz;
-    int64_t converted = 0;
-    std::vector<int32_t> gnode((size_t)std::max<int64_t>(A->n - A->m, 0), -1), gcomp(gnode.size(), 0);
-    if (ngn > 0) {
-        for (int64_t g = 0; g < ngn; ++g)
-            for (int a = 0; a < A->gn_ncomp[(size_t)g]; ++a) {
-                gnode[(size_t)(A->gn_col[(size_t)g] - A->m + a)] = (int32_t)g;
-                gcomp[(size_t)(A->gn_col[(size_t)g] - A->m + a)] = a;
-            }
-        const std::vector<int64_t> &prow0 = A->h_prow, &grow0 = A->h_grow;
-        wprow.assign((size_t)nnode + 1, 0);
-        wgrow.assign((size_t)nnode + 1, 0);
-        std::vector<int64_t> slot;           // per ghost node touched by the current row node: index of its records by component
-        for (int64_t q = 0; q < nnode; ++q) {
-            const bool qfull = q < nfull;
-            // the node's own records, without the zero record that padded them (it is re-made below)
-            int64_t pe = prow0[q + 1];
-            if (pe - prow0[q] >= 2 && pkc_in[2 * (pe - 1)] == 0.0 && pkc_in[2 * (pe - 1) + 1] == 0.0 && pcol_in[pe - 1] == pcol_in[pe - 2]) --pe;
-            for (int64_t e = prow0[q]; e < pe; ++e) {
-                wpcol.push_back(pcol_in[e]);
-                wpkc.push_back(pkc_in[2 * e]);
-                wpkc.push_back(pkc_in[2 * e + 1]);
-            }
-            double scale_q = 0.0;
-            for (int64_t e = prow0[q]; e < pe; ++e) scale_q = std::max(scale_q, std::fabs(pkc_in[2 * e]));
-            const double tol = 1e-12 * scale_q;
-            // column records, ascending columns: the components of a ghost node are adjacent
-            for (int64_t e = grow0[q]; e < grow0[q + 1];) {
-                const int64_t m0 = gcol_in[e];
-                const int32_t g = m0 >= A->m ? gnode[(size_t)(m0 - A->m)] : -1;
-                if (g < 0 || gcomp[(size_t)(m0 - A->m)] != 0) {
-                    wgcol.push_back(gcol_in[e]);
-                    wgxy.push_back(gxy_in[2 * e]);
-                    wgxy.push_back(gxy_in[2 * e + 1]);
-                    wgz.push_back(gz_in[e]);
-                    ++e;
-                    continue;
-                }
-                // records of this ghost node: columns m0 (x), m0 + 1 (y)[, m0 + 2 (z)], any of them possibly absent
-                const int nc = A->gn_ncomp[(size_t)g];
-                int64_t rec[3] = {-1, -1, -1}, e1 = e;
-                while (e1 < grow0[q + 1] && gcol_in[e1] < m0 + nc) {
-                    rec[gcol_in[e1] - m0] = e1;
-                    ++e1;
-                }
-                auto val = [&](int c, int a) { return rec[c] < 0 ? 0.0 : (a == 2 ? gz_in[rec[c]] : gxy_in[2 * rec[c] + a]); };
-                const double K = val(0, 0), Cc = val(1, 0);
-                bool ok = std::fabs(val(1, 1) - K) <= tol && std::fabs(val(0, 1) + Cc) <= tol && std::fabs(val(0, 2)) <= tol &&
-                          std::fabs(val(1, 2)) <= tol;
-                if (nc == 3) ok = ok && std::fabs(val(2, 0)) <= tol && std::fabs(val(2, 1)) <= tol && (!qfull || std::fabs(val(2, 2) - K) <= tol);
-                if (ok) {
-                    wpcol.push_back((int32_t)(nnode + g));
-                    wpkc.push_back(K);
-                    wpkc.push_back(Cc);
-                    ++converted;
-                } else {
-                    for (int64_t k = e; k < e1; ++k) {
-                        wgcol.push_back(gcol_in[k]);
-                        wgxy.push_back(gxy_in[2 * k]);
-                        wgxy.push_back(gxy_in[2 * k + 1]);
-                        wgz.push_back(gz_in[k]);
-                    }
-                }
-                e = e1;
-            }
-            if (((int64_t)wpcol.size() - wprow[q]) & 1) {            // zero record on the node's last column node
-                wpcol.push_back(wpcol.back());
-                wpkc.push_back(0.0);
-                wpkc.push_back(0.0);
-            }
-            wprow[q + 1] = (int64_t)wpcol.size();
-            wgrow[q + 1] = (int64_t)wgcol.size();
-        }
+template <class T>
+static hipError_t upload_min(DevBuf<T> &d, const std::vector<T> &v, bool once_read = false) {
+    const size_t n = v.size();
+    hipError_t e;
+    if (once_read && win_uncached() && n * sizeof(T) >= (1u << 20)) {
+        void *q = nullptr;
+        if ((e = hipExtMallocWithFlags(&q, n * sizeof(T), hipDeviceMallocUncached)) == hipSuccess) d.adopt((T *)q);
+    } else {
+        e = d.alloc(std::max<size_t>(n, (15 + sizeof(T)) / sizeof(T)));
     }
-    const bool own = ngn > 0 && converted > 0;
-    const std::vector<int64_t> &prow = own ? wprow : A->h_prow, &grow = own ? wgrow : A->h_grow;
-    const std::vector<int32_t> &pcol = own ? wpcol : pcol_in, &gcol = own ? wgcol : gcol_in;
-    const std::vector<double> &pkc = own ? wpkc : pkc_in;
-    const int64_t nwin_nodes = nnode + (own ? ngn : 0);
-    constexpr int NT = 512;
-    int64_t hard = 8 * (int64_t)kTileNnz;
-    if (getenv("NPG_WIN_BYTES")) hard = std::min<int64_t>(hard, std::max<int64_t>(8192, atoll(getenv("NPG_WIN_BYTES"))));    // tuning: smaller tiles
-    scale = std::min(1.0, std::max(0.25, scale));       // all caps of a tile scaled (build_window_tiles; NPG_WIN_SCALE)
-    hard = (int64_t)(scale * (double)hard);
-    const int64_t cap_p = (int64_t)(scale * kWinPairs * NT), cap_c = (int64_t)(scale * kWinCols * NT);
-    // small matrices: about one tile per CU (as tile_boundaries does)
-    const int64_t total = 8 * (3 * (prow[nfull] / 2 + grow[nfull]) + 2 * ((prow[nnode] - prow[nfull]) / 2 + grow[nnode] - grow[nfull]));
-    const int64_t soft = std::min<int64_t>(hard, std::max<int64_t>(8 * 1024, total / std::max(1, A->ctx->num_cu)));
-    std::vector<int32_t> stampW((size_t)nwin_nodes, -1), stampV((size_t)A->n, -1), posW((size_t)nwin_nodes, 0), posV((size_t)A->n, 0);
-    std::vector<uint16_t> widx(pcol.size()), gidx(gcol.size());
-    std::vector<int32_t> wlist, vlist, tw, tv, nwl, nvl, wbk((size_t)2 * nnode);
-    std::vector<WTileDesc> blk;
-    std::vector<char> ghost;
-    auto bytes_of = [](int ncomp, int64_t np, int64_t ng, int64_t nw, int64_t nv) {
-        const int64_t slots = ncomp * (np + ng);
-        return 8 * ((slots + 1) & ~(int64_t)1) + 16 * nw + 4 * nv;
-    };
-    for (int kind = 0; kind < 2; ++kind) {
-        const int64_t lo = kind ? nfull : 0, hi = kind ? nnode : nfull;
-        const int ncomp = kind ? 2 : 3;
-        int64_t q = lo;
-        while (q < hi) {
-            const int32_t T = (int32_t)blk.size();
-            tw.clear();
-            tv.clear();
-            int64_t np = 0, ng = 0, qe = q;
-            while (qe < hi) {
-                nwl.clear();
-                nvl.clear();
-                for (int64_t e = prow[qe]; e < prow[qe + 1]; ++e)
-                    if (stampW[pcol[e]] != T) {
-                        stampW[pcol[e]] = T;
-                        nwl.push_back(pcol[e]);
-                    }
-                for (int64_t e = grow[qe]; e < grow[qe + 1]; ++e)
-                    if (stampV[gcol[e]] != T) {
-                        stampV[gcol[e]] = T;
-                        nvl.push_back(gcol[e]);
-                    }
-                const int64_t np2 = np + (prow[qe + 1] - prow[qe]) / 2, ng2 = ng + (grow[qe + 1] - grow[qe]);
-                const int64_t nw2 = (int64_t)(tw.size() + nwl.size()), nv2 = (int64_t)(tv.size() + nvl.size());
-                const int64_t by = bytes_of(ncomp, np2, ng2, nw2, nv2);
-                const bool shape = (qe + 1 - q) * ncomp <= kTileRows && np2 <= cap_p && ng2 <= cap_c && nw2 <= kWinNodes * NT && nv2 <= NT;
-                if (qe == q && !(shape && by <= hard)) return NPG_OK;       // one node's rows do not fit: no windowed set
-                if (qe > q && !(shape && by <= soft)) {
-                    for (int32_t c : nwl) stampW[c] = -1;
-                    for (int32_t c : nvl) stampV[c] = -1;
-                    break;
-                }
-                tw.insert(tw.end(), nwl.begin(), nwl.end());
-                tv.insert(tv.end(), nvl.begin(), nvl.end());
-                np = np2;
-                ng = ng2;
-                ++qe;
-            }
-            std::sort(tw.begin(), tw.end());
-            std::sort(tv.begin(), tv.end());
-            for (size_t i = 0; i < tw.size(); ++i) posW[tw[i]] = (int32_t)i;
-            for (size_t i = 0; i < tv.size(); ++i) posV[tv[i]] = (int32_t)i;
-            for (int64_t e = prow[q]; e < prow[qe]; ++e) widx[e] = (uint16_t)posW[pcol[e]];
-            for (int64_t e = grow[q]; e < grow[qe]; ++e) gidx[e] = (uint16_t)posV[gcol[e]];
-            for (int64_t k = q; k < qe; ++k) {
-                wbk[2 * k] = (int32_t)(grow[k + 1] - grow[q]);
-                wbk[2 * k + 1] = (int32_t)((prow[k + 1] - prow[q]) >> 1);
-            }
-            WTileDesc d;
-            d.r0 = (int32_t)(kind ? 3 * nfull + 2 * (q - nfull) : 3 * q);
-            d.nrows = (int32_t)((qe - q) * ncomp);
-            d.base = grow[q];
-            d.n = (int32_t)ng;
-            d.pbase = prow[q];
-            d.npe = (int32_t)(2 * np);
-            d.woff = (int32_t)wlist.size();
-            d.nw = (int32_t)tw.size();
-            d.voff = (int32_t)vlist.size();
-            d.nv = (int32_t)tv.size();
-            if (d.nw == 0) return NPG_OK;        // a tile of nodes without any entry in the block columns: no windowed set
-            wlist.insert(wlist.end(), tw.begin(), tw.end());
-            vlist.insert(vlist.end(), tv.begin(), tv.end());
-            blk.push_back(d);
-            ghost.push_back((!tv.empty() && tv.back() >= A->m) || tw.back() >= nnode);   // (ghost columns; ghost nodes as record columns)
-            q = qe;
-        }
-    }
-    // The rows behind the block rows (the divergence rows) as windowed tiles too, when all they hold is coupling records: two
-    // adjacent records of a row per lane (every row's list is padded to an even count), at most kWinPairs pairs per lane and
-    // kWinNodes distinct column nodes per lane - small tiles, one dependent chain each (the ordinary tile function walks such
-    // a row block in four trips of two round trips).  NPG_WIN_ROWS=0: ordinary tiles for these rows.
-    std::vector<WTileDesc> rowt;
-    std::vector<char> rghost;
-    std::vector<uint16_t> dwidx;
-    std::vector<int32_t> dbk;
-    const int64_t nbehind = A->m - nbr;
-    const bool rows_env = !(getenv("NPG_WIN_ROWS") && atoi(getenv("NPG_WIN_ROWS")) == 0);
-    // A rank's row block with ghost nodes: what the rows behind the block rows (the divergence rows) hold on ghost columns is CSR
-    // remainder for the ordinary tiles; for THIS tile set the entries on a ghost node's components become one coupling record
-    // {nnode + g, d_x, d_y, d_z} behind the row's owned-node records - if that accounts for every remaining entry of those rows,
-    // they are windowed like a one-GPU matrix's (and the Arnoldi kernel runs its instance without ordinary tile code)
-    std::vector<int64_t> wdrow;
-    std::vector<int32_t> wdcol;
-    std::vector<double> wdxy, wdz;
-    bool rows_own = false;
-    if (own && rows_env && A->drow && nbehind > 0 && A->n > A->m) {
-        rows_own = true;
-        wdrow.assign((size_t)nbehind + 1, 0);
-        const std::vector<int64_t> &d0 = A->h_drow, &rp0 = A->h_rowptr;
-        for (int64_t r = 0; r < nbehind && rows_own; ++r) {
-            int64_t e1 = d0[r + 1];
-            if (e1 - d0[r] >= 2 && dxy_in[2 * (e1 - 1)] == 0.0 && dxy_in[2 * (e1 - 1) + 1] == 0.0 && dz_in[e1 - 1] == 0.0 &&
-                dcol_in[e1 - 1] == dcol_in[e1 - 2])
-                --e1;                                                    // (the zero record that padded the list: re-made below)
-            for (int64_t e = d0[r]; e < e1; ++e) {
-                wdcol.push_back(dcol_in[e]);
-                wdxy.push_back(dxy_in[2 * e]);
-                wdxy.push_back(dxy_in[2 * e + 1]);
-                wdz.push_back(dz_in[e]);
-            }
-            int32_t cur = -1;
-            for (int64_t k = rp0[nbr + r]; k < rp0[nbr + r + 1]; ++k) {
-                const int64_t m0 = rcol[k];
-                const int32_t g = m0 >= A->m ? gnode[(size_t)(m0 - A->m)] : -1;
-                if (g < 0) {
-                    rows_own = false;                                    // an entry that is no node component: ordinary tiles for these rows
-                    break;
-                }
-                if (g != cur) {
-                    wdcol.push_back((int32_t)(nnode + g));
-                    wdxy.push_back(0.0);
-                    wdxy.push_back(0.0);
-                    wdz.push_back(0.0);
-                    cur = g;
-                }
-                const int a = gcomp[(size_t)(m0 - A->m)];
-                if (a == 2) wdz.back() = rval[k];
-                else wdxy[wdxy.size() - 2 + a] = rval[k];
-            }
-            if (((int64_t)wdcol.size() - wdrow[r]) & 1) {
-                wdcol.push_back(wdcol.back());
-                wdxy.push_back(0.0);
-                wdxy.push_back(0.0);
-                wdz.push_back(0.0);
-            }
-            wdrow[r + 1] = (int64_t)wdcol.size();
-        }
-    }
-    const std::vector<int32_t> &dcol = rows_own ? wdcol : dcol_in;
-    const std::vector<double> &dxy = rows_own ? wdxy : dxy_in;
-    if (rows_env && A->drow && nbehind > 0 && ((A->h_rowptr[A->m] - A->h_rowptr[nbr] == 0 && A->n == A->m) || rows_own)) {
-        const std::vector<int64_t> &drow = rows_own ? wdrow : A->h_drow;
-        dwidx.assign(dcol.size(), 0);
-        dbk.assign((size_t)nbehind, 0);
-        int64_t cap_pairs = cap_p;
-        {       // small matrices: about as many tiles as the block rows got per byte
-            const int64_t want = std::max<int64_t>(1, (int64_t)blk.size() * (drow[nbehind] * 28) / std::max<int64_t>(1, total * 3));
-            cap_pairs = std::min<int64_t>(cap_pairs, std::max<int64_t>(64, drow[nbehind] / 2 / want));
-        }
-        int64_t r = 0;
-        bool ok = true;
-        const size_t wlist_blk = wlist.size();
-        while (r < nbehind && ok) {
-            const int32_t T = (int32_t)(blk.size() + rowt.size());
-            tw.clear();
-            int64_t np = 0, re = r;
-            while (re < nbehind) {
-                nwl.clear();
-                for (int64_t e = drow[re]; e < drow[re + 1]; ++e)
-                    if (stampW[dcol[e]] != T) {
-                        stampW[dcol[e]] = T;
-                        nwl.push_back(dcol[e]);
-                    }
-                const int64_t np2 = np + (drow[re + 1] - drow[re]) / 2, nw2 = (int64_t)(tw.size() + nwl.size());
-                const bool hardfit = re + 1 - r <= kTileRows / 2 && np2 <= kWinPairs * NT && nw2 <= kWinNodes * NT &&
-                                     8 * ((np2 + 1) & ~(int64_t)1) + 16 * nw2 <= hard;
-                if (re == r && !hardfit) {
-                    ok = false;
-                    break;
-                }
-                if (re > r && !(hardfit && np2 <= cap_pairs)) {
-                    for (int32_t c : nwl) stampW[c] = -1;
-                    break;
-                }
-                tw.insert(tw.end(), nwl.begin(), nwl.end());
-                np = np2;
-                ++re;
-            }
-            if (!ok) break;
-            std::sort(tw.begin(), tw.end());
-            for (size_t i = 0; i < tw.size(); ++i) posW[tw[i]] = (int32_t)i;
-            for (int64_t e = drow[r]; e < drow[re]; ++e) dwidx[e] = (uint16_t)posW[dcol[e]];
-            for (int64_t k = r; k < re; ++k) dbk[k] = (int32_t)((drow[k + 1] - drow[r]) >> 1);
-            WTileDesc d;
-            d.r0 = (int32_t)(nbr + r);
-            d.nrows = (int32_t)(re - r);
-            d.base = 0;
-            d.n = 0;
-            d.pbase = drow[r];
-            d.npe = (int32_t)(2 * np);
-            d.woff = (int32_t)wlist.size();
-            d.nw = (int32_t)tw.size();
-            d.voff = (int32_t)vlist.size();
-            d.nv = 0;
-            if (d.nw == 0) {            // (a block of empty rows: nothing to window)
-                ok = false;
-                break;
-            }
-            wlist.insert(wlist.end(), tw.begin(), tw.end());
-            rowt.push_back(d);
-            rghost.push_back(tw.back() >= nnode);
-            r = re;
-        }
-        if (!ok) {          // (ordinary tiles for these rows: the lists of the row tiles made so far go with them)
-            rowt.clear();
-            wlist.resize(wlist_blk);
-        }
-    }
-    vlist.push_back((int32_t)nbr);           // sentinel: a tile without such columns still reads one entry at its offset
-    NPG_REQUIRE(wlist.size() < (size_t)INT32_MAX && vlist.size() < (size_t)INT32_MAX, "build_window_tiles: window lists exceed int32 offsets");
-    // the tiles of the rows behind the block rows: windowed (above), or as build_tiles made (and ordered) them
-    std::vector<WTileDesc> ord;
-    ord.reserve(blk.size() + A->h_tiles.size() + rowt.size());
-    auto widen = [](const TileDesc &t) { return WTileDesc{t.base, t.pbase, t.r0, t.nrows, t.n, t.npe, 0, 0, 0, 0}; };
-    int32_t nint = 0;
-    // order within a pass (tuning, NPG_WIN_ORDER): 0 = block tiles, then the rows behind them; 1 = the other way round;
-    // 2 = the tiles of the rows behind the block rows spread evenly among the block tiles
-    const int order = getenv("NPG_WIN_ORDER") ? atoi(getenv("NPG_WIN_ORDER")) : 0;
-    for (int pass = 0; pass < 2; ++pass) {
-        std::vector<WTileDesc> a, b;
-        for (size_t t = 0; t < blk.size(); ++t)
-            if ((ghost[t] != 0) == (pass == 1)) a.push_back(blk[t]);
-        if (!rowt.empty()) {
-            for (size_t t = 0; t < rowt.size(); ++t)
-                if ((rghost[t] != 0) == (pass == 1)) b.push_back(rowt[t]);
-        } else {
-            for (int32_t t = 0; t < A->ntiles; ++t)
-                if (A->h_tiles[t].r0 >= nbr && (t >= A->ntiles_interior) == (pass == 1)) b.push_back(widen(A->h_tiles[t]));
-        }
-        if (order == 1) {
-            ord.insert(ord.end(), b.begin(), b.end());
-            ord.insert(ord.end(), a.begin(), a.end());
-        } else if (order == 2 && !b.empty()) {
-            size_t ib = 0;
-            for (size_t ia = 0; ia < a.size(); ++ia) {
-                while (ib < b.size() && ib * a.size() <= ia * b.size()) ord.push_back(b[ib++]);
-                ord.push_back(a[ia]);
-            }
-            while (ib < b.size()) ord.push_back(b[ib++]);
-        } else {
-            ord.insert(ord.end(), a.begin(), a.end());
-            ord.insert(ord.end(), b.begin(), b.end());
-        }
-        if (pass == 0) nint = (int32_t)ord.size();
-    }
-    // NPG_WIN_UNCACHED=1 (experiment): the once-read record streams in uncached device memory, so that they do not displace the
-    // Krylov basis and the gather-layout copy from L2 / the Infinity Cache
-    static const bool uncached = getenv("NPG_WIN_UNCACHED") && atoi(getenv("NPG_WIN_UNCACHED")) != 0;
-    auto up = [&](void **dst, const void *src, size_t bytes) -> int {
-        if (uncached && bytes >= (1u << 20))
-            NPG_HIP(hipExtMallocWithFlags(dst, bytes, hipDeviceMallocUncached));
-        else
-            NPG_HIP(hipMalloc(dst, std::max<size_t>(bytes, 16)));
-        if (bytes) NPG_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-        return NPG_OK;
-    };
-    int rc = NPG_OK;
-    auto chk = [&](int r) { if (rc == NPG_OK) rc = r; };
-    chk(up((void **)&A->wtile_ptr, ord.data(), ord.size() * sizeof(WTileDesc)));
-    chk(up((void **)&A->widx, widx.data(), widx.size() * sizeof(uint16_t)));
-    chk(up((void **)&A->gidx, gidx.data(), gidx.size() * sizeof(uint16_t)));
-    chk(up((void **)&A->wlist, wlist.data(), wlist.size() * sizeof(int32_t)));
-    chk(up((void **)&A->vlist, vlist.data(), vlist.size() * sizeof(int32_t)));
-    chk(up((void **)&A->wbk, wbk.data(), wbk.size() * sizeof(int32_t)));
-    {       // the {K, C} values once more, split by position in the pair: [pairs] first records, then [pairs] second records -
-            // a lane's two 16-byte loads are then each part of a fully contiguous stream (the interleaved pkc gives 32-byte strides)
-        const size_t P = pcol.size() / 2;
-        std::vector<double> k2(4 * P);
-        for (size_t pr = 0; pr < P; ++pr) {
-            k2[2 * pr] = pkc[4 * pr];
-            k2[2 * pr + 1] = pkc[4 * pr + 1];
-            k2[2 * P + 2 * pr] = pkc[4 * pr + 2];
-            k2[2 * P + 2 * pr + 1] = pkc[4 * pr + 3];
-        }
-        chk(up((void **)&A->pkc2, k2.data(), k2.size() * sizeof(double)));
-        A->npairs = (int64_t)P;
-    }
-    if (!rowt.empty()) {
-        chk(up((void **)&A->dwidx, dwidx.data(), dwidx.size() * sizeof(uint16_t)));
-        chk(up((void **)&A->dbk, dbk.data(), dbk.size() * sizeof(int32_t)));
-        const size_t P = dcol.size() / 2;      // (d_x, d_y) split by position in the record pair, like pkc2
-        std::vector<double> d2(4 * P);
-        for (size_t pr = 0; pr < P; ++pr) {
-            d2[2 * pr] = dxy[4 * pr];
-            d2[2 * pr + 1] = dxy[4 * pr + 1];
-            d2[2 * P + 2 * pr] = dxy[4 * pr + 2];
-            d2[2 * P + 2 * pr + 1] = dxy[4 * pr + 3];
-        }
-        chk(up((void **)&A->dxy2, d2.data(), d2.size() * sizeof(double)));
-        A->ndpairs = (int64_t)P;
-        if (rows_own) chk(up((void **)&A->wdz, wdz.data(), wdz.size() * sizeof(double)));
-        A->nw_drec = (int64_t)dcol.size();
-    }
-    if (own) {
-        std::vector<double> gv(3 * wgz.size());
-        std::copy(wgxy.begin(), wgxy.end(), gv.begin());
-        std::copy(wgz.begin(), wgz.end(), gv.begin() + (ptrdiff_t)wgxy.size());
-        chk(up((void **)&A->wgval, gv.data(), gv.size() * sizeof(double)));
-        // where the halo unpack stores a ghost column's float beside its place behind the owned entries: its node's 4-float slot
-        std::vector<int32_t> gs((size_t)(A->n - A->m), -1);
-        for (int64_t g = 0; g < ngn; ++g)
-            for (int a = 0; a < A->gn_ncomp[(size_t)g]; ++a) gs[(size_t)(A->gn_col[(size_t)g] - A->m + a)] = (int32_t)(4 * (nnode + g) + a);
-        chk(up((void **)&A->gslot, gs.data(), gs.size() * sizeof(int32_t)));
-    }
-    A->nw_grec = (int64_t)gcol.size();
-    A->nw_rec = prow[nnode];
-    A->nwrow_tiles = (int32_t)rowt.size();
-    if (rc != NPG_OK) {
-        free_window_tiles(A);
-        return rc;
-    }
-    A->nwtiles = (int32_t)ord.size();
-    A->nwtiles_interior = nint;
-    A->nwlist = (int64_t)wlist.size();
-    A->nvlist = (int64_t)vlist.size();
-    // lanes per node in the segmented sums of a windowed tile (a lane takes two slots per trip): measured on bowl3D h = 0.02
-    // (14 pair slots + 8 column-record slots per row, 64 nodes per tile) 8 lanes 136.9 us per product against 142.6 with 4
-    const double mean = (double)(prow[nnode] / 2 + grow[nnode]) / (double)nnode;
-    A->wlanes = mean <= 12 ? 4 : 8;
-    if (getenv("NPG_SPMV_WLANES")) A->wlanes = atoi(getenv("NPG_SPMV_WLANES")) == 8 ? 8 : 4;
-    A->gen++;
+    return e == hipSuccess && n ? hipMemcpy(d.p, v.data(), n * sizeof(T), hipMemcpyHostToDevice) : e;
+}
+// [2 n] (x, y) pairs followed by [n] z: the layout of gval / dval
+static hipError_t upload_xyz(DevBuf<double> &d, const std::vector<double> &xy, const std::vector<double> &z) {
+    hipError_t e = d.alloc(std::max<size_t>(3 * z.size(), 2));
+    if (e == hipSuccess && !z.empty()) e = hipMemcpy(d.p, xy.data(), xy.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !z.empty()) e = hipMemcpy(d.p + xy.size(), z.data(), z.size() * sizeof(double), hipMemcpyHostToDevice);
+    return e;
+}
+// the pattern arrays stay raw beside owns_pattern (a clone shares them with its pattern owner)
+static int upload_pattern(npg_csr *C, const std::vector<int64_t> &rowptr, const std::vector<int32_t> &col) {
+    C->owns_pattern = true;
+    NPG_HIP(hipMalloc((void **)&C->rowptr, rowptr.size() * sizeof(int64_t)));
+    NPG_HIP(hipMalloc((void **)&C->col, std::max<size_t>(4, col.size()) * sizeof(int32_t)));
+    NPG_HIP(hipMemcpy(C->rowptr, rowptr.data(), rowptr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (!col.empty()) NPG_HIP(hipMemcpy(C->col, col.data(), col.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    C->h_rowptr = rowptr;
+    C->rnnz = (int64_t)col.size();
     return NPG_OK;
 }
 
-// The windowed tile set at full tile size (NPG_WIN_SCALE: all caps of a tile scaled, tuning).  A rule that shrinks the tiles of
-// small matrices until their number fills a whole number of rounds of the 3 x num_cu persistent workgroups was measured and
-// dropped: bowl3D h = 0.04 (2.2 -> 2.9 rounds) 27.5 -> 29.0 us per Arnoldi launch, h = 0.05 (1.1 -> 1.9 rounds) 18.8 -> 20.6 us -
-// the workgroups do not move in rounds, and smaller tiles cost more than a partly filled last round (profiles/r04_windowed_tiles.txt).
-static int build_window_tiles(npg_csr *A, const std::vector<int32_t> &pcol, const std::vector<int32_t> &gcol,
-                              const std::vector<int32_t> &dcol, const std::vector<double> &pkc, const std::vector<double> &dxy,
-                              const std::vector<double> &gxy, const std::vector<double> &gz, const std::vector<double> &dz,
-                              const std::vector<int32_t> &rcol, const std::vector<double> &rval) {
-    const double s_env = getenv("NPG_WIN_SCALE") ? atof(getenv("NPG_WIN_SCALE")) : -1.0;
-    return build_window_tiles_scaled(A, pcol, gcol, dcol, pkc, dxy, gxy, gz, dz, rcol, rval, s_env > 0 ? s_env : 1.0);
+struct CsrDeleter {
+    void operator()(npg_csr *A) const { npg_csr_destroy(A); }
+};
+using CsrCandidate = std::unique_ptr<npg_csr, CsrDeleter>;
+
+// the switches of one conversion (defaults and clamps as they always were)
+static RecordSwitches record_switches() {
+    RecordSwitches s;
+    s.window = env_int("NPG_SPMV_WINDOW", 1) != 0;
+    s.column_records = env_int("NPG_SPMV_COLUMN_RECORDS", 1) != 0;
+    s.coupling = env_int("NPG_SPMV_COUPLING", 1) != 0;
+    s.win_rows = env_int("NPG_WIN_ROWS", 1) != 0;
+    if (getenv("NPG_WIN_BYTES")) s.win_bytes = std::max<int64_t>(8192, env_int64("NPG_WIN_BYTES", 0));
+    const double scale = getenv("NPG_WIN_SCALE") ? atof(getenv("NPG_WIN_SCALE")) : -1.0;
+    s.win_scale = scale > 0 ? scale : 1.0;
+    s.win_order = env_int("NPG_WIN_ORDER", 0);
+    if (getenv("NPG_SPMV_WLANES")) s.wlanes = env_int("NPG_SPMV_WLANES", 0) == 8 ? 8 : 4;
+    return s;
+}
+
+static int upload_window(npg_csr::WindowSet &w, const WindowPlan &W) {
+    std::vector<WTileDesc> td;
+    td.reserve(W.tiles.size());
+    for (const PlanTile &t : W.tiles) td.push_back(WTileDesc{t.base, t.pbase, t.r0, t.nrows, t.n, t.npe, t.woff, t.voff, t.nw, t.nv});
+    NPG_HIP(upload_min(w.wtile_ptr, td, true));
+    NPG_HIP(upload_min(w.widx, W.widx, true));
+    NPG_HIP(upload_min(w.gidx, W.gidx, true));
+    NPG_HIP(upload_min(w.wlist, W.wlist, true));
+    NPG_HIP(upload_min(w.vlist, W.vlist, true));
+    NPG_HIP(upload_min(w.wbk, W.wbk, true));
+    NPG_HIP(upload_min(w.pkc2, W.pkc2, true));
+    if (W.nrow_tiles) {
+        NPG_HIP(upload_min(w.dwidx, W.dwidx, true));
+        NPG_HIP(upload_min(w.dbk, W.dbk, true));
+        NPG_HIP(upload_min(w.dxy2, W.dxy2, true));
+        if (W.rows_own) NPG_HIP(upload_min(w.wdz, W.wdz, true));
+    }
+    if (W.own) {
+        NPG_HIP(upload_min(w.wgval, W.wgval, true));
+        NPG_HIP(upload_min(w.gslot, W.gslot, true));
+    }
+    w.npairs = W.npairs;
+    w.ndpairs = W.ndpairs;
+    w.nw_grec = W.nw_grec;
+    w.nw_rec = W.nw_rec;
+    w.nw_drec = W.nw_drec;
+    w.nwrow_tiles = W.nrow_tiles;
+    w.nwtiles = (int32_t)W.tiles.size();
+    w.nwtiles_interior = W.ninterior;
+    w.nwlist = (int64_t)W.wlist.size();
+    w.nvlist = (int64_t)W.vlist.size();
+    w.wlanes = W.wlanes;
+    return NPG_OK;
 }
 
 constexpr int kSpmvThreads = 512;
@@ -667,25 +267,18 @@ __global__ void k_inv_diag(const int64_t *rowptr, const int32_t *col, const doub
 
 static int upload_csr(npg_ctx *ctx, int64_t m, int64_t n, std::vector<int64_t> &&rowptr, const std::vector<int32_t> &col,
                       const std::vector<double> &val, npg_csr **out) {
-    npg_csr *A = new npg_csr();
+    CsrCandidate A(new npg_csr());
     A->ctx = ctx;
     A->m = m;
     A->n = n;
     A->nnz = (int64_t)col.size();
-    A->rnnz = A->nnz;
     NPG_HIP(hipSetDevice(ctx->device));
-    NPG_HIP(hipMalloc((void **)&A->rowptr, (size_t)(m + 1) * sizeof(int64_t)));
-    NPG_HIP(hipMalloc((void **)&A->col, std::max<size_t>(1, col.size()) * sizeof(int32_t)));
-    NPG_HIP(hipMalloc((void **)&A->val, std::max<size_t>(1, val.size()) * sizeof(double)));
-    NPG_HIP(hipMemcpy(A->rowptr, rowptr.data(), (size_t)(m + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-    if (!col.empty()) {
-        NPG_HIP(hipMemcpy(A->col, col.data(), col.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        NPG_HIP(hipMemcpy(A->val, val.data(), val.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-    A->h_rowptr = std::move(rowptr);
-    int rc = build_tiles(A);
+    int rc = upload_pattern(A.get(), rowptr, col);
     if (rc) return rc;
-    *out = A;
+    NPG_HIP(upload_min(A->val, val));
+    rc = build_tiles(A.get());
+    if (rc) return rc;
+    *out = A.release();
     return NPG_OK;
 }
 
@@ -721,24 +314,24 @@ int csr_refresh_fp32(const npg_csr *Ac) {
     NPG_HIP(hipSetDevice(A->ctx->device));
     const int64_t nz = A->rnnz, nrec = A->nnode() ? A->h_prow[A->nnode()] : 0;
     if (!A->val32) {
-        NPG_HIP(hipMalloc((void **)&A->val32, std::max<size_t>(4, (size_t)nz + 2) * sizeof(float)));
+        NPG_HIP(A->val32.alloc(std::max<size_t>(4, (size_t)nz + 2)));
         A->gen++;
     }
     if (nz)
         hipLaunchKernelGGL(k_to_float32, dim3((unsigned)std::min<int64_t>(4096, (nz + 255) / 256)), dim3(256), 0, A->ctx->stream,
                            A->val, A->val32, nz);
     if (nrec) {
-        if (!A->pkc32) NPG_HIP(hipMalloc((void **)&A->pkc32, (size_t)2 * nrec * sizeof(float)));
+        if (!A->pkc32) NPG_HIP(A->pkc32.alloc((size_t)2 * nrec));
         hipLaunchKernelGGL(k_to_float32, dim3((unsigned)std::min<int64_t>(4096, (2 * nrec + 255) / 256)), dim3(256), 0,
                            A->ctx->stream, A->pkc, A->pkc32, 2 * nrec);
     }
     if (A->ngrec) {
-        if (!A->gval32) NPG_HIP(hipMalloc((void **)&A->gval32, (size_t)3 * A->ngrec * sizeof(float)));
+        if (!A->gval32) NPG_HIP(A->gval32.alloc((size_t)3 * A->ngrec));
         hipLaunchKernelGGL(k_to_float32, dim3((unsigned)std::min<int64_t>(4096, (3 * A->ngrec + 255) / 256)), dim3(256), 0,
                            A->ctx->stream, A->gval, A->gval32, 3 * A->ngrec);
     }
     if (A->ndrec) {
-        if (!A->dval32) NPG_HIP(hipMalloc((void **)&A->dval32, (size_t)3 * A->ndrec * sizeof(float)));
+        if (!A->dval32) NPG_HIP(A->dval32.alloc((size_t)3 * A->ndrec));
         hipLaunchKernelGGL(k_to_float32, dim3((unsigned)std::min<int64_t>(4096, (3 * A->ndrec + 255) / 256)), dim3(256), 0,
                            A->ctx->stream, A->dval, A->dval32, 3 * A->ndrec);
     }
@@ -753,22 +346,22 @@ CsrDev csr_view(const npg_csr *A) {
     v.nnz = A->rnnz;
     v.prow = A->prow;
     v.pcol = A->pcol;
-    v.pkc = reinterpret_cast<const double2 *>(A->pkc);
+    v.pkc = reinterpret_cast<const double2 *>(A->pkc.p);
     v.nfull = A->nfull;
     v.nsurf = A->nsurf;
     v.val32 = A->val32;
-    v.pkc32 = reinterpret_cast<const float2 *>(A->pkc32);
+    v.pkc32 = reinterpret_cast<const float2 *>(A->pkc32.p);
     v.drow = A->drow;
     v.dcol = A->dcol;
-    v.dxy = reinterpret_cast<const double2 *>(A->dval);
+    v.dxy = reinterpret_cast<const double2 *>(A->dval.p);
     v.dz = A->dval ? A->dval + 2 * A->ndrec : nullptr;
-    v.dxy32 = reinterpret_cast<const float2 *>(A->dval32);
+    v.dxy32 = reinterpret_cast<const float2 *>(A->dval32.p);
     v.dz32 = A->dval32 ? A->dval32 + 2 * A->ndrec : nullptr;
     v.grow = A->grow;
     v.gcol = A->gcol;
-    v.gxy = reinterpret_cast<const double2 *>(A->gval);
+    v.gxy = reinterpret_cast<const double2 *>(A->gval.p);
     v.gz = A->gval ? A->gval + 2 * A->ngrec : nullptr;
-    v.gxy32 = reinterpret_cast<const float2 *>(A->gval32);
+    v.gxy32 = reinterpret_cast<const float2 *>(A->gval32.p);
     v.gz32 = A->gval32 ? A->gval32 + 2 * A->ngrec : nullptr;
     v.pk9 = A->pk9;
     v.pk9_32 = A->pk9_32;
@@ -777,22 +370,23 @@ CsrDev csr_view(const npg_csr *A) {
 }
 
 WinDev win_view(const npg_csr *A) {
+    const npg_csr::WindowSet &s = A->win;
     WinDev w;
-    w.widx = A->widx;
-    w.gidx = A->gidx;
-    w.ngrec = A->wgval ? A->nw_grec : A->ngrec;
-    w.gxy = reinterpret_cast<const double2 *>(A->wgval ? A->wgval : A->gval);
-    w.gz = A->wgval ? A->wgval + 2 * A->nw_grec : (A->gval ? A->gval + 2 * A->ngrec : nullptr);
-    w.dz = A->wdz ? A->wdz : (A->dval ? A->dval + 2 * A->ndrec : nullptr);
-    w.wlist = A->wlist;
-    w.vlist = A->vlist;
-    w.pkc2 = reinterpret_cast<const double2 *>(A->pkc2);
-    w.npairs = A->npairs;
-    w.wbk = A->wbk;
-    w.dwidx = A->dwidx;
-    w.dbk = A->dbk;
-    w.dxy2 = reinterpret_cast<const double2 *>(A->dxy2);
-    w.ndpairs = A->ndpairs;
+    w.widx = s.widx;
+    w.gidx = s.gidx;
+    w.ngrec = s.wgval ? s.nw_grec : A->ngrec;
+    w.gxy = reinterpret_cast<const double2 *>(s.wgval ? s.wgval.p : A->gval.p);
+    w.gz = s.wgval ? s.wgval + 2 * s.nw_grec : (A->gval ? A->gval + 2 * A->ngrec : nullptr);
+    w.dz = s.wdz ? s.wdz.p : (A->dval ? A->dval + 2 * A->ndrec : nullptr);
+    w.wlist = s.wlist;
+    w.vlist = s.vlist;
+    w.pkc2 = reinterpret_cast<const double2 *>(s.pkc2.p);
+    w.npairs = s.npairs;
+    w.wbk = s.wbk;
+    w.dwidx = s.dwidx;
+    w.dbk = s.dbk;
+    w.dxy2 = reinterpret_cast<const double2 *>(s.dxy2.p);
+    w.ndpairs = s.ndpairs;
     return w;
 }
 
@@ -804,271 +398,92 @@ using namespace npg;
 // products read instead of the CSR values; only that routine refreshes them.  Any other writer of the CSR values of such a handle
 // would leave the packs stale and products would silently use the old inverse: refused.
 #define NPG_REQUIRE_NO_PACKS(A, who)                                                                                           \
-    NPG_REQUIRE((A)->lb_nblocks == 0, who ": the matrix holds dense line-block packs (npg_csr_line_block_inverse); rewriting its CSR " \
+    NPG_REQUIRE((A)->lb.nblocks == 0, who ": the matrix holds dense line-block packs (npg_csr_line_block_inverse); rewriting its CSR " \
                 "values would leave them stale - build the values through npg_csr_line_block_inverse")
+
+// Build the {K, C} record form of the host matrix H - what A holds or (npg_csr_block_nodes_dofs) a permutation of it - in a
+// candidate handle and swap it into A when it stands: plan (csr_records_core.h), upload, tiles, windowed set, commit.  Anything
+// short of that - not the structure, a node whose rows fit no tile, a failed allocation - destroys the candidate and A was never
+// touched: a matrix that was not converted is the caller's matrix, bit for bit.
+static int convert_to_records(npg_csr *A, const HostCsr &H, const NodeOrder &o, double rtol, int *blocked) {
+    const RecordSwitches sw = record_switches();
+    const RecordPlan P = plan_block_records(H, o, rtol, sw, kTileNnz);
+    if (P.outcome == PlanOutcome::not_the_structure) return NPG_OK;
+    if (P.outcome != PlanOutcome::accepted) {
+        // like a structure that does not hold, no error: *blocked = 0 and npg_last_error says why
+        set_error("build_tiles: the rows of one node do not fit one tile");
+        return NPG_OK;
+    }
+    CsrCandidate C(new npg_csr());
+    C->ctx = A->ctx;
+    C->m = H.m;
+    C->n = H.n;
+    C->nnz = H.rowptr[H.m];           // stays the LOGICAL entry count
+    C->lanes = A->lanes;
+    C->lanes_set = A->lanes_set;
+    C->gn_col = A->gn_col;
+    C->gn_ncomp = A->gn_ncomp;
+    C->nfull = (int32_t)o.nfull;
+    C->nsurf = (int32_t)o.nsurf;
+    C->nrec_real = P.nrec_real;
+    int rc = upload_pattern(C.get(), P.rowptr, P.col);
+    if (rc) return rc;
+    NPG_HIP(upload_min(C->val, P.val));
+    NPG_HIP(upload_min(C->prow, P.prow));
+    NPG_HIP(upload_min(C->pcol, P.pcol));
+    NPG_HIP(upload_min(C->pkc, P.pkc));
+    C->h_prow = P.prow;
+    if (P.colrec) {
+        NPG_HIP(upload_min(C->grow, P.grow));
+        NPG_HIP(upload_min(C->gcol, P.gcol));
+        NPG_HIP(upload_xyz(C->gval, P.gxy, P.gz));
+        C->ngrec = (int64_t)P.gcol.size();
+        C->h_grow = P.grow;
+    }
+    if (P.coupling) {
+        NPG_HIP(upload_min(C->drow, P.drow));
+        NPG_HIP(upload_min(C->dcol, P.dcol));
+        NPG_HIP(upload_xyz(C->dval, P.dxy, P.dz));
+        C->ndrec = (int64_t)P.dcol.size();
+        C->ndrec_real = P.ndrec_real;
+        C->h_drow = P.drow;
+    }
+    rc = build_tiles(C.get());
+    if (rc) return rc == NPG_EINVAL ? NPG_OK : rc;
+    if (sw.window && P.colrec) {
+        std::vector<PlanTile> ordinary;
+        ordinary.reserve(C->h_tiles.size());
+        for (const TileDesc &t : C->h_tiles) ordinary.push_back(PlanTile{t.base, t.pbase, t.r0, t.nrows, t.n, t.npe, 0, 0, 0, 0});
+        const WindowPlan W = plan_window_tiles(P, GhostNodes{A->gn_col, A->gn_ncomp}, A->ctx->num_cu, ordinary, C->ntiles_interior, sw);
+        NPG_REQUIRE(!W.overflow, "build_window_tiles: window lists exceed int32 offsets");
+        if (W.present && (rc = upload_window(C->win, W))) return rc;
+    }
+    // commit: A takes the candidate's contents (a clone thereby detaches from its pattern owner), the candidate takes A's plain
+    // arrays to their release.  Line-block packs are not part of the record form and stay with A.
+    C->lb = std::move(A->lb);
+    C->gen = A->gen + 1;
+    std::swap(*A, *C);
+    *blocked = 1;
+    return NPG_OK;
+}
 
 // Store the velocity block of A_inversion node by node (see spmv_device.h): one record {c, K, C} per coupled node pair.
 // The structure is verified entry by entry on the host (K_xx = K_yy = K_zz, C_xy = -C_yx within rtol * row scale, nothing
 // else in the block); if anything does not match the matrix is left untouched and *blocked = 0.  The same when the record
-// form does not fit its tiles or cannot be allocated: the plain arrays are kept until the new form stands (see the swap below).
+// form does not fit its tiles or cannot be allocated (convert_to_records).
 NPG_API int npg_csr_block_nodes(npg_csr *A, int64_t nfull, int64_t nsurf, double rtol, int *blocked) {
     NPG_REQUIRE(A && blocked && nfull >= 0 && nsurf >= 0, "npg_csr_block_nodes: bad argument");
-    const int64_t nf3 = 3 * nfull, nbr = nf3 + 2 * nsurf, nnode = nfull + nsurf;
-    NPG_REQUIRE(nbr <= A->m && nbr <= A->n, "npg_csr_block_nodes: more block rows than the matrix has");
+    const NodeOrder o{nfull, nsurf};
+    NPG_REQUIRE(o.block_rows() <= A->m && o.block_rows() <= A->n, "npg_csr_block_nodes: more block rows than the matrix has");
     NPG_REQUIRE(A->nnode() == 0 && !A->packed, "npg_csr_block_nodes: matrix is already stored by node blocks (or has a record-form companion)");
     *blocked = 0;
-    if (nnode == 0) return NPG_OK;
+    if (o.nnode() == 0) return NPG_OK;
     NPG_HIP(hipStreamSynchronize(A->ctx->stream));
     std::vector<int32_t> col((size_t)A->nnz);
     std::vector<double> val((size_t)A->nnz);
     NPG_HIP(hipMemcpy(col.data(), A->col, col.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     NPG_HIP(hipMemcpy(val.data(), A->val, val.size() * sizeof(double), hipMemcpyDeviceToHost));
-    const std::vector<int64_t> &rp = A->h_rowptr;
-    std::vector<int64_t> prow((size_t)nnode + 1, 0), nrp((size_t)A->m + 1, 0);
-    std::vector<int32_t> pcol, ncol, gcolv;
-    std::vector<double> pkc, nval, gxy, gzv;
-    std::vector<int64_t> growv((size_t)nnode + 1, 0);
-    pcol.reserve((size_t)A->nnz / 5);
-    pkc.reserve((size_t)A->nnz / 5 * 2);
-    ncol.reserve((size_t)A->nnz / 2);
-    nval.reserve((size_t)A->nnz / 2);
-    // first DoF of column node c / node and component of a block column
-    auto first = [&](int64_t c) { return c < nfull ? 3 * c : nf3 + 2 * (c - nfull); };
-    // windowed tile set (spmv_window.h; NPG_SPMV_WINDOW=0: none): every node's record list is padded to an even count
-    const char *we = getenv("NPG_SPMV_WINDOW");
-    const bool want_win = !(we && atoi(we) == 0);
-    int64_t nrec_real = 0;
-    for (int64_t q = 0; q < nnode; ++q) {
-        const bool qfull = q < nfull;
-        const int64_t rx = first(q), ry = rx + 1, rz = rx + 2;
-        int64_t ia = rp[rx], ib = rp[ry], iz = qfull ? rp[rz] : 0;
-        const int64_t a1 = rp[rx + 1], b1 = rp[ry + 1], z1 = qfull ? rp[rz + 1] : 0;
-        double scale = 0.0;
-        for (int64_t k = ia; k < a1 && col[k] < nbr; ++k) scale = std::max(scale, std::fabs(val[k]));
-        const double tol = rtol * scale;
-        // sorted rows: the block columns come first.  x row: (x_c, K) (y_c, C); y row: (x_c, -C) (y_c, K); z row: (z_c, K)
-        while (ia < a1 && col[ia] < nbr) {
-            if (ia + 1 >= a1 || ib + 1 >= b1) return NPG_OK;
-            const int64_t c0 = col[ia];
-            const int64_t c = c0 < nf3 ? c0 / 3 : nfull + (c0 - nf3) / 2;
-            if (c0 != first(c) || col[ia + 1] != c0 + 1 || col[ib] != c0 || col[ib + 1] != c0 + 1) return NPG_OK;
-            const double K = val[ia], Cc = val[ia + 1];
-            if (std::fabs(val[ib + 1] - K) > tol || std::fabs(val[ib] + Cc) > tol) return NPG_OK;
-            if (qfull && c < nfull) {
-                if (iz >= z1 || col[iz] != c0 + 2 || std::fabs(val[iz] - K) > tol) return NPG_OK;
-                ++iz;
-            }
-            pcol.push_back((int32_t)c);
-            pkc.push_back(K);
-            pkc.push_back(Cc);
-            ia += 2;
-            ib += 2;
-        }
-        // nothing of the block may be left in the y and z rows
-        if (ib < b1 && col[ib] < nbr) return NPG_OK;
-        if (qfull && iz < z1 && col[iz] < nbr) return NPG_OK;
-        nrec_real += (int64_t)pcol.size() - prow[q];
-        if (want_win && (((int64_t)pcol.size() - prow[q]) & 1)) {        // zero record on the node's last column node
-            pcol.push_back(pcol.back());
-            pkc.push_back(0.0);
-            pkc.push_back(0.0);
-        }
-        prow[q + 1] = (int64_t)pcol.size();
-        const int64_t lo[3] = {ia, ib, iz}, hi[3] = {a1, b1, z1};
-        // what is left of the node's rows (columns outside the block): as column records {m, a_x, a_y, a_z} - a three-way
-        // merge of the sorted rows - and, in case they are not used, as plain CSR entries
-        {
-            int64_t it[3] = {lo[0], lo[1], qfull ? lo[2] : 0};
-            const int nc = qfull ? 3 : 2;
-            for (;;) {
-                int64_t mcol = INT64_MAX;
-                for (int a = 0; a < nc; ++a)
-                    if (it[a] < hi[a]) mcol = std::min<int64_t>(mcol, col[it[a]]);
-                if (mcol == INT64_MAX) break;
-                double a3[3] = {0.0, 0.0, 0.0};
-                for (int a = 0; a < nc; ++a)
-                    if (it[a] < hi[a] && col[it[a]] == mcol) a3[a] = val[it[a]++];
-                gcolv.push_back((int32_t)mcol);
-                gxy.push_back(a3[0]);
-                gxy.push_back(a3[1]);
-                gzv.push_back(a3[2]);
-            }
-            growv[q + 1] = (int64_t)gcolv.size();
-        }
-        for (int a = 0; a < (qfull ? 3 : 2); ++a) {
-            for (int64_t k = lo[a]; k < hi[a]; ++k) {
-                ncol.push_back(col[k]);
-                nval.push_back(val[k]);
-            }
-            nrp[rx + a + 1] = (int64_t)ncol.size();
-        }
-    }
-    // column records pay when they replace more than 28 / 12 entries each (NPG_SPMV_COLUMN_RECORDS=0: never)
-    const char *ge = getenv("NPG_SPMV_COLUMN_RECORDS");
-    const bool colrec = !(ge && atoi(ge) == 0) && !gcolv.empty() && 28 * gcolv.size() <= 12 * ncol.size();
-    if (colrec) {           // the block rows keep no CSR entries
-        ncol.clear();
-        nval.clear();
-        for (int64_t r = 0; r < nbr; ++r) nrp[r + 1] = 0;
-    }
-    // rows behind the block rows: their entries in the block columns become coupling records {c, d_x, d_y, d_z} (spmv_device.h)
-    // unless NPG_SPMV_COUPLING=0 or a row would not fit a tile that way
-    const char *ce = getenv("NPG_SPMV_COUPLING");
-    bool coupling = !(ce && atoi(ce) == 0) && A->m > nbr;
-    std::vector<int64_t> drow;
-    std::vector<int32_t> dcol;
-    std::vector<double> dxy, dz;
-    int64_t ndrec_real = 0;
-    if (coupling) {
-        drow.assign((size_t)(A->m - nbr) + 1, 0);
-        for (int64_t r = nbr; r < A->m && coupling; ++r) {
-            int64_t k = rp[r], nrec = 0;
-            while (k < rp[r + 1] && col[k] < nbr) {
-                const int64_t c0 = col[k];
-                const int64_t c = c0 < nf3 ? c0 / 3 : nfull + (c0 - nf3) / 2, f = first(c);
-                double d[3] = {0.0, 0.0, 0.0};
-                for (; k < rp[r + 1] && col[k] < nbr && col[k] - f < (c < nfull ? 3 : 2) && col[k] >= f; ++k) d[col[k] - f] = val[k];
-                dcol.push_back((int32_t)c);
-                dxy.push_back(d[0]);
-                dxy.push_back(d[1]);
-                dz.push_back(d[2]);
-                ++nrec;
-            }
-            ndrec_real += nrec;
-            if (want_win && (nrec & 1)) {          // zero record on the row's last column node (windowed tiles take records in pairs)
-                dcol.push_back(dcol.back());
-                dxy.push_back(0.0);
-                dxy.push_back(0.0);
-                dz.push_back(0.0);
-                ++nrec;
-            }
-            drow[r - nbr + 1] = (int64_t)dcol.size();
-            if (nrec + (rp[r + 1] - k) > kTileNnz) coupling = false;
-        }
-    }
-    for (int64_t r = nbr; r < A->m; ++r) {
-        for (int64_t k = rp[r]; k < rp[r + 1]; ++k) {
-            if (coupling && col[k] < nbr) continue;
-            ncol.push_back(col[k]);
-            nval.push_back(val[k]);
-        }
-        nrp[r + 1] = (int64_t)ncol.size();
-    }
-    // Swap the device arrays.  The plain arrays are set aside, not freed, until the record form and its tiles stand: the fit
-    // checks of build_tiles / build_window_tiles need the new form in the handle, and when one of them (or an allocation) fails
-    // the handle gets its plain arrays back - a matrix that was not converted is the caller's matrix, bit for bit.
-    // (A clone shares rowptr / col / tiles with its pattern owner and detaches from them.)
-    int64_t *const old_rowptr = A->rowptr;
-    int32_t *const old_col = A->col;
-    double *const old_val = A->val;
-    TileDesc *const old_tile_ptr = A->tile_ptr;
-    const bool old_owns = A->owns_pattern;
-    const int32_t old_ntiles = A->ntiles, old_interior = A->ntiles_interior, old_lanes = A->lanes, old_lanes_default = A->lanes_default;
-    const int64_t old_rnnz = A->rnnz;
-    std::vector<int64_t> old_h_rowptr = A->h_rowptr;
-    std::vector<TileDesc> old_h_tiles = A->h_tiles;
-    A->col = nullptr;
-    A->val = nullptr;
-    A->rowptr = nullptr;
-    A->tile_ptr = nullptr;
-    A->owns_pattern = true;
-    bool no_fit = false;        // build_tiles: the rows of one node do not fit one tile
-    auto convert = [&]() -> int {
-        NPG_HIP(hipMalloc((void **)&A->rowptr, nrp.size() * sizeof(int64_t)));
-        NPG_HIP(hipMalloc((void **)&A->col, std::max<size_t>(1, ncol.size()) * sizeof(int32_t)));
-        NPG_HIP(hipMalloc((void **)&A->val, std::max<size_t>(1, nval.size()) * sizeof(double)));
-        NPG_HIP(hipMalloc((void **)&A->prow, prow.size() * sizeof(int64_t)));
-        NPG_HIP(hipMalloc((void **)&A->pcol, std::max<size_t>(1, pcol.size()) * sizeof(int32_t)));
-        NPG_HIP(hipMalloc((void **)&A->pkc, std::max<size_t>(2, pkc.size()) * sizeof(double)));
-        NPG_HIP(hipMemcpy(A->rowptr, nrp.data(), nrp.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        if (!ncol.empty()) {
-            NPG_HIP(hipMemcpy(A->col, ncol.data(), ncol.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            NPG_HIP(hipMemcpy(A->val, nval.data(), nval.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
-        NPG_HIP(hipMemcpy(A->prow, prow.data(), prow.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        if (!pcol.empty()) {
-            NPG_HIP(hipMemcpy(A->pcol, pcol.data(), pcol.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            NPG_HIP(hipMemcpy(A->pkc, pkc.data(), pkc.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
-        if (colrec) {
-            const size_t ng = gcolv.size();
-            NPG_HIP(hipMalloc((void **)&A->grow, growv.size() * sizeof(int64_t)));
-            NPG_HIP(hipMalloc((void **)&A->gcol, ng * sizeof(int32_t)));
-            NPG_HIP(hipMalloc((void **)&A->gval, 3 * ng * sizeof(double)));
-            NPG_HIP(hipMemcpy(A->grow, growv.data(), growv.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-            NPG_HIP(hipMemcpy(A->gcol, gcolv.data(), ng * sizeof(int32_t), hipMemcpyHostToDevice));
-            NPG_HIP(hipMemcpy(A->gval, gxy.data(), 2 * ng * sizeof(double), hipMemcpyHostToDevice));
-            NPG_HIP(hipMemcpy(A->gval + 2 * ng, gzv.data(), ng * sizeof(double), hipMemcpyHostToDevice));
-            A->ngrec = (int64_t)ng;
-            A->h_grow = std::move(growv);
-        }
-        if (coupling && !dcol.empty()) {
-            const size_t nd = dcol.size();
-            NPG_HIP(hipMalloc((void **)&A->drow, drow.size() * sizeof(int64_t)));
-            NPG_HIP(hipMalloc((void **)&A->dcol, nd * sizeof(int32_t)));
-            NPG_HIP(hipMalloc((void **)&A->dval, 3 * nd * sizeof(double)));
-            NPG_HIP(hipMemcpy(A->drow, drow.data(), drow.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-            NPG_HIP(hipMemcpy(A->dcol, dcol.data(), nd * sizeof(int32_t), hipMemcpyHostToDevice));
-            NPG_HIP(hipMemcpy(A->dval, dxy.data(), 2 * nd * sizeof(double), hipMemcpyHostToDevice));
-            NPG_HIP(hipMemcpy(A->dval + 2 * nd, dz.data(), nd * sizeof(double), hipMemcpyHostToDevice));
-            A->ndrec = (int64_t)nd;
-            A->ndrec_real = ndrec_real;
-            A->h_drow = std::move(drow);
-        }
-        A->h_rowptr = std::move(nrp);
-        A->h_prow = std::move(prow);
-        A->rnnz = (int64_t)ncol.size();
-        A->nfull = (int32_t)nfull;
-        A->nsurf = (int32_t)nsurf;
-        A->nrec_real = nrec_real;
-        int rc = build_tiles(A);
-        if (rc) {
-            no_fit = rc == NPG_EINVAL;
-            return rc;
-        }
-        if (want_win && colrec) return build_window_tiles(A, pcol, gcolv, dcol, pkc, dxy, gxy, gzv, dz, ncol, nval);
-        return NPG_OK;
-    };
-    const int rc = convert();
-    if (rc != NPG_OK) {
-        // back to the plain matrix: drop whatever of the record form exists, put the arrays that were set aside back
-        free_window_tiles(A);
-        for (void *p : {(void *)A->rowptr, (void *)A->col, (void *)A->val, (void *)A->tile_ptr, (void *)A->prow, (void *)A->pcol, (void *)A->pkc,
-                        (void *)A->grow, (void *)A->gcol, (void *)A->gval, (void *)A->drow, (void *)A->dcol, (void *)A->dval})
-            if (p) hipFree(p);
-        A->prow = A->grow = A->drow = nullptr;
-        A->pcol = A->gcol = A->dcol = nullptr;
-        A->pkc = A->gval = A->dval = nullptr;
-        A->ngrec = A->ndrec = A->ndrec_real = A->nrec_real = 0;
-        A->h_prow.clear();
-        A->h_grow.clear();
-        A->h_drow.clear();
-        A->nfull = A->nsurf = 0;
-        A->rowptr = old_rowptr;
-        A->col = old_col;
-        A->val = old_val;
-        A->tile_ptr = old_tile_ptr;
-        A->owns_pattern = old_owns;
-        A->ntiles = old_ntiles;
-        A->ntiles_interior = old_interior;
-        A->lanes = old_lanes;
-        A->lanes_default = old_lanes_default;
-        A->rnnz = old_rnnz;
-        A->h_rowptr = std::move(old_h_rowptr);
-        A->h_tiles = std::move(old_h_tiles);
-        A->gen++;
-        // the rows of one node do not fit one tile: like a structure that does not hold, no error - *blocked = 0 and
-        // npg_last_error says so; anything else (out of memory, window lists beyond int32 offsets) is returned
-        return no_fit ? NPG_OK : rc;
-    }
-    if (old_owns) {
-        hipFree(old_col);
-        hipFree(old_rowptr);
-        if (old_tile_ptr) hipFree(old_tile_ptr);
-    }
-    hipFree(old_val);
-    *blocked = 1;
-    return NPG_OK;
+    return convert_to_records(A, HostCsr{A->m, A->n, A->h_rowptr.data(), col.data(), val.data()}, o, rtol, blocked);
 }
 
 namespace npg {
@@ -1079,9 +494,8 @@ __global__ void k_gather_map(double *__restrict__ dst, const double *__restrict_
     }
 }
 
-int csr_repack(const npg_csr *A) {
-    if (!A || !A->packed) return NPG_OK;
-    npg_csr *P = A->packed;
+// the values of the record-form companion P from the plain matrix A's
+static int repack(const npg_csr *A, npg_csr *P) {
     auto go = [&](double *dst, const int64_t *map, int64_t n) {
         if (n > 0)
             hipLaunchKernelGGL(k_gather_map, dim3((unsigned)std::min<int64_t>(4096, (n + 255) / 256)), dim3(256), 0, A->ctx->stream, dst,
@@ -1094,6 +508,7 @@ int csr_repack(const npg_csr *A) {
     NPG_HIP(hipGetLastError());
     return NPG_OK;
 }
+int csr_repack(const npg_csr *A) { return A && A->packed ? repack(A, A->packed) : NPG_OK; }
 }  // namespace npg
 
 // Record-form companion of a PLAIN matrix whose velocity block has no {K, C} structure (function-valued viscosity: the
@@ -1106,157 +521,52 @@ int csr_repack(const npg_csr *A) {
 // *packed = 0 and nothing changed if the rows of some node would not fit a tile.
 NPG_API int npg_csr_pack_nodes(npg_csr *A, int64_t nfull, int64_t nsurf, int *packed) {
     NPG_REQUIRE(A && packed && nfull >= 0 && nsurf >= 0, "npg_csr_pack_nodes: bad argument");
-    const int64_t nf3 = 3 * nfull, nbr = nf3 + 2 * nsurf, nnode = nfull + nsurf;
-    NPG_REQUIRE(nbr <= A->m && nbr <= A->n, "npg_csr_pack_nodes: more block rows than the matrix has");
+    const NodeOrder o{nfull, nsurf};
+    NPG_REQUIRE(o.block_rows() <= A->m && o.block_rows() <= A->n, "npg_csr_pack_nodes: more block rows than the matrix has");
     NPG_REQUIRE(A->nnode() == 0 && !A->packed, "npg_csr_pack_nodes: the matrix is in record form already");
     *packed = 0;
-    if (nnode == 0) return NPG_OK;
+    if (o.nnode() == 0) return NPG_OK;
     NPG_HIP(hipSetDevice(A->ctx->device));
     NPG_HIP(hipStreamSynchronize(A->ctx->stream));
     std::vector<int32_t> col((size_t)A->nnz);
     NPG_HIP(hipMemcpy(col.data(), A->col, col.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    const std::vector<int64_t> &rp = A->h_rowptr;
-    auto first = [&](int64_t c) { return c < nfull ? 3 * c : nf3 + 2 * (c - nfull); };
-    auto node_of = [&](int64_t c0) { return c0 < nf3 ? c0 / 3 : nfull + (c0 - nf3) / 2; };
-    std::vector<int64_t> prow((size_t)nnode + 1, 0), grow((size_t)nnode + 1, 0), nrp((size_t)A->m + 1, 0);
-    std::vector<int32_t> pcol, gcol, dcol, ncol;
-    std::vector<int64_t> m9, mg3, md3, mrem;          // source positions, record-major (re-laid below)
-    for (int64_t q = 0; q < nnode; ++q) {
-        const int nc = q < nfull ? 3 : 2;
-        const int64_t rx = first(q);
-        int64_t it[3] = {0, 0, 0}, en[3] = {0, 0, 0};
-        for (int a = 0; a < nc; ++a) {
-            it[a] = rp[rx + a];
-            en[a] = rp[rx + a + 1];
-        }
-        for (;;) {                                    // block columns, node by node (rows are sorted: block columns come first)
-            int64_t cn = INT64_MAX;
-            for (int a = 0; a < nc; ++a)
-                if (it[a] < en[a] && col[it[a]] < nbr) cn = std::min(cn, node_of(col[it[a]]));
-            if (cn == INT64_MAX) break;
-            int64_t src[9] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};
-            const int64_t f = first(cn);
-            for (int a = 0; a < nc; ++a)
-                while (it[a] < en[a] && col[it[a]] < nbr && node_of(col[it[a]]) == cn) {
-                    src[3 * a + (int)(col[it[a]] - f)] = it[a];
-                    ++it[a];
-                }
-            pcol.push_back((int32_t)cn);
-            m9.insert(m9.end(), src, src + 9);
-        }
-        prow[q + 1] = (int64_t)pcol.size();
-        for (;;) {                                    // what is left: columns outside the block, one record per column
-            int64_t mc = INT64_MAX;
-            for (int a = 0; a < nc; ++a)
-                if (it[a] < en[a]) mc = std::min<int64_t>(mc, col[it[a]]);
-            if (mc == INT64_MAX) break;
-            int64_t src[3] = {-1, -1, -1};
-            for (int a = 0; a < nc; ++a)
-                if (it[a] < en[a] && col[it[a]] == mc) src[a] = it[a]++;
-            gcol.push_back((int32_t)mc);
-            mg3.insert(mg3.end(), src, src + 3);
-        }
-        grow[q + 1] = (int64_t)gcol.size();
-    }
-    std::vector<int64_t> drow((size_t)(A->m - nbr) + 1, 0);
-    for (int64_t r = nbr; r < A->m; ++r) {
-        int64_t k = rp[r], nrec = 0;
-        while (k < rp[r + 1] && col[k] < nbr) {
-            const int64_t cn = node_of(col[k]), f = first(cn);
-            int64_t src[3] = {-1, -1, -1};
-            for (; k < rp[r + 1] && col[k] < nbr && node_of(col[k]) == cn; ++k) src[col[k] - f] = k;
-            dcol.push_back((int32_t)cn);
-            md3.insert(md3.end(), src, src + 3);
-            ++nrec;
-        }
-        drow[r - nbr + 1] = (int64_t)dcol.size();
-        for (; k < rp[r + 1]; ++k) {
-            ncol.push_back(col[k]);
-            mrem.push_back(k);
-        }
-        nrp[r + 1] = (int64_t)ncol.size();
-        if (nrec + (nrp[r + 1] - nrp[r]) > kTileNnz) return NPG_OK;          // (a row that would not fit a tile: stay plain)
-    }
-    for (int64_t q = 0; q < nnode; ++q)
-        if ((q < nfull ? 3 : 2) * ((prow[q + 1] - prow[q]) + (grow[q + 1] - grow[q])) > kTileNnz) return NPG_OK;
+    const PackPlan F = plan_full_records(HostCsr{A->m, A->n, A->h_rowptr.data(), col.data(), nullptr}, o, kTileNnz);
+    if (F.outcome != PlanOutcome::accepted) return NPG_OK;          // (a row or a node that would not fit a tile: stay plain)
     // the companion object
-    npg_csr *P = new npg_csr();
+    CsrCandidate P(new npg_csr());
     P->ctx = A->ctx;
     P->m = A->m;
     P->n = A->n;
     P->nnz = A->nnz;
-    P->rnnz = (int64_t)ncol.size();
     P->nfull = (int32_t)nfull;
     P->nsurf = (int32_t)nsurf;
-    const int64_t n9 = (int64_t)pcol.size(), ng = (int64_t)gcol.size(), nd = (int64_t)dcol.size();
-    P->npk9 = n9;
-    P->ngrec = ng;
-    P->ndrec = nd;
-    std::vector<int64_t> map9((size_t)9 * n9), mapg((size_t)3 * ng), mapd((size_t)3 * nd);
-    for (int64_t e = 0; e < n9; ++e) {           // (a_2k, a_2k+1) pairs as four 16-byte streams, a_8 as one 8-byte stream (spmv_device.h)
-        for (int s9 = 0; s9 < 8; ++s9) map9[(size_t)(s9 & ~1) * n9 + 2 * e + (s9 & 1)] = m9[(size_t)9 * e + s9];
-        map9[(size_t)8 * n9 + e] = m9[(size_t)9 * e + 8];
+    P->npk9 = (int64_t)F.pcol.size();
+    P->ngrec = (int64_t)F.gcol.size();
+    P->ndrec = (int64_t)F.dcol.size();
+    int rc = upload_pattern(P.get(), F.rowptr, F.col);
+    if (rc) return rc;
+    NPG_HIP(upload_min(P->prow, F.prow));
+    NPG_HIP(upload_min(P->pcol, F.pcol));
+    NPG_HIP(upload_min(P->grow, F.grow));
+    NPG_HIP(upload_min(P->gcol, F.gcol));
+    if (P->ndrec) NPG_HIP(upload_min(P->drow, F.drow));          // (no coupling records: the tile code keys on drow)
+    NPG_HIP(upload_min(P->dcol, F.dcol));
+    NPG_HIP(upload_min(P->map9, F.map9));
+    NPG_HIP(upload_min(P->mapg, F.mapg));
+    NPG_HIP(upload_min(P->mapd, F.mapd));
+    NPG_HIP(upload_min(P->maprem, F.maprem));
+    if (P->val.alloc(std::max<size_t>(2, F.col.size())) != hipSuccess || P->pk9.alloc(std::max<size_t>(2, F.map9.size())) != hipSuccess ||
+        P->gval.alloc(std::max<size_t>(2, F.mapg.size())) != hipSuccess || P->dval.alloc(std::max<size_t>(2, F.mapd.size())) != hipSuccess) {
+        set_error("npg_csr_pack_nodes: out of device memory");
+        return NPG_ENOMEM;
     }
-    for (int64_t e = 0; e < ng; ++e) {               // [2 ng] (a_x, a_y) pairs, then [ng] a_z
-        mapg[2 * e] = mg3[3 * e];
-        mapg[2 * e + 1] = mg3[3 * e + 1];
-        mapg[2 * ng + e] = mg3[3 * e + 2];
-    }
-    for (int64_t e = 0; e < nd; ++e) {
-        mapd[2 * e] = md3[3 * e];
-        mapd[2 * e + 1] = md3[3 * e + 1];
-        mapd[2 * nd + e] = md3[3 * e + 2];
-    }
-    auto up = [&](void **dst, const void *src, size_t bytes) -> int {
-        NPG_HIP(hipMalloc(dst, std::max<size_t>(bytes, 16)));
-        if (bytes) NPG_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-        return NPG_OK;
-    };
-    int rc = NPG_OK;
-    auto chk = [&](int r) { if (rc == NPG_OK) rc = r; };
-    chk(up((void **)&P->rowptr, nrp.data(), nrp.size() * 8));
-    chk(up((void **)&P->col, ncol.data(), ncol.size() * 4));
-    chk(up((void **)&P->prow, prow.data(), prow.size() * 8));
-    chk(up((void **)&P->pcol, pcol.data(), pcol.size() * 4));
-    chk(up((void **)&P->grow, grow.data(), grow.size() * 8));
-    chk(up((void **)&P->gcol, gcol.data(), gcol.size() * 4));
-    chk(up((void **)&P->drow, drow.data(), drow.size() * 8));
-    chk(up((void **)&P->dcol, dcol.data(), dcol.size() * 4));
-    chk(up((void **)&P->map9, map9.data(), map9.size() * 8));
-    chk(up((void **)&P->mapg, mapg.data(), mapg.size() * 8));
-    chk(up((void **)&P->mapd, mapd.data(), mapd.size() * 8));
-    chk(up((void **)&P->maprem, mrem.data(), mrem.size() * 8));
-    if (rc == NPG_OK) {
-        hipError_t e1 = hipMalloc((void **)&P->val, std::max<size_t>(16, ncol.size() * 8));
-        hipError_t e2 = hipMalloc((void **)&P->pk9, std::max<size_t>(16, (size_t)9 * n9 * 8));
-        hipError_t e3 = hipMalloc((void **)&P->gval, std::max<size_t>(16, (size_t)3 * ng * 8));
-        hipError_t e4 = hipMalloc((void **)&P->dval, std::max<size_t>(16, (size_t)3 * nd * 8));
-        if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) {
-            set_error("npg_csr_pack_nodes: out of device memory");
-            rc = NPG_ENOMEM;
-        }
-    }
-    if (rc != NPG_OK) {
-        npg_csr_destroy(P);
-        return rc;
-    }
-    if (nd == 0) {                 // (no coupling records: the tile code keys on drow)
-        hipFree(P->drow);
-        P->drow = nullptr;
-    }
-    P->h_rowptr = std::move(nrp);
-    P->h_prow = std::move(prow);
-    P->h_grow = std::move(grow);
-    P->h_drow = std::move(drow);
-    P->owns_pattern = true;
-    A->packed = P;
-    rc = csr_repack(A);
-    if (rc == NPG_OK) rc = build_tiles(P);
-    if (rc != NPG_OK) {
-        A->packed = nullptr;
-        npg_csr_destroy(P);
-        return rc;
-    }
+    P->h_prow = F.prow;
+    P->h_grow = F.grow;
+    P->h_drow = F.drow;
+    rc = repack(A, P.get());
+    if (rc == NPG_OK) rc = build_tiles(P.get());
+    if (rc != NPG_OK) return rc;
+    A->packed = P.release();
     *packed = 1;
     return NPG_OK;
 }
@@ -1344,19 +654,12 @@ NPG_API int npg_csr_block_nodes_dofs(npg_csr *A, const int64_t *node_of_dof, con
     NPG_HIP(hipSetDevice(A->ctx->device));
     NPG_HIP(hipStreamSynchronize(A->ctx->stream));
     // (what the handle will carry is allocated first: a failure here leaves the caller's matrix as it was)
-    int32_t *d_perm = nullptr;
-    double *d_vec[3] = {nullptr, nullptr, nullptr};
-    auto release = [&]() {
-        if (d_perm) hipFree(d_perm);
-        for (double *q : d_vec)
-            if (q) hipFree(q);
-    };
+    DevBuf<int32_t> d_perm;
+    DevBuf<double> d_vec[3];
     {
-        hipError_t e0 = hipMalloc((void **)&d_perm, (size_t)N * sizeof(int32_t));
-        for (int k = 0; k < 3 && e0 == hipSuccess; ++k) e0 = hipMalloc((void **)&d_vec[k], (size_t)N * sizeof(double));
-        if (e0 == hipSuccess) e0 = hipMemcpy(d_perm, perm.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice);
+        hipError_t e0 = d_perm.upload(perm);
+        for (int k = 0; k < 3 && e0 == hipSuccess; ++k) e0 = d_vec[k].alloc((size_t)N);
         if (e0 != hipSuccess) {
-            release();
             set_error("npg_csr_block_nodes_dofs: out of device memory");
             return NPG_ENOMEM;
         }
@@ -1365,7 +668,7 @@ NPG_API int npg_csr_block_nodes_dofs(npg_csr *A, const int64_t *node_of_dof, con
     std::vector<double> val((size_t)A->nnz), nval((size_t)A->nnz);
     NPG_HIP(hipMemcpy(col.data(), A->col, col.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     NPG_HIP(hipMemcpy(val.data(), A->val, val.size() * sizeof(double), hipMemcpyDeviceToHost));
-    const std::vector<int64_t> orp = A->h_rowptr;
+    const std::vector<int64_t> &orp = A->h_rowptr;
     std::vector<int64_t> nrp((size_t)N + 1, 0);
     std::vector<std::pair<int32_t, double>> row;
     for (int64_t i = 0; i < N; ++i) {
@@ -1384,32 +687,11 @@ NPG_API int npg_csr_block_nodes_dofs(npg_csr *A, const int64_t *node_of_dof, con
         }
         nrp[i + 1] = o;
     }
-    auto put = [&](const std::vector<int64_t> &rp, const std::vector<int32_t> &c, const std::vector<double> &v) -> int {
-        NPG_HIP(hipMemcpy(A->rowptr, rp.data(), rp.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        if (!c.empty()) {
-            NPG_HIP(hipMemcpy(A->col, c.data(), c.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            NPG_HIP(hipMemcpy(A->val, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
-        A->h_rowptr = rp;
-        return build_tiles(A);
-    };
-    const int64_t nnz_in = A->nnz;
-    A->nnz = nrp[(size_t)N];                      // (<= nnz_in: the arrays keep their size)
-    ncol.resize((size_t)A->nnz);
-    nval.resize((size_t)A->nnz);
-    int rc = put(nrp, ncol, nval);
-    if (rc == NPG_OK) rc = npg_csr_block_nodes(A, nfull, nsurf, rtol, blocked);
-    if (rc != NPG_OK || !*blocked) {              // not the structure (or an error): the caller's matrix again, untouched
-        if (A->nnode() == 0) {
-            A->nnz = nnz_in;
-            const int rc2 = put(orp, col, val);
-            if (rc == NPG_OK) rc = rc2;
-        }
-        release();
-        return rc;
-    }
-    A->uperm = d_perm;
-    for (int k = 0; k < 3; ++k) A->uvec[k] = d_vec[k];
+    // the record form is planned from the permuted host matrix; the caller's matrix stays on the device as it is unless that stands
+    const int rc = convert_to_records(A, HostCsr{N, N, nrp.data(), ncol.data(), nval.data()}, NodeOrder{nfull, nsurf}, rtol, blocked);
+    if (rc != NPG_OK || !*blocked) return rc;
+    A->uperm = std::move(d_perm);
+    for (int k = 0; k < 3; ++k) A->uvec[k] = std::move(d_vec[k]);
     return NPG_OK;
 }
 
@@ -1495,31 +777,7 @@ NPG_API int npg_csr_destroy(npg_csr *A) {
         if (A->col) hipFree(A->col);
         if (A->tile_ptr) hipFree(A->tile_ptr);
     }
-    if (A->val) hipFree(A->val);
-    if (A->prow) hipFree(A->prow);
-    if (A->pcol) hipFree(A->pcol);
-    if (A->pkc) hipFree(A->pkc);
-    if (A->val32) hipFree(A->val32);
-    if (A->pkc32) hipFree(A->pkc32);
     if (A->packed) npg_csr_destroy(A->packed);
-    if (A->pk9) hipFree(A->pk9);
-    if (A->pk9_32) hipFree(A->pk9_32);
-    for (int64_t *mp : {A->map9, A->mapd, A->mapg, A->maprem})
-        if (mp) hipFree(mp);
-    if (A->grow) hipFree(A->grow);
-    if (A->gcol) hipFree(A->gcol);
-    if (A->gval) hipFree(A->gval);
-    if (A->gval32) hipFree(A->gval32);
-    if (A->drow) hipFree(A->drow);
-    if (A->dcol) hipFree(A->dcol);
-    if (A->dval) hipFree(A->dval);
-    if (A->dval32) hipFree(A->dval32);
-    free_window_tiles(A);
-    for (void *q : {(void *)A->lb_ptr, (void *)A->lb_dofs, (void *)A->lb_off, (void *)A->lb_val, (void *)A->lb_val32, (void *)A->lb_val16, (void *)A->lb_scale})
-        if (q) hipFree(q);
-    if (A->uperm) hipFree(A->uperm);
-    for (double *p : A->uvec)
-        if (p) hipFree(p);
     delete A;
     return NPG_OK;
 }
@@ -1556,24 +814,24 @@ NPG_API int npg_csr_window_info(const npg_csr *Ap, int64_t *tiles, int64_t *bloc
     NPG_REQUIRE(Ap, "npg_csr_window_info: NULL matrix");
     const npg_csr *A = spmv_form(Ap);
     int64_t nblk = 0;
-    if (A->wtile_ptr) {
+    if (A->win.wtile_ptr) {
         // (block tiles are the descriptors with a window: count them from the lists' owner - every block tile has nw > 0)
         const int64_t nbr = A->block_rows();
-        int64_t behind = A->nwrow_tiles;
+        int64_t behind = A->win.nwrow_tiles;
         if (!behind)
             for (const npg::TileDesc &t : A->h_tiles) behind += t.r0 >= nbr;
-        nblk = A->nwtiles - behind;
+        nblk = A->win.nwtiles - behind;
     }
-    if (tiles) *tiles = A->nwtiles;
+    if (tiles) *tiles = A->win.nwtiles;
     if (block_tiles) *block_tiles = nblk;
-    if (distinct) *distinct = A->nwlist + A->nvlist;
+    if (distinct) *distinct = A->win.nwlist + A->win.nvlist;
     if (matrix_bytes) {
         int64_t b = 0;
-        if (A->wtile_ptr) {
-            const int64_t nnode = A->nnode(), nrec = A->nw_rec ? A->nw_rec : A->h_prow[nnode], ngr = A->nw_rec ? A->nw_grec : A->ngrec;
-            b = 48 * (int64_t)A->nwtiles + 18 * nrec + 26 * ngr + 4 * (A->nwlist + A->nvlist) + 8 * nnode +
+        if (A->win.wtile_ptr) {
+            const int64_t nnode = A->nnode(), nrec = A->win.nw_rec ? A->win.nw_rec : A->h_prow[nnode], ngr = A->win.nw_rec ? A->win.nw_grec : A->ngrec;
+            b = 48 * (int64_t)A->win.nwtiles + 18 * nrec + 26 * ngr + 4 * (A->win.nwlist + A->win.nvlist) + 8 * nnode +
                 12 * A->rnnz + 8 * (A->m - A->block_rows() + 1);
-            if (A->drow) b += A->nwrow_tiles ? 4 * (A->m - A->block_rows()) + 26 * (A->nw_drec ? A->nw_drec : A->ndrec) : 8 * (A->m - A->block_rows() + 1) + 28 * A->ndrec;
+            if (A->drow) b += A->win.nwrow_tiles ? 4 * (A->m - A->block_rows()) + 26 * (A->win.nw_drec ? A->win.nw_drec : A->ndrec) : 8 * (A->m - A->block_rows() + 1) + 28 * A->ndrec;
         }
         *matrix_bytes = b;
     }
@@ -1632,7 +890,7 @@ NPG_API int npg_csr_clone(const npg_csr *A, npg_csr **out) {
     B->lanes = A->lanes;
     B->owns_pattern = false;
     B->h_rowptr = A->h_rowptr;
-    NPG_HIP(hipMalloc((void **)&B->val, std::max<size_t>(1, (size_t)A->nnz) * sizeof(double)));
+    NPG_HIP(B->val.alloc(std::max<size_t>(1, (size_t)A->nnz)));
     NPG_HIP(hipMemcpyAsync(B->val, A->val, (size_t)A->nnz * sizeof(double), hipMemcpyDeviceToDevice, A->ctx->stream));
     *out = B;
     return NPG_OK;
@@ -2081,39 +1339,29 @@ NPG_API int npg_csr_line_block_inverse(npg_csr *Dinv, const npg_csr *A, const np
     const size_t lds = (size_t)nmax * nmax * sizeof(double) + (size_t)nmax * sizeof(int32_t) + 8;
     NPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_line_block_inverse), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     npg_ctx *ctx = A->ctx;
-    if (Dinv->lb_nblocks != nb || !Dinv->lb_val) {         // first call: the dense pack and the handle's own copy of the blocks
-        for (void *q : {(void *)Dinv->lb_ptr, (void *)Dinv->lb_dofs, (void *)Dinv->lb_off, (void *)Dinv->lb_val, (void *)Dinv->lb_val32,
-                        (void *)Dinv->lb_val16, (void *)Dinv->lb_scale})
-            if (q) hipFree(q);
-        Dinv->lb_ptr = Dinv->lb_dofs = Dinv->lb_off = nullptr;
-        Dinv->lb_val = nullptr;
-        Dinv->lb_val32 = nullptr;
-        Dinv->lb_val16 = nullptr;
-        Dinv->lb_scale = nullptr;
-        Dinv->lb_nblocks = 0;
+    if (Dinv->lb.nblocks != nb || !Dinv->lb.val) {         // first call: the dense pack and the handle's own copy of the blocks
         std::vector<int64_t> off((size_t)nb + 1, 0);
         for (int64_t b = 0; b < nb; ++b) {
             const int64_t n = bp[(size_t)b + 1] - bp[(size_t)b];
             off[(size_t)b + 1] = off[(size_t)b] + n * n;
         }
-        NPG_HIP(hipMalloc((void **)&Dinv->lb_ptr, bp.size() * sizeof(int64_t)));
-        NPG_HIP(hipMalloc((void **)&Dinv->lb_dofs, dofs.size() * sizeof(int64_t)));
-        NPG_HIP(hipMalloc((void **)&Dinv->lb_off, off.size() * sizeof(int64_t)));
-        NPG_HIP(hipMalloc((void **)&Dinv->lb_val, (size_t)total * sizeof(double)));
-        NPG_HIP(hipMalloc((void **)&Dinv->lb_val32, (size_t)total * sizeof(float)));
-        NPG_HIP(hipMalloc((void **)&Dinv->lb_val16, (size_t)total * sizeof(_Float16)));
-        NPG_HIP(hipMalloc((void **)&Dinv->lb_scale, (size_t)nu * sizeof(double)));
-        NPG_HIP(hipMemcpy(Dinv->lb_ptr, bp.data(), bp.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        NPG_HIP(hipMemcpy(Dinv->lb_dofs, dofs.data(), dofs.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        NPG_HIP(hipMemcpy(Dinv->lb_off, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        Dinv->lb_nblocks = nb;
+        npg_csr::LineBlocks lb;             // (swapped in whole: a failed allocation leaves no half-made pack)
+        NPG_HIP(lb.ptr.upload(bp));
+        NPG_HIP(lb.dofs.upload(dofs));
+        NPG_HIP(lb.off.upload(off));
+        NPG_HIP(lb.val.alloc((size_t)total));
+        NPG_HIP(lb.val32.alloc((size_t)total));
+        NPG_HIP(lb.val16.alloc((size_t)total));
+        NPG_HIP(lb.scale.alloc((size_t)nu));
+        lb.nblocks = nb;
+        std::swap(Dinv->lb, lb);
         Dinv->gen++;
     }
     int *bad = reinterpret_cast<int *>(ctx->d_scratch);
     NPG_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
     const int grid = (int)std::min<int64_t>(nb, 8 * ctx->num_cu);
     hipLaunchKernelGGL(k_line_block_inverse, dim3(grid), dim3(256), lds, ctx->stream, A->rowptr, A->col, A->val, block_ptr->d, block_dofs->d,
-                       nb, Dinv->rowptr, Dinv->val, (const int64_t *)Dinv->lb_off, Dinv->lb_val, Dinv->lb_val32, Dinv->lb_val16, Dinv->lb_scale, bad);
+                       nb, Dinv->rowptr, Dinv->val, (const int64_t *)Dinv->lb.off, Dinv->lb.val, Dinv->lb.val32, Dinv->lb.val16, Dinv->lb.scale, bad);
     NPG_HIP(hipGetLastError());
     int nbad = 0;
     NPG_HIP(hipMemcpyAsync(&nbad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -2128,8 +1376,8 @@ NPG_API int npg_csr_line_schur(npg_csr *S, const npg_csr *D, const npg_csr *Dinv
     NPG_REQUIRE(S && D && Dinv && G && wptr && wcols && woff && dperm && dpos && seg_ptr && seg_line && seg_start,
                 "npg_csr_line_schur: NULL argument");
     NPG_REQUIRE(S->nnode() == 0 && D->nnode() == 0 && G->nnode() == 0, "npg_csr_line_schur: node-blocked matrices are not supported");
-    NPG_REQUIRE(Dinv->lb_nblocks > 0 && Dinv->lb_val, "npg_csr_line_schur: Dinv is not a line-block inverse (npg_csr_line_block_inverse)");
-    const int64_t nl = Dinv->lb_nblocks, np = S->m, nu = Dinv->m;
+    NPG_REQUIRE(Dinv->lb.nblocks > 0 && Dinv->lb.val, "npg_csr_line_schur: Dinv is not a line-block inverse (npg_csr_line_block_inverse)");
+    const int64_t nl = Dinv->lb.nblocks, np = S->m, nu = Dinv->m;
     NPG_REQUIRE(D->n == nu && G->m == nu && D->m == np && S->n == G->n, "npg_csr_line_schur: shapes do not chain");
     NPG_REQUIRE(wptr->n == nl + 1 && woff->n == nl + 1 && wcols->bound == G->n && dperm->n == D->nnz && dperm->bound == D->nnz &&
                     dpos->n == D->nnz && seg_ptr->n == np + 1 && seg_start->n == seg_line->n + 1 && seg_line->bound == nl &&
@@ -2161,7 +1409,7 @@ NPG_API int npg_csr_line_schur(npg_csr *S, const npg_csr *D, const npg_csr *Dinv
     hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(k_line_schur_w), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (ea != hipSuccess) { hipFree(W); NPG_HIP(ea); }
     hipLaunchKernelGGL(k_line_schur_w, dim3((unsigned)std::min<int64_t>(nl, 4 * ctx->num_cu)), dim3(256), lds, ctx->stream,
-                       (const int64_t *)Dinv->lb_ptr, (const int64_t *)Dinv->lb_dofs, (const int64_t *)Dinv->lb_off, (const double *)Dinv->lb_val, nl,
+                       (const int64_t *)Dinv->lb.ptr, (const int64_t *)Dinv->lb.dofs, (const int64_t *)Dinv->lb.off, (const double *)Dinv->lb.val, nl,
                        G->rowptr, G->col, G->val, (const int64_t *)wptr->d, (const int64_t *)wcols->d, (const int64_t *)woff->d, W, missing);
     hipLaunchKernelGGL(k_line_schur_s, dim3((unsigned)std::min<int64_t>((np + 3) / 4, 16 * ctx->num_cu)), dim3(256), 0, ctx->stream, np,
                        (const double *)D->val, (const int64_t *)dperm->d, (const int64_t *)dpos->d, (const int64_t *)seg_ptr->d,
@@ -2301,19 +1549,19 @@ __global__ void __launch_bounds__(256) k_line_apply(const int64_t *__restrict__ 
 }
 
 static int line_apply(const npg_csr *A, const double *x, const SpmvEpi &e) {
-    const int grid = (int)std::min<int64_t>((A->lb_nblocks + 3) / 4, 16 * (int64_t)A->ctx->num_cu);
+    const int grid = (int)std::min<int64_t>((A->lb.nblocks + 3) / 4, 16 * (int64_t)A->ctx->num_cu);
     static const bool fp16 = !getenv("NPG_LINE_FP16") || atoi(getenv("NPG_LINE_FP16")) != 0;
     if (e.f32 && fp16)          // (products that accept rounded operator values: the column-scaled fp16 pack, half of fp32's bytes)
-        hipLaunchKernelGGL(k_line_apply<_Float16>, dim3(std::max(grid, 1)), dim3(256), 0, A->ctx->stream, (const int64_t *)A->lb_ptr,
-                           (const int64_t *)A->lb_dofs, (const int64_t *)A->lb_off, (const _Float16 *)A->lb_val16, A->lb_nblocks, x, e.alpha, e.beta,
-                           e.c, e.y, (const double *)A->lb_scale);
+        hipLaunchKernelGGL(k_line_apply<_Float16>, dim3(std::max(grid, 1)), dim3(256), 0, A->ctx->stream, (const int64_t *)A->lb.ptr,
+                           (const int64_t *)A->lb.dofs, (const int64_t *)A->lb.off, (const _Float16 *)A->lb.val16, A->lb.nblocks, x, e.alpha, e.beta,
+                           e.c, e.y, (const double *)A->lb.scale);
     else if (e.f32)
-        hipLaunchKernelGGL(k_line_apply<float>, dim3(std::max(grid, 1)), dim3(256), 0, A->ctx->stream, (const int64_t *)A->lb_ptr,
-                           (const int64_t *)A->lb_dofs, (const int64_t *)A->lb_off, (const float *)A->lb_val32, A->lb_nblocks, x, e.alpha, e.beta, e.c,
+        hipLaunchKernelGGL(k_line_apply<float>, dim3(std::max(grid, 1)), dim3(256), 0, A->ctx->stream, (const int64_t *)A->lb.ptr,
+                           (const int64_t *)A->lb.dofs, (const int64_t *)A->lb.off, (const float *)A->lb.val32, A->lb.nblocks, x, e.alpha, e.beta, e.c,
                            e.y);
     else
-        hipLaunchKernelGGL(k_line_apply<double>, dim3(std::max(grid, 1)), dim3(256), 0, A->ctx->stream, (const int64_t *)A->lb_ptr,
-                           (const int64_t *)A->lb_dofs, (const int64_t *)A->lb_off, (const double *)A->lb_val, A->lb_nblocks, x, e.alpha, e.beta, e.c,
+        hipLaunchKernelGGL(k_line_apply<double>, dim3(std::max(grid, 1)), dim3(256), 0, A->ctx->stream, (const int64_t *)A->lb.ptr,
+                           (const int64_t *)A->lb.dofs, (const int64_t *)A->lb.off, (const double *)A->lb.val, A->lb.nblocks, x, e.alpha, e.beta, e.c,
                            e.y);
     NPG_HIP(hipGetLastError());
     return NPG_OK;
@@ -2322,7 +1570,7 @@ static int line_apply(const npg_csr *A, const double *x, const SpmvEpi &e) {
 // y[0, m) = alpha A x[0, n) + beta y on raw device pointers (x and y may be windows into larger vectors; they must not overlap)
 bool nb_epilogue_ok(const npg_csr *Ap, const npg_csr *Dinv, int64_t nu) {
     const npg_csr *A = spmv_form(Ap);
-    if (!A || !Dinv || A->nnode() == 0 || A->pk9 || A->uperm || Dinv->lb_nblocks || Dinv->nnode() || A->n != A->m) return false;
+    if (!A || !Dinv || A->nnode() == 0 || A->pk9 || A->uperm || Dinv->lb.nblocks || Dinv->nnode() || A->n != A->m) return false;
     const int64_t nf = A->nfull, ns = A->nsurf, rest = nu - 3 * nf - 2 * ns;
     return rest >= 0 && Dinv->m == nu && Dinv->nnz == 9 * nf + 4 * ns + rest && A->block_rows() <= nu;
 }
@@ -2334,9 +1582,9 @@ int64_t spmv_stream_bytes(const npg_csr *Ap, const SpmvEpi &e, bool windowed) {
     static const bool dense_blocks = !getenv("NPG_LINE_DENSE") || atoi(getenv("NPG_LINE_DENSE")) != 0;
     static const bool fp16 = !getenv("NPG_LINE_FP16") || atoi(getenv("NPG_LINE_FP16")) != 0;
     int64_t b = 0;
-    if (A->lb_nblocks && !e.z && dense_blocks) {
+    if (A->lb.nblocks && !e.z && dense_blocks) {
         // dense column-major block pack (k_line_apply): sum of n_b^2 values = the CSR form's nnz, + block offsets and DoF lists
-        b = A->nnz * (e.f32 ? (fp16 ? 2 : 4) : 8) + 16 * A->lb_nblocks + 8 * A->m + (e.f32 && fp16 ? 8 * A->m : 0);
+        b = A->nnz * (e.f32 ? (fp16 ? 2 : 4) : 8) + 16 * A->lb.nblocks + 8 * A->m + (e.f32 && fp16 ? 8 * A->m : 0);
     } else if (windowed) {
         int64_t wb = 0;
         npg_csr_window_info(A, nullptr, nullptr, nullptr, &wb);
@@ -2355,7 +1603,7 @@ int spmv_epi(const npg_csr *Ap, const double *x, const SpmvEpi &e, const NbEpi *
     const npg_csr *A = spmv_form(Ap);
     static const bool dense_blocks = !getenv("NPG_LINE_DENSE") || atoi(getenv("NPG_LINE_DENSE")) != 0;
     if (byte_sink) *byte_sink += spmv_stream_bytes(A, e, false) + (nb ? 8 * (int64_t)nb->rows * 4 : 0);
-    if (A->lb_nblocks && !e.z && dense_blocks) return line_apply(A, x, e);
+    if (A->lb.nblocks && !e.z && dense_blocks) return line_apply(A, x, e);
     if (int rc = check_record_view(A, true, "spmv")) return rc;
     NPG_REQUIRE(!nb || (A->nnode() > 0 && !A->pk9), "spmv: the node-block epilogue needs a matrix stored by {c, K, C} node blocks");
     switch (A->lanes) {
@@ -2558,7 +1806,7 @@ int64_t gather32_floats(const npg_csr *Ap);
 // them, the ghost nodes the windowed tile set addresses as record columns
 int64_t gather32_nodes(const npg_csr *Ap) {
     const npg_csr *A = spmv_form(Ap);
-    return A->nnode() + (A->gslot ? A->ngn() : 0);
+    return A->nnode() + (A->win.gslot ? A->ngn() : 0);
 }
 // x (n entries, fp64) -> its fp32 gather-layout copy; then y = alpha A fl32(x) + beta c ... on A's windowed tiles
 int spmv_epi_gather32(const npg_csr *Ap, const double *x, float *xg, const SpmvEpi &e, const NbEpi *nb) {
@@ -2569,17 +1817,17 @@ int spmv_epi_gather32(const npg_csr *Ap, const double *x, float *xg, const SpmvE
     const int64_t nbr = A->block_rows();
     const GatherMap g{xg, 3 * A->nfull, A->nfull, (int)nbr, (int)(gather32_nodes(A) * 4 - nbr)};
     hipLaunchKernelGGL(k_fill_gather32, dim3((unsigned)std::min<int64_t>(2048, (A->n + 255) / 256)), dim3(256), 0, A->ctx->stream, x, g, A->n);
-    const dim3 grid(std::max(1, std::min<int>(A->nwtiles, 3 * A->ctx->num_cu))), blk(kSpmvThreads);
+    const dim3 grid(std::max(1, std::min<int>(A->win.nwtiles, 3 * A->ctx->num_cu))), blk(kSpmvThreads);
     const WinDev W = win_view(A);
 #define NPG_G32E(LL)                                                                                                                     \
-    if (nb && A->wlanes == 8)                                                                                                            \
-        hipLaunchKernelGGL((k_spmv_g32e<LL, 8, true>), grid, blk, 0, A->ctx->stream, csr_view(A), W, A->wtile_ptr, A->nwtiles, g, e, *nb); \
+    if (nb && A->win.wlanes == 8)                                                                                                            \
+        hipLaunchKernelGGL((k_spmv_g32e<LL, 8, true>), grid, blk, 0, A->ctx->stream, csr_view(A), W, A->win.wtile_ptr, A->win.nwtiles, g, e, *nb); \
     else if (nb)                                                                                                                         \
-        hipLaunchKernelGGL((k_spmv_g32e<LL, 4, true>), grid, blk, 0, A->ctx->stream, csr_view(A), W, A->wtile_ptr, A->nwtiles, g, e, *nb); \
-    else if (A->wlanes == 8)                                                                                                             \
-        hipLaunchKernelGGL((k_spmv_g32e<LL, 8>), grid, blk, 0, A->ctx->stream, csr_view(A), W, A->wtile_ptr, A->nwtiles, g, e, NbEpi{}); \
+        hipLaunchKernelGGL((k_spmv_g32e<LL, 4, true>), grid, blk, 0, A->ctx->stream, csr_view(A), W, A->win.wtile_ptr, A->win.nwtiles, g, e, *nb); \
+    else if (A->win.wlanes == 8)                                                                                                             \
+        hipLaunchKernelGGL((k_spmv_g32e<LL, 8>), grid, blk, 0, A->ctx->stream, csr_view(A), W, A->win.wtile_ptr, A->win.nwtiles, g, e, NbEpi{}); \
     else                                                                                                                                 \
-        hipLaunchKernelGGL((k_spmv_g32e<LL, 4>), grid, blk, 0, A->ctx->stream, csr_view(A), W, A->wtile_ptr, A->nwtiles, g, e, NbEpi{})
+        hipLaunchKernelGGL((k_spmv_g32e<LL, 4>), grid, blk, 0, A->ctx->stream, csr_view(A), W, A->win.wtile_ptr, A->win.nwtiles, g, e, NbEpi{})
     switch (A->lanes) {
         case 4: NPG_G32E(4); break;
         case 8: NPG_G32E(8); break;
@@ -2593,14 +1841,14 @@ int spmv_epi_gather32(const npg_csr *Ap, const double *x, float *xg, const SpmvE
 // floats the gather-layout copy of one of A's input vectors takes (0: A has no windowed tile set to multiply it with)
 int64_t gather32_floats(const npg_csr *Ap) {
     const npg_csr *A = spmv_form(Ap);
-    if (!(A->nnode() > 0 && !A->pk9 && !A->uperm && A->wtile_ptr && A->n == A->m)) return 0;
+    if (!(A->nnode() > 0 && !A->pk9 && !A->uperm && A->win.wtile_ptr && A->n == A->m)) return 0;
     return 4 * gather32_nodes(A) + (A->n - A->block_rows()) + 8;
 }
 
 template <int L>
 static void launch_spmv_g32(const npg_csr *A, const GatherMap &g, double *y, bool win) {
-    const void *tiles = win ? (const void *)A->wtile_ptr : (const void *)A->tile_ptr;
-    const int nt = win ? A->nwtiles : A->ntiles;
+    const void *tiles = win ? (const void *)A->win.wtile_ptr : (const void *)A->tile_ptr;
+    const int nt = win ? A->win.nwtiles : A->ntiles;
     const WinDev W = win_view(A);
     const dim3 grid(std::max(1, std::min<int>(nt, 3 * A->ctx->num_cu))), blk(kSpmvThreads);
     static const int diag = getenv("NPG_WIN_DIAG") ? atoi(getenv("NPG_WIN_DIAG")) : 0;      // tools/window_ab.py: timing diagnostics
@@ -2608,7 +1856,7 @@ static void launch_spmv_g32(const npg_csr *A, const GatherMap &g, double *y, boo
         unsigned long long *acc = nullptr, h[10];
         if (hipMalloc((void **)&acc, sizeof h) != hipSuccess) return;
         hipMemsetAsync(acc, 0, sizeof h, A->ctx->stream);
-        hipLaunchKernelGGL((k_spmv_g32_timed<L, 4>), grid, blk, 0, A->ctx->stream, csr_view(A), W, A->wtile_ptr, nt, g, y, acc);
+        hipLaunchKernelGGL((k_spmv_g32_timed<L, 4>), grid, blk, 0, A->ctx->stream, csr_view(A), W, A->win.wtile_ptr, nt, g, y, acc);
         hipMemcpyAsync(h, acc, sizeof h, hipMemcpyDeviceToHost, A->ctx->stream);
         hipStreamSynchronize(A->ctx->stream);
         hipFree(acc);
@@ -2641,7 +1889,7 @@ static void launch_spmv_g32(const npg_csr *A, const GatherMap &g, double *y, boo
         }
         return;
     }
-    if (win && A->wlanes == 8)
+    if (win && A->win.wlanes == 8)
         hipLaunchKernelGGL((k_spmv_g32<L, 8>), grid, blk, 0, A->ctx->stream, csr_view(A), W, tiles, nt, g, y);
     else if (win)
         hipLaunchKernelGGL((k_spmv_g32<L, 4>), grid, blk, 0, A->ctx->stream, csr_view(A), W, tiles, nt, g, y);
@@ -2660,7 +1908,7 @@ NPG_API int npg_spmv_gather32(const npg_csr *A, const npg_vec *x, npg_vec *y, in
                 (long long)A->m, (long long)A->n, (long long)x->n, (long long)y->n);
     NPG_REQUIRE(A->nnode() > 0 && !A->pk9 && !A->packed, "npg_spmv_gather32: the matrix is not stored by {c, K, C} node blocks");
     NPG_REQUIRE(!A->uperm, "npg_spmv_gather32: the matrix carries an internal renumbering (npg_csr_block_nodes_dofs)");
-    NPG_REQUIRE(!windowed || A->wtile_ptr, "npg_spmv_gather32: the matrix has no windowed tile set");
+    NPG_REQUIRE(!windowed || A->win.wtile_ptr, "npg_spmv_gather32: the matrix has no windowed tile set");
     NPG_HIP(hipSetDevice(A->ctx->device));
     const int64_t nbr = A->block_rows(), need = 4 * gather32_nodes(A) + (A->n - nbr) + 8;
     float *buf = nullptr;
@@ -2669,9 +1917,9 @@ NPG_API int npg_spmv_gather32(const npg_csr *A, const npg_vec *x, npg_vec *y, in
     const GatherMap g{buf, 3 * A->nfull, A->nfull, (int)nbr, (int)(4 * gather32_nodes(A) - nbr)};
     hipLaunchKernelGGL(k_fill_gather32, dim3((unsigned)std::min<int64_t>(4096, (A->n + 255) / 256)), dim3(256), 0, A->ctx->stream, x->d, g,
                        A->n);
-    if (A->gslot && A->n > A->m)
+    if (A->win.gslot && A->n > A->m)
         hipLaunchKernelGGL(k_fill_ghost_slots, dim3((unsigned)std::min<int64_t>(4096, (A->n - A->m + 255) / 256)), dim3(256), 0,
-                           A->ctx->stream, x->d + A->m, buf, A->n - A->m, A->gslot);
+                           A->ctx->stream, x->d + A->m, buf, A->n - A->m, A->win.gslot);
     for (int r = 0; r < std::max(1, reps); ++r) switch (A->lanes) {
             case 4: launch_spmv_g32<4>(A, g, y->d, windowed != 0); break;
             case 8: launch_spmv_g32<8>(A, g, y->d, windowed != 0); break;

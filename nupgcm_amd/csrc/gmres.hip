@@ -1682,19 +1682,19 @@ static void gmres_plan(GmresPlan &p, npg_gmres *ws, const npg_csr *A, int precon
         // node slots: the owned block nodes and, behind them, the ghost nodes the windowed tiles use as record columns
         // (NOT gather32_floats(A): that is the stand-alone product's question and answers 0 for a rank's row block - round 5's first
         //  version sized the copy without the ghost slots through it and the unpack wrote 4 ngn floats past the end)
-        const int64_t nslots = A->wtile_ptr ? gather32_nodes(A) : A->nnode();
+        const int64_t nslots = A->win.wtile_ptr ? gather32_nodes(A) : A->nnode();
         const int64_t nbr = A->block_rows();
         p.xg_floats = 4 * nslots + (A->n - nbr) + 8;
         d.xg = GatherMap{nullptr, 3 * A->nfull, A->nfull, (int)nbr, (int)(4 * nslots - nbr)};
-        d.gslot = A->wtile_ptr ? A->gslot : nullptr;
+        d.gslot = A->win.wtile_ptr ? A->win.gslot : nullptr;
         // windowed tile set of the block rows (spmv_window.h; NPG_GMRES_WINDOW=0: the ordinary tiles)
-        if (k.window && ws->gather32 != 2 && d.split && A->wtile_ptr && !A->pk9 && nbr > 0) {
-            d.wt_ptr = A->wtile_ptr;
+        if (k.window && ws->gather32 != 2 && d.split && A->win.wtile_ptr && !A->pk9 && nbr > 0) {
+            d.wt_ptr = A->win.wtile_ptr;
             d.W = win_view(A);
-            d.nwt = A->nwtiles;
-            d.nwt_int = A->nwtiles_interior;
-            d.wl = A->wlanes;
-            d.word = k.win_ord || (A->nwrow_tiles == 0 && A->m > A->block_rows());
+            d.nwt = A->win.nwtiles;
+            d.nwt_int = A->win.nwtiles_interior;
+            d.wl = A->win.wlanes;
+            d.word = k.win_ord || (A->win.nwrow_tiles == 0 && A->m > A->block_rows());
             d.wpre = k.win_pre;
         }
     }

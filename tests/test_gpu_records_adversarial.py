@@ -155,7 +155,7 @@ def test_hubs_at_the_window_caps(arch, monkeypatch, N, values):
     """A windowed tile lists its distinct column nodes, at most kWinNodes = 2 per lane of 512 (spmv_window.h): 1024.  A node's N
     records name N distinct nodes; the zero record that pads an odd list repeats the last column node and adds none, and N records
     are (N + 1) / 2 <= 1024 pairs (cap kWinPairs x 512) and 8 x 3 x 513 + 16 x 1025 bytes - far from the other limits
-    (build_window_tiles_scaled).  So N = 513 .. 1024 fills the second window-list slot (tid + 512), 1024 fits and 1025 is the
+    (plan_window_tiles).  So N = 513 .. 1024 fills the second window-list slot (tid + 512), 1024 fits and 1025 is the
     first that does not: the matrix is still node-blocked but has NO windowed set."""
     c = R.hub_case(N, 0, values, np.random.default_rng(N))
     info = run_case(arch, c, monkeypatch, want_window=N <= 1024)
@@ -166,7 +166,7 @@ def test_hubs_at_the_window_caps(arch, monkeypatch, N, values):
 @pytest.mark.parametrize("G", [512, 513])
 def test_gradient_columns_at_the_window_caps(arch, monkeypatch, G, values):
     """kWinCols = 1 column record per lane and one distinct other column per lane: 512 of each (cap_c and nv <= NT in
-    build_window_tiles_scaled); a node with 513 gradient columns leaves the matrix without a windowed set."""
+    plan_window_tiles); a node with 513 gradient columns leaves the matrix without a windowed set."""
     c = R.hub_case(0, G, values, np.random.default_rng(G))
     run_case(arch, c, monkeypatch, want_window=G <= 512)
 
