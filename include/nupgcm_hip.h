@@ -671,6 +671,29 @@ int npg_tavg_accumulate(npg_tavg *T, double r, double q, const npg_vec *x_inv, c
 int npg_tavg_info(const npg_tavg *T, int64_t *nnode, int64_t *n_inv, int64_t *n_b);
 int npg_tavg_destroy(npg_tavg *T);
 
+/* ---- gradients of the state recovered at the mesh's P2 nodes (new work: the reference's save_vtk hands Gridap cell fields) -------------
+ * d_j u_a, grad b', grad p as NODAL fields: what vorticity, divergence, N^2 + d_z b' and the planetary PV are made of
+ * (csrc/nodal_core.h).  Tetrahedral engines only.  Selected node j has the incidences inc[inc_ptr[j] .. inc_ptr[j + 1]),
+ * each 16 cell + local with local = 0 .. 9 the node's place in that cell (vertices, then the edges (0,1) (0,2) (1,2) (0,3) (1,3) (2,3)),
+ * in ascending cell order.  Per cell and field the gradient at the cell's four vertices is formed as npg_fe_sample forms it there; a
+ * mid-node of the edge (a, b) takes 0.5 (g_a + g_b); per node S = sum_c w_c g_c and W = sum_c w_c from 0.0 in incidence order and the
+ * result is S / W, with w_c = the cell's wdet (weight_mode 0) or 1.0 (weight_mode 1).  Boundary nodes get one-sided averages.
+ * out[channel][nsel], the channels of the groups of fields_mask in this order: NPG_NODAL_U d_j u_a at 3 a + j (9), NPG_NODAL_B grad b' (3),
+ * NPG_NODAL_P grad p (3), then W and the valence - NPG_NODAL_NCH = 17 with every group.  Two launches on the context's stream (cells
+ * into a scratch of [ncell][<= 51] doubles owned by the handle, then nodes), no atomics: the bits of the host library on every call.
+ * Validation (NPG_EINVAL + message) happens before anything is launched: NULL arguments, inc_ptr not starting at 0 or decreasing, a
+ * selected node without incidence, cell >= ncell, local >= 10, cells not ascending, ncell >= 2^27, weight_mode, fields_mask, vector
+ * lengths, an embedded 2-D engine.  nsel = 0 is legal.  The engine must outlive the handle. */
+typedef struct npg_nodal npg_nodal;
+#define NPG_NODAL_U 1
+#define NPG_NODAL_B 2
+#define NPG_NODAL_P 4
+#define NPG_NODAL_NCH 17
+int npg_nodal_create(npg_fe *fe, int64_t nsel, const int64_t *inc_ptr, const int32_t *inc, int weight_mode, npg_nodal **out);
+int npg_nodal_compute(npg_nodal *N, const npg_vec *x_inv, const npg_vec *b, int fields_mask, npg_vec *out);
+int npg_nodal_info(const npg_nodal *N, int64_t *nsel, int64_t *ninc, int64_t *max_valence, int64_t *scratch_doubles);
+int npg_nodal_destroy(npg_nodal *N);
+
 /* ---- the state binned into (latitude band, buoyancy class) (new work: the reference overlays isopycnals on a z-coordinate psi) --
  * A joint table [ny + 1][nb + 1][NPG_NCLS] over the cells of the mesh (csrc/classes_core.h).
  * Sample rule - NOT the engine's quadrature (Keast's rule has a negative weight): ns barycentric points rule_lam[ns][4] with weights

@@ -18,6 +18,7 @@ from .io import save_checkpoint, save_state, save_vtk, set_out_dir, set_state_fr
 from .iterative_solvers import BatchedCgWorkspace, CgWorkspace, Diagonal, GmresWorkspace, IterativeSolverToolkit, MgsGmresWorkspace, iterative_solve
 from .multigrid import BlockDiagonalPreconditioner, DenseInversePreconditioner, FgmresWorkspace, GeneralPreconditioner, MultigridPreconditioner
 from .model import BlowUp, Model, State, evolve, invert, run, set_b, sync_flow
+from .nodal import NodalFields, NodalGradients
 from .particles import ParticleTracker, cell_neighbours, mesh_period
 from .sampling import (GridDiagnostics, GridIntegrals, GridSamples, Located, PointLocator, average_stratification,
                        barotropic_streamfunction, depth, find_H, nan_eval, overturning_streamfunction, sample_profiles,

@@ -169,6 +169,8 @@ def _declare(L, partial=False):
         "npg_forcing_info": [P] + [C.POINTER(I64)] * 5, "npg_csr_axpy": [P, D, P],
         "npg_tavg_create": [P, I64, I64, I64, VP, VP, PP], "npg_tavg_destroy": [P], "npg_tavg_accumulate": [P, D, D, P, P, P, P, P],
         "npg_tavg_info": [P] + [C.POINTER(I64)] * 3,
+        "npg_nodal_create": [P, I64, VP, VP, C.c_int, PP], "npg_nodal_destroy": [P], "npg_nodal_compute": [P, P, P, C.c_int, P],
+        "npg_nodal_info": [P] + [C.POINTER(I64)] * 4,
         "npg_classes_create": [P, VP, VP, VP, VP, VP, C.c_int, VP, I64, VP, I64, PP], "npg_classes_destroy": [P],
         "npg_classes_compute": [P, P, P, D, P, P],
         "npg_classes_set_diffusivity": [P, VP, D, VP, D], "npg_classes_mixing": [P, P, D, D, D, D, D, P, P],
@@ -245,6 +247,8 @@ NPG_NBND = 24
 NPG_BND_NU, NPG_BND_KH, NPG_BND_KV, NPG_BND_TAUX, NPG_BND_TAUY, NPG_BND_FLUX = range(6)
 NPG_FRC_NSERIES = 4
 NPG_FRC_TAUX, NPG_FRC_TAUY, NPG_FRC_FLUX, NPG_FRC_TARGET = range(4)
+NPG_NODAL_U, NPG_NODAL_B, NPG_NODAL_P = 1, 2, 4
+NPG_NODAL_NCH = 17
 NPG_NCLS = 8
 NPG_NMIX = 8
 NPG_NSURF = 9

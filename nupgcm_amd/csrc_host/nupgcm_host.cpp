@@ -1724,6 +1724,73 @@ NPG_API int npg_tavg_accumulate(npg_tavg *T, double r, double q, const npg_vec *
     return NPG_OK;
 }
 
+// ---- gradients of the state recovered at the mesh's P2 nodes (csrc/nodal.hip on the host): the per-cell vertex gradients, the per-node
+// sum and the argument checks are the SAME code (csrc/nodal_core.h); every cell's record and every node's row is one thread's own. --------
+#include "../csrc/nodal_core.h"
+static_assert(NPG_NODAL_U == npg::kNodalU && NPG_NODAL_B == npg::kNodalB && NPG_NODAL_P == npg::kNodalP && NPG_NODAL_NCH == npg::kNodalMaxCh,
+              "the field codes of the header and of nodal_core.h must agree");
+
+struct npg_nodal {
+    npg_fe *fe = nullptr;
+    int64_t nsel = 0, max_valence = 0;
+    int weight_mode = 0;
+    std::vector<int64_t> ptr;
+    std::vector<int32_t> inc;
+    std::vector<double> scratch;
+};
+NPG_API int npg_nodal_create(npg_fe *fe, int64_t nsel, const int64_t *inc_ptr, const int32_t *inc, int weight_mode, npg_nodal **out) {
+    REQUIRE(fe && out, "npg_nodal_create: NULL argument");
+    {   // an embedded 2-D engine pads its triangles to tetrahedra with a zero fourth gradient: its nodes have other local numbers
+        bool flat = true;
+        for (int q = 0; q < fe->nq; ++q) flat = flat && fe->N1[(size_t)q * 4 + 3] == 0.0;
+        REQUIRE(!flat, "npg_nodal_create: an embedded 2-D engine is refused (the recovery is written for tetrahedra)");
+    }
+    int64_t vmax = 0;
+    REQUIRE_OK(npg::check_nodal_create(fe->ncell, nsel, inc_ptr, inc, weight_mode, &vmax));
+    std::unique_ptr<npg_nodal> N(new npg_nodal());
+    N->fe = fe;
+    N->nsel = nsel, N->max_valence = vmax, N->weight_mode = weight_mode;
+    N->ptr.assign(inc_ptr, inc_ptr + nsel + 1);
+    if (nsel > 0) N->inc.assign(inc, inc + inc_ptr[nsel]);
+    *out = N.release();
+    return NPG_OK;
+}
+NPG_API int npg_nodal_destroy(npg_nodal *N) {
+    delete N;
+    return NPG_OK;
+}
+NPG_API int npg_nodal_info(const npg_nodal *N, int64_t *nsel, int64_t *ninc, int64_t *max_valence, int64_t *scratch_doubles) {
+    REQUIRE(N, "npg_nodal_info: NULL argument");
+    if (nsel) *nsel = N->nsel;
+    if (ninc) *ninc = (int64_t)N->inc.size();
+    if (max_valence) *max_valence = N->max_valence;
+    if (scratch_doubles) *scratch_doubles = (int64_t)N->scratch.size();
+    return NPG_OK;
+}
+NPG_API int npg_nodal_compute(npg_nodal *N, const npg_vec *x_inv, const npg_vec *b, int fields_mask, npg_vec *out) {
+    REQUIRE(N && x_inv && b && out, "npg_nodal_compute: NULL argument");
+    const npg_fe *fe = N->fe;
+    REQUIRE_OK(npg::check_nodal_compute(fe->n_inv, fe->n_b, fe->nb, N->nsel, x_inv->n, b->n, fields_mask, out->n,
+                                        x_inv->ctx == fe->ctx && b->ctx == fe->ctx && out->ctx == fe->ctx));
+    if (N->nsel == 0) return NPG_OK;
+    const npg::NodalPlan pl = npg::nodal_plan(fields_mask, fe->nb);
+    const int64_t ncell = fe->ncell, nsel = N->nsel;
+    if (N->scratch.size() < (size_t)ncell * pl.nslot) N->scratch.resize((size_t)ncell * pl.nslot);
+    const HostView t = host_view(fe);
+    double *scr = N->scratch.data();
+    if (fe->nb == 10) {
+#pragma omp parallel for schedule(static)
+        for (int64_t c = 0; c < ncell; ++c) npg::nodal_cell<HostView, 10>(t, pl, x_inv->d, b->d, c, scr + (size_t)c * pl.nslot);
+    } else {
+#pragma omp parallel for schedule(static)
+        for (int64_t c = 0; c < ncell; ++c) npg::nodal_cell<HostView, 4>(t, pl, x_inv->d, b->d, c, scr + (size_t)c * pl.nslot);
+    }
+    const npg::NodalTable tab{nsel, N->ptr.data(), N->inc.data(), fe->wdet.data(), N->weight_mode};
+#pragma omp parallel for schedule(static)
+    for (int64_t j = 0; j < nsel; ++j) npg::nodal_node(tab, pl, scr, j, out->d);
+    return NPG_OK;
+}
+
 // ---- the state binned into (latitude band, buoyancy class) (csrc/classes.hip on the host): the per-sample arithmetic and the edge
 // search are the SAME code (csrc/classes_core.h).  Pass 1 in fixed chunks of kClsChunk cells, folded in chunk order; pass 2 adds the
 // quantised terms as 64-bit integers (relaxed atomics on one table, a run of samples in one bin added up first): integer addition is

@@ -120,6 +120,13 @@ def _nodal_closure_fields(model, b_full):
     np.add.at(acc, m.cell_nodes.ravel(), bz.ravel())
     np.add.at(cnt, m.cell_nodes.ravel(), 1.0)
     abz = prm.alpha * acc / np.maximum(cnt, 1.0)
+    return _closures_of(model, abz)
+
+
+def _closures_of(model, abz):
+    """(alpha*b_z, nu, kappa_v) at the P2 nodes from alpha*b_z there: the closures of src/inputs.jl:87-91, 130-137 or the forcing
+    functions (what _nodal_closure_fields and NodalGradients.closures share)"""
+    m, frc = model.fe_data.mesh, model.forcings
     x = m.node_coords
 
     def ev(fn):
@@ -138,10 +145,15 @@ def _nodal_closure_fields(model, b_full):
     return abz, nu, kv
 
 
-def save_vtk(model, ofile):
+def save_vtk(model, ofile, nodal=None):
     """save_vtk(model; ofile) - src/IO.jl:25-59 with order = 2 (quadratic tetrahedra): fields u, p, b = N2 z + b',
-    alpha*b_z, nu, kappa_v and t."""
+    alpha*b_z, nu, kappa_v and t.  nodal: a NodalFields of the model - its gradients of the CURRENT state (computed on the device) add
+    the PointData arrays grad_b, vorticity, div_u, N2 and pv after those; without it the file is what it always was."""
     m = model.fe_data.mesh
+    extra = ()
+    if nodal is not None:
+        g = nodal.compute()
+        extra = (("grad_b", g.grad_b), ("vorticity", g.vorticity()), ("div_u", g.divergence()), ("N2", g.N2()), ("pv", g.pv()))
     u, p, b = _nodal_fields(model)                 # (distributed models: collective gathers of the state)
     if getattr(model.arch.ctx, "rank", 0) != 0:
         return ofile                               # one writer
@@ -174,5 +186,9 @@ def save_vtk(model, ofile):
         for name, a in (("alpha*b_z", abz), ("nu", nu), ("kappa_v", kv)):
             f.write(f'<DataArray type="Float64" Name="{name}" format="ascii">\n' + arr(a.reshape(-1, 1), "%.17g")
                     + "\n</DataArray>\n")
+        for name, a in extra:
+            a = a.reshape(m.nn, -1)
+            nco = f' NumberOfComponents="{a.shape[1]}"' if a.shape[1] > 1 else ""
+            f.write(f'<DataArray type="Float64" Name="{name}"{nco} format="ascii">\n' + arr(a, "%.17g") + "\n</DataArray>\n")
         f.write("</PointData>\n</Piece>\n</UnstructuredGrid>\n</VTKFile>\n")
     return ofile
