@@ -694,6 +694,41 @@ int npg_nodal_compute(npg_nodal *N, const npg_vec *x_inv, const npg_vec *b, int 
 int npg_nodal_info(const npg_nodal *N, int64_t *nsel, int64_t *ninc, int64_t *max_valence, int64_t *scratch_doubles);
 int npg_nodal_destroy(npg_nodal *N);
 
+/* ---- transports through sections: exact quadrature on the polygons a plane cuts out of the cells (new work: the reference samples
+ * slices of a .vtu file) ------------------------------------------------------------------------------------------------------------
+ * A section is a frame {o, n, e1, e2} (orthonormal to 1e-12) and two strictly increasing edge arrays (first / last may be -inf / +inf);
+ * bin (i, j) of section s is edges1[i] <= (x - o) . e1 < edges1[i + 1], edges2[j] <= (x - o) . e2 < edges2[j + 1], numbered section by
+ * section, (i, j) row-major (csrc/sections_core.h).  Integrated over every bin, with the degree-4 six-point triangle rule
+ * on every piece (exact for the P2 / P1 fields): NPG_NSEC = 14 raw channels - 1, u.n, b', b' u.n, z u.n, p, u_x, u_y, u_z, grad b'.n,
+ * kappa_h (d_x b' n_x + d_y b' n_y) + kappa_v d_z b' n_z, kappa_v n_z, z, d_z b'.
+ * The cut rule: d = ((x0 - o0) n0 + (x1 - o1) n1) + (x2 - o2) n2 at a cell's own vertices, below iff d < 0 (d == 0 is above); the corners
+ * lie on the edges with d_a < 0 <= d_b at t = d_a / (d_a - d_b).  So a mesh face in the plane is counted by exactly one of its two
+ * cells, and the polygons are clipped at the bin edges with the same half-open rule and fan-triangulated into pieces of area > 0.
+ * Pieces are ordered by (bin, cell, index); out[bin][ch] adds a bin's pieces in one fixed order - 64 accumulators filled round-robin in
+ * piece order from 0.0, then a fixed pairwise tree (section_fold of csrc/sections_core.h); an empty bin gives zeros; pieces_out
+ * [ch][npiece] holds the pieces' own terms.  Two launches on the context's stream, no atomics: the bits of the host library on every
+ * call (the convection closure's tanh apart).  set_coeff: kappa_h / kappa_v at the 6 points of every piece, [6][npiece] in piece order
+ * (NULL removes the table; a missing table contributes 0); set_closure adds the convection closure to kappa_v at the point's own d_z b'.
+ * Validation (NPG_EINVAL + message) happens before anything is launched: NULL arguments, non-finite frames or vertices, axes that are
+ * not orthonormal, edges that do not increase or are infinite inside, nsec outside 1 .. 64, more than 2^20 bins, more than 2^31 - 1
+ * pieces, non-finite coefficients (the handle keeps the table it had), vector lengths, an embedded 2-D engine.  The engine must outlive
+ * the handle. */
+typedef struct npg_sections npg_sections;
+#define NPG_NSEC 14
+#define NPG_SEC_KH 0
+#define NPG_SEC_KV 1
+int npg_sections_create(npg_fe *fe, const double *cell_xyz /* [ncell][4][3], the cells' own vertices */, int nsec,
+                        const double *frames /* [nsec][12]: o, n, e1, e2 */, const int32_t *n1, const int32_t *n2,
+                        const double *edges1 /* concatenated, n1[s] + 1 each */, const double *edges2,
+                        const uint8_t *cell_mask /* or NULL */, npg_sections **out);
+int npg_sections_info(const npg_sections *S, int64_t *npiece, int64_t *nbin, int64_t *ncut_cells, int64_t *max_per_bin);
+int npg_sections_pieces(const npg_sections *S, int32_t *cell, int32_t *bin, double *lam /* [npiece][3][4] */, double *area);
+int npg_sections_set_coeff(npg_sections *S, int which, const double *table /* [6][npiece] or NULL */);
+int npg_sections_set_closure(npg_sections *S, double kappa_c, double N2min, double alpha, double N2c);
+int npg_sections_compute(npg_sections *S, const npg_vec *x_inv, const npg_vec *b, npg_vec *out /* [nbin][NPG_NSEC] */,
+                         npg_vec *pieces_out /* or NULL: [NPG_NSEC][npiece] */);
+int npg_sections_destroy(npg_sections *S);
+
 /* ---- the state binned into (latitude band, buoyancy class) (new work: the reference overlays isopycnals on a z-coordinate psi) --
  * A joint table [ny + 1][nb + 1][NPG_NCLS] over the cells of the mesh (csrc/classes_core.h).
  * Sample rule - NOT the engine's quadrature (Keast's rule has a negative weight): ns barycentric points rule_lam[ns][4] with weights

@@ -23,6 +23,7 @@ from .particles import ParticleTracker, cell_neighbours, mesh_period
 from .sampling import (GridDiagnostics, GridIntegrals, GridSamples, Located, PointLocator, average_stratification,
                        barotropic_streamfunction, depth, find_H, nan_eval, overturning_streamfunction, sample_profiles,
                        sample_slice, sample_to_grid, zonal_mean, zonal_width)
+from .sections import Section, SectionFluxes, SectionMaps, SectionRecorder, SectionTransports
 from .surfaces import BuoyancySurfaces, SurfaceMaps, SurfaceRecorder, column_depth
 from .timesteppers import BDF1, BDF2, update_dt, update_t
 from .tracers import PassiveTracers, TracerSpec

@@ -171,6 +171,9 @@ def _declare(L, partial=False):
         "npg_tavg_info": [P] + [C.POINTER(I64)] * 3,
         "npg_nodal_create": [P, I64, VP, VP, C.c_int, PP], "npg_nodal_destroy": [P], "npg_nodal_compute": [P, P, P, C.c_int, P],
         "npg_nodal_info": [P] + [C.POINTER(I64)] * 4,
+        "npg_sections_create": [P, VP, C.c_int, VP, VP, VP, VP, VP, VP, PP], "npg_sections_destroy": [P],
+        "npg_sections_info": [P] + [C.POINTER(I64)] * 4, "npg_sections_pieces": [P, VP, VP, VP, VP],
+        "npg_sections_set_coeff": [P, C.c_int, VP], "npg_sections_set_closure": [P, D, D, D, D], "npg_sections_compute": [P, P, P, P, P],
         "npg_classes_create": [P, VP, VP, VP, VP, VP, C.c_int, VP, I64, VP, I64, PP], "npg_classes_destroy": [P],
         "npg_classes_compute": [P, P, P, D, P, P],
         "npg_classes_set_diffusivity": [P, VP, D, VP, D], "npg_classes_mixing": [P, P, D, D, D, D, D, P, P],
@@ -249,6 +252,8 @@ NPG_FRC_NSERIES = 4
 NPG_FRC_TAUX, NPG_FRC_TAUY, NPG_FRC_FLUX, NPG_FRC_TARGET = range(4)
 NPG_NODAL_U, NPG_NODAL_B, NPG_NODAL_P = 1, 2, 4
 NPG_NODAL_NCH = 17
+NPG_NSEC = 14
+NPG_SEC_KH, NPG_SEC_KV = 0, 1
 NPG_NCLS = 8
 NPG_NMIX = 8
 NPG_NSURF = 9

@@ -1791,6 +1791,98 @@ NPG_API int npg_nodal_compute(npg_nodal *N, const npg_vec *x_inv, const npg_vec 
     return NPG_OK;
 }
 
+// ---- transports through sections (csrc/sections.hip on the host): the plan, the per-piece arithmetic, the fold order and the argument
+// checks are the SAME code (csrc/sections_core.h); every piece's terms and every (bin, channel) sum is one thread's own. -----------------
+#include "../csrc/sections_core.h"
+static_assert(NPG_NSEC == npg::kNSec, "NPG_NSEC of the header and kNSec of sections_core.h must agree");
+static_assert(NPG_SEC_KH == npg::kSecKh && NPG_SEC_KV == npg::kSecKv, "the coefficient codes of the header and of sections_core.h must agree");
+
+struct npg_sections {
+    npg_fe *fe = nullptr;
+    npg::SecPlan plan;
+    npg::MixClosure cl{0.0, 0.0, 0.0, 0.0};
+    std::vector<double> cz;                      // [ncell][4]
+    std::vector<double> lam;                     // [12][npiece]
+    std::vector<double> coef[npg::kSecNCoef];    // [6][npiece] or empty
+    std::vector<double> terms;                   // [NPG_NSEC][npiece]
+};
+NPG_API int npg_sections_create(npg_fe *fe, const double *cell_xyz, int nsec, const double *frames, const int32_t *n1, const int32_t *n2,
+                                const double *edges1, const double *edges2, const uint8_t *cell_mask, npg_sections **out) {
+    REQUIRE(fe && out, "npg_sections_create: NULL argument");
+    bool flat = true;                   // an embedded 2-D engine keeps every quadrature point on the face lambda_4 = 0 of its padded tetrahedra
+    for (int q = 0; q < fe->nq; ++q) flat = flat && fe->N1[(size_t)q * 4 + 3] == 0.0;
+    std::unique_ptr<npg_sections> S(new npg_sections());
+    const int64_t nc = fe->ncell;
+    REQUIRE_OK(npg::sec_build_plan(true, flat, nc, cell_xyz, nsec, frames, n1, n2, edges1, edges2, cell_mask, S->plan));
+    S->fe = fe;
+    const size_t np = (size_t)S->plan.npiece();
+    S->cz.resize((size_t)nc * 4), S->lam.resize(12 * np), S->terms.resize(NPG_NSEC * np);
+    for (int64_t c = 0; c < nc; ++c)
+        for (int k = 0; k < 4; ++k) S->cz[(size_t)c * 4 + k] = cell_xyz[(size_t)c * 12 + 3 * k + 2];
+    for (size_t i = 0; i < np; ++i)
+        for (int k = 0; k < 12; ++k) S->lam[(size_t)k * np + i] = S->plan.lam[12 * i + k];
+    *out = S.release();
+    return NPG_OK;
+}
+NPG_API int npg_sections_destroy(npg_sections *S) {
+    delete S;
+    return NPG_OK;
+}
+NPG_API int npg_sections_info(const npg_sections *S, int64_t *npiece, int64_t *nbin, int64_t *ncut_cells, int64_t *max_per_bin) {
+    REQUIRE(S, "npg_sections_info: NULL argument");
+    if (npiece) *npiece = S->plan.npiece();
+    if (nbin) *nbin = S->plan.nbin;
+    if (ncut_cells) *ncut_cells = S->plan.ncut_cells;
+    if (max_per_bin) *max_per_bin = S->plan.max_per_bin;
+    return NPG_OK;
+}
+NPG_API int npg_sections_pieces(const npg_sections *S, int32_t *cell, int32_t *bin, double *lam, double *area) {
+    REQUIRE(S, "npg_sections_pieces: NULL argument");
+    const npg::SecPlan &pl = S->plan;
+    if (cell) std::copy(pl.cell.begin(), pl.cell.end(), cell);
+    if (bin) std::copy(pl.bin.begin(), pl.bin.end(), bin);
+    if (lam) std::copy(pl.lam.begin(), pl.lam.end(), lam);
+    if (area) std::copy(pl.area.begin(), pl.area.end(), area);
+    return NPG_OK;
+}
+NPG_API int npg_sections_set_coeff(npg_sections *S, int which, const double *table) {
+    REQUIRE_OK(npg::check_sections_coeff(S != nullptr, which, table, S ? S->plan.npiece() : 0));
+    std::vector<double> t;
+    if (table) t.assign(table, table + (size_t)npg::kSecQ * (size_t)S->plan.npiece());
+    S->coef[which].swap(t);
+    return NPG_OK;
+}
+NPG_API int npg_sections_set_closure(npg_sections *S, double kappa_c, double N2min, double alpha, double N2c) {
+    REQUIRE_OK(npg::check_sections_closure(S != nullptr, kappa_c, N2min, alpha, N2c));
+    S->cl = npg::MixClosure{kappa_c, N2min, alpha, N2c};
+    return NPG_OK;
+}
+NPG_API int npg_sections_compute(npg_sections *S, const npg_vec *x_inv, const npg_vec *b, npg_vec *out, npg_vec *pieces_out) {
+    REQUIRE(S && x_inv && b && out, "npg_sections_compute: NULL argument");
+    const npg_fe *fe = S->fe;
+    const npg::SecPlan &pl = S->plan;
+    const int64_t np = pl.npiece(), nbin = pl.nbin;
+    REQUIRE_OK(npg::check_sections_compute(true, fe->n_inv, fe->n_b, x_inv->n, b->n, nbin, np, out->n, pieces_out ? pieces_out->n : -1,
+                                           x_inv->ctx == fe->ctx && b->ctx == fe->ctx && out->ctx == fe->ctx &&
+                                               (!pieces_out || pieces_out->ctx == fe->ctx)));
+    npg::SecPieces<HostView> t{{host_view(fe), nullptr, S->cz.data()}, np, pl.cell.data(), pl.sec.data(), S->lam.data(), pl.area.data(),
+                               pl.normal.data(), {}};
+    // (a set_coeff table of a plan without pieces is empty, hence "missing": nothing reads it)
+    for (int w = 0; w < npg::kSecNCoef; ++w) t.coef_[w] = data_or_null(S->coef[w]);
+    double *terms = pieces_out ? pieces_out->d : S->terms.data();
+    const npg::MixClosure cl = S->cl;
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < np; ++i) {
+        double term[NPG_NSEC];
+        if (fe->nb == 10) npg::section_piece<10>(t, x_inv->d, b->d, i, cl, term);
+        else npg::section_piece<4>(t, x_inv->d, b->d, i, cl, term);
+        for (int k = 0; k < NPG_NSEC; ++k) terms[(size_t)k * (size_t)np + i] = term[k];
+    }
+#pragma omp parallel for schedule(static)
+    for (int64_t j = 0; j < nbin * NPG_NSEC; ++j) out->d[j] = npg::section_fold(pl.bin_ptr.data(), terms, np, j / NPG_NSEC, (int)(j % NPG_NSEC));
+    return NPG_OK;
+}
+
 // ---- the state binned into (latitude band, buoyancy class) (csrc/classes.hip on the host): the per-sample arithmetic and the edge
 // search are the SAME code (csrc/classes_core.h).  Pass 1 in fixed chunks of kClsChunk cells, folded in chunk order; pass 2 adds the
 // quantised terms as 64-bit integers (relaxed atomics on one table, a run of samples in one bin added up first): integer addition is
