@@ -652,6 +652,37 @@ int npg_forcing_info(const npg_forcing *F, int64_t *nface, int64_t *wind_slots, 
                      int64_t *matrix_slots);
 int npg_forcing_destroy(npg_forcing *F);
 
+/* ---- interior buoyancy forcing: a volume source and a sponge (new work: the reference forces the buoyancy at the boundary only) -------
+ * The volume load of d_t b' = ... + Q(x, t) + gamma(x) (b*(x, t) - b'), recomputed on the device for the time level being solved, the
+ * gamma-weighted mass matrix R of the sponge and the integrals of its budget (csrc/interior_core.h).  The handle holds
+ * the nkept KEPT cells (strictly ascending cell ids of the engine), keyframe tables [nkey][nq][nkept] per series (NPG_ITR_SOURCE: Q,
+ * NPG_ITR_TARGET: b*) at the points of the engine's own volume rule - the rule NPG_MAT_M is assembled with - and a static table gamma
+ * [nq][nkept] (>= 0).  Tables are copied; NULL removes one; every value is finite.
+ *   npg_interior_apply: the value of series c at a point is (1 - w[c]) table[key[c]] + w[c] table[key[c] + 1] (behind the last
+ *   keyframe: table[0]); w[c] = 0 reads one keyframe and returns its bits.  key and w have NPG_ITR_NSERIES entries; those of a series
+ *   that is not set are ignored.  Then
+ *       rhs_src_out[r] = int (Q + gamma (b* - b_D)) phi_r dV     on the buoyancy rows the kept cells touch, else 0
+ *   with b_D the finite-element function of the cell's Dirichlet nodal values (the Dirichlet columns of R, lifted) and Dirichlet rows
+ *   skipped.  Two launches, sums in one fixed order, no atomics: the same bits on every call.  nkept = 0 is legal: zeros.
+ *   npg_interior_matrix: R = int gamma phi_i phi_j dV on the pattern given at create (entries no kept cell touches: 0).  A position
+ *   missing in the pattern is an error of create.
+ *   npg_interior_budget: out[0 .. NPG_ITR_NBUDGET) = int dV, int Q dV, int gamma (b* - b) dV over the kept cells for the state b
+ *   (Dirichlet values included); a per-workgroup partial row and a fold in fixed order.
+ * Validation (NPG_EINVAL + message) happens before anything is launched.  The engine must outlive the handle. */
+typedef struct npg_interior npg_interior;
+#define NPG_ITR_NSERIES 2
+#define NPG_ITR_SOURCE 0
+#define NPG_ITR_TARGET 1
+#define NPG_ITR_NBUDGET 3
+int npg_interior_create(npg_fe *fe, int64_t nkept, const int32_t *cells, const npg_csr *pattern, npg_interior **out);
+int npg_interior_set_series(npg_interior *F, int which, int nkey, const double *tables);
+int npg_interior_set_gamma(npg_interior *F, const double *table);
+int npg_interior_apply(npg_interior *F, const int32_t *key, const double *w, npg_vec *rhs_src_out);
+int npg_interior_matrix(npg_interior *F, npg_csr *R);
+int npg_interior_budget(npg_interior *F, const int32_t *key, const double *w, const npg_vec *b, npg_vec *out);
+int npg_interior_info(const npg_interior *F, int64_t *nkept, int64_t *load_slots, int64_t *matrix_entries, int64_t *matrix_slots);
+int npg_interior_destroy(npg_interior *F);
+
 /* ---- time means and eddy co-moments of the running state (new work: the reference has no time averaging) ------------------------------
  * A weighted running mean of [u; p] and b and the ten co-moments uu uv uw vv vw ww ub vb wb bb of the mesh nodes, updated once per
  * time step on the device (csrc/tavg_core.h).  The handle owns the node table only: iu[3][nnode] the position of each

@@ -13,6 +13,7 @@ from .fe import DoFHandler, FEData, Mesh, Spaces, get_n_dofs
 from .inputs import (ConvectionParameterization, EddyParameterization, Forcings, Parameters, SurfaceDirichletBC,
                      SurfaceFluxBC)
 from .integrals import BudgetRecorder, Budgets, MeshIntegrals
+from .interior import InteriorForcing
 from .inversion import InversionToolkit, build_A_inversion, build_B_inversion, build_b_inversion
 from .io import save_checkpoint, save_state, save_vtk, set_out_dir, set_state_from_file
 from .iterative_solvers import BatchedCgWorkspace, CgWorkspace, Diagonal, GmresWorkspace, IterativeSolverToolkit, MgsGmresWorkspace, iterative_solve

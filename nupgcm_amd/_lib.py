@@ -167,6 +167,9 @@ def _declare(L, partial=False):
         "npg_forcing_create": [P, I64, VP, VP, VP, P, PP], "npg_forcing_destroy": [P], "npg_forcing_set_series": [P, C.c_int, C.c_int, VP],
         "npg_forcing_set_gamma": [P, VP], "npg_forcing_apply": [P, VP, VP, D, P, P, P], "npg_forcing_surface_matrix": [P, D, P],
         "npg_forcing_info": [P] + [C.POINTER(I64)] * 5, "npg_csr_axpy": [P, D, P],
+        "npg_interior_create": [P, I64, VP, P, PP], "npg_interior_destroy": [P], "npg_interior_set_series": [P, C.c_int, C.c_int, VP],
+        "npg_interior_set_gamma": [P, VP], "npg_interior_apply": [P, VP, VP, P], "npg_interior_matrix": [P, P],
+        "npg_interior_budget": [P, VP, VP, P, P], "npg_interior_info": [P] + [C.POINTER(I64)] * 4,
         "npg_tavg_create": [P, I64, I64, I64, VP, VP, PP], "npg_tavg_destroy": [P], "npg_tavg_accumulate": [P, D, D, P, P, P, P, P],
         "npg_tavg_info": [P] + [C.POINTER(I64)] * 3,
         "npg_nodal_create": [P, I64, VP, VP, C.c_int, PP], "npg_nodal_destroy": [P], "npg_nodal_compute": [P, P, P, C.c_int, P],
@@ -250,6 +253,9 @@ NPG_NBND = 24
 NPG_BND_NU, NPG_BND_KH, NPG_BND_KV, NPG_BND_TAUX, NPG_BND_TAUY, NPG_BND_FLUX = range(6)
 NPG_FRC_NSERIES = 4
 NPG_FRC_TAUX, NPG_FRC_TAUY, NPG_FRC_FLUX, NPG_FRC_TARGET = range(4)
+NPG_ITR_NSERIES = 2
+NPG_ITR_SOURCE, NPG_ITR_TARGET = range(2)
+NPG_ITR_NBUDGET = 3
 NPG_NODAL_U, NPG_NODAL_B, NPG_NODAL_P = 1, 2, 4
 NPG_NODAL_NCH = 17
 NPG_NSEC = 14

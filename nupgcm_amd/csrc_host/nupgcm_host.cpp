@@ -1673,6 +1673,139 @@ NPG_API int npg_forcing_info(const npg_forcing *F, int64_t *nface, int64_t *wind
     return NPG_OK;
 }
 
+// ---- interior buoyancy forcing (csrc/interior.hip on the host): the per-cell arithmetic, the row and entry gathers, the plan and the
+// argument checks are the SAME code (csrc/interior_core.h); every row and every entry is one thread's own sum.  The budget: fixed chunks
+// of kItrChunk kept cells give one partial row each, folded in chunk order - the sums do not depend on the number of threads. ------------
+#include "../csrc/interior_core.h"
+static_assert(NPG_ITR_NSERIES == npg::kItrNSeries, "NPG_ITR_NSERIES of the header and kItrNSeries of interior_core.h must agree");
+static_assert(NPG_ITR_NBUDGET == npg::kItrNBudget, "NPG_ITR_NBUDGET of the header and kItrNBudget of interior_core.h must agree");
+
+struct npg_interior {
+    npg_fe *fe = nullptr;
+    int64_t nkept = 0;
+    npg::ItrPlan plan;
+    int32_t nkey[npg::kItrNSeries] = {0, 0};
+    bool has_ser[npg::kItrNSeries] = {false, false}, has_gamma = false;
+    std::vector<int32_t> cell;
+    std::vector<double> ser[npg::kItrNSeries], gamma, loc, part;
+};
+static npg::ItrCells itr_cells(const npg_interior *F, const int32_t *key, const double *w) {
+    npg::ItrCells t{};
+    t.nkept = F->nkept;
+    t.nq = F->fe->nq;
+    t.cell = F->cell.data();
+    for (int c = 0; c < npg::kItrNSeries; ++c) {
+        t.ser[c] = F->has_ser[c] ? F->ser[c].data() : nullptr, t.nkey[c] = F->nkey[c];
+        t.key[c] = key && F->nkey[c] ? key[c] : 0, t.w[c] = w && F->nkey[c] ? w[c] : 0.0;
+    }
+    t.gamma = F->has_gamma ? F->gamma.data() : nullptr;
+    return t;
+}
+NPG_API int npg_interior_create(npg_fe *fe, int64_t nkept, const int32_t *cells, const npg_csr *pattern, npg_interior **out) {
+    REQUIRE(fe && out, "npg_interior_create: NULL argument");
+    REQUIRE(!pattern || pattern->ctx == fe->ctx, "npg_interior_create: the pattern must be a plain-CSR matrix of the engine's context");
+    std::unique_ptr<npg_interior> F(new npg_interior());
+    REQUIRE_OK(npg::itr_build_plan(host_view(fe), fe->n_b, nkept, cells, pattern ? pattern->m : 0, pattern ? pattern->rowptr.data() : nullptr,
+                                   pattern ? pattern->col.data() : nullptr, F->plan));
+    F->fe = fe;
+    F->nkept = nkept;
+    F->cell.assign(cells, cells + nkept);
+    F->loc.assign((size_t)fe->nb * (size_t)nkept + 1, 0.0);
+    F->part.assign((size_t)((nkept + npg::kItrChunk - 1) / npg::kItrChunk) * npg::kItrNBudget + 1, 0.0);
+    *out = F.release();
+    return NPG_OK;
+}
+NPG_API int npg_interior_destroy(npg_interior *F) {
+    delete F;
+    return NPG_OK;
+}
+NPG_API int npg_interior_set_series(npg_interior *F, int which, int nkey, const double *tables) {
+    REQUIRE_OK(npg::check_interior_set_series(F != nullptr, which, nkey, tables, F ? F->fe->nq : 0, F ? F->nkept : 0));
+    F->ser[which].assign(1, 0.0);
+    if (tables && F->nkept > 0) F->ser[which].assign(tables, tables + (size_t)nkey * F->fe->nq * (size_t)F->nkept);
+    F->has_ser[which] = tables != nullptr;
+    F->nkey[which] = tables ? nkey : 0;
+    return NPG_OK;
+}
+NPG_API int npg_interior_set_gamma(npg_interior *F, const double *table) {
+    REQUIRE_OK(npg::check_interior_set_gamma(F != nullptr, table, F ? F->fe->nq : 0, F ? F->nkept : 0));
+    F->gamma.assign(1, 0.0);
+    if (table && F->nkept > 0) F->gamma.assign(table, table + (size_t)F->fe->nq * (size_t)F->nkept);
+    F->has_gamma = table != nullptr;
+    return NPG_OK;
+}
+NPG_API int npg_interior_apply(npg_interior *F, const int32_t *key, const double *w, npg_vec *rhs_src_out) {
+    const bool all = F && rhs_src_out;
+    REQUIRE_OK(npg::check_interior_apply(all, key, w, all ? F->nkey : nullptr, all ? F->fe->n_b : 0, all ? rhs_src_out->n : 0,
+                                         all && rhs_src_out->ctx == F->fe->ctx));
+    const npg_fe *fe = F->fe;
+    const npg::ItrCells t = itr_cells(F, key, w);
+    const HostShape s = host_shape(fe);
+    const HostView v = host_view(fe);
+    const int64_t nk = F->nkept, nrow = fe->n_b;
+    double *loc = F->loc.data();
+#pragma omp parallel for schedule(static)
+    for (int64_t kc = 0; kc < nk; ++kc) {
+        if (fe->nb == 10) npg::itr_cell_load<10>(s, v, t, kc, loc);
+        else npg::itr_cell_load<4>(s, v, t, kc, loc);
+    }
+    const int32_t *ptr = F->plan.gptr.data(), *slot = F->plan.gslot.data();
+#pragma omp parallel for schedule(static)
+    for (int64_t r = 0; r < nrow; ++r) npg::itr_gather_row(r, ptr, slot, loc, rhs_src_out->d);
+    return NPG_OK;
+}
+NPG_API int npg_interior_matrix(npg_interior *F, npg_csr *R) {
+    const bool all = F && R;
+    REQUIRE_OK(npg::check_interior_matrix(all, all && F->plan.has_pattern, all && F->has_gamma,
+                                          all && R->ctx == F->fe->ctx && R->m == F->plan.pat_m && R->nnz == F->plan.pat_nnz));
+    std::fill(R->val.begin(), R->val.end(), 0.0);
+    const npg_fe *fe = F->fe;
+    const npg::ItrCells t = itr_cells(F, nullptr, nullptr);
+    const HostShape s = host_shape(fe);
+    const HostView v = host_view(fe);
+    const npg::ItrPlan &pl = F->plan;
+    const int64_t nent = (int64_t)pl.epos.size();
+#pragma omp parallel for schedule(static)
+    for (int64_t e = 0; e < nent; ++e) {
+        R->val[(size_t)pl.epos[(size_t)e]] = fe->nb == 10 ? npg::itr_matrix_entry<10>(s, v, t, pl.eptr.data(), pl.ecell.data(), pl.ecode.data(), e)
+                                                          : npg::itr_matrix_entry<4>(s, v, t, pl.eptr.data(), pl.ecell.data(), pl.ecode.data(), e);
+    }
+    return NPG_OK;
+}
+NPG_API int npg_interior_budget(npg_interior *F, const int32_t *key, const double *w, const npg_vec *b, npg_vec *out) {
+    const bool all = F && b && out;
+    REQUIRE_OK(npg::check_interior_budget(all, key, w, all ? F->nkey : nullptr, all ? F->fe->n_b : 0, all ? b->n : 0, all ? out->n : 0,
+                                          all && b->ctx == F->fe->ctx && out->ctx == F->fe->ctx));
+    const npg_fe *fe = F->fe;
+    const npg::ItrCells t = itr_cells(F, key, w);
+    const HostShape s = host_shape(fe);
+    const HostView v = host_view(fe);
+    const int64_t nk = F->nkept, nchunk = (nk + npg::kItrChunk - 1) / npg::kItrChunk;
+#pragma omp parallel for schedule(static)
+    for (int64_t k = 0; k < nchunk; ++k) {
+        double acc[npg::kItrNBudget] = {0.0, 0.0, 0.0};
+        for (int64_t kc = k * npg::kItrChunk; kc < std::min(nk, (k + 1) * npg::kItrChunk); ++kc) {
+            if (fe->nb == 10) npg::itr_cell_budget<10>(s, v, t, b->d, kc, acc);
+            else npg::itr_cell_budget<4>(s, v, t, b->d, kc, acc);
+        }
+        for (int a = 0; a < npg::kItrNBudget; ++a) F->part[(size_t)k * npg::kItrNBudget + a] = acc[a];
+    }
+    for (int a = 0; a < npg::kItrNBudget; ++a) {
+        double sum = 0.0;
+        for (int64_t k = 0; k < nchunk; ++k) sum += F->part[(size_t)k * npg::kItrNBudget + a];
+        out->d[a] = sum;
+    }
+    return NPG_OK;
+}
+NPG_API int npg_interior_info(const npg_interior *F, int64_t *nkept, int64_t *load_slots, int64_t *matrix_entries, int64_t *matrix_slots) {
+    REQUIRE(F, "npg_interior_info: NULL argument");
+    if (nkept) *nkept = F->nkept;
+    if (load_slots) *load_slots = (int64_t)F->plan.gslot.size();
+    if (matrix_entries) *matrix_entries = (int64_t)F->plan.epos.size();
+    if (matrix_slots) *matrix_slots = (int64_t)F->plan.ecell.size();
+    return NPG_OK;
+}
+
 // ---- time means and co-moments of the running state (csrc/tavg.hip on the host): the per-node and per-entry arithmetic and the argument
 // checks are the SAME code (csrc/tavg_core.h); every node and every entry is one thread's own. -------------------------------------------
 #include "../csrc/tavg_core.h"

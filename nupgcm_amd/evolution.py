@@ -50,6 +50,8 @@ class EvolutionToolkit:
         self.arch, self.fe_data, self.params, self.forcings = arch, fe_data, params, forcings
         self.first_step_lhs = first_step_lhs
         self.S = None               # the surface matrix of an attached restoring condition (forcing.SurfaceForcing): A += dt S
+        self.R = None               # the sponge's matrix int gamma phi_i phi_j (interior.InteriorForcing): A += c R, c = scheme_constant
+        self.rhs_src = None         # its unscaled volume load, p_b order, owned by the forcing: evolve() adds (c / dt) rhs_src to rhs_flux
         fe = self.fe = device_fe(arch, fe_data)
         ctx, nb = arch.ctx, fe_data.dofs.nb
         fe.set_coeff("kappa_h", forcings.kappa_h)
@@ -85,14 +87,22 @@ def _cpu_factorisation(arch, forcings, ts, A, P):
     return P
 
 
-def collect_evolution_LHS_into(A, P, params, ts, M, Kh, Kv, S=None):
-    """A = M + theta (Kh + Kv) [+ dt S]; P = Diagonal(1 ./ diag(A)) - src/evolution.jl:143-177, as two device kernels on the shared
-    pattern instead of a host sparse add + upload.  S: the surface matrix of a restoring condition (forcing.SurfaceForcing); its
-    factor dt is the one that multiplies rhs_flux in npg_fe_evolution_rhs in both schemes.  P = None: no Jacobi vector is wanted."""
+def scheme_constant(ts):
+    """c, the factor of a volume tendency in the step: dt for BDF1, 2/3 dt for BDF2 - the cdt npg_tracers_rhs puts on a tracer's source"""
+    return ts.dt if isinstance(ts, BDF1) else 2.0 / 3.0 * ts.dt
+
+
+def collect_evolution_LHS_into(A, P, params, ts, M, Kh, Kv, S=None, R=None):
+    """A = M + theta (Kh + Kv) [+ dt S] [+ c R]; P = Diagonal(1 ./ diag(A)) - src/evolution.jl:143-177, as two device kernels on the
+    shared pattern instead of a host sparse add + upload.  S: the surface matrix of a restoring condition (forcing.SurfaceForcing); its
+    factor dt is the one that multiplies rhs_flux in npg_fe_evolution_rhs in both schemes.  R: the sponge's matrix
+    (interior.InteriorForcing); its factor is scheme_constant(ts).  P = None: no Jacobi vector is wanted."""
     theta = evolution_parameter(params, ts)
     A.combine(1.0, M, theta, Kh, Kv)
     if S is not None:
         A.axpy(ts.dt, S)
+    if R is not None:
+        A.axpy(scheme_constant(ts), R)
     if P is not None:
         A.inv_diag(P.diag)
     return A, P
@@ -109,9 +119,10 @@ def lhs_timestepper(evolution: EvolutionToolkit, ts, step_index):
 def collect_evolution_LHS(evolution: EvolutionToolkit, params, forcings, ts):
     """collect_evolution_LHS! - src/evolution.jl:133-142"""
     s = evolution.solver
+    S, R = getattr(evolution, "S", None), getattr(evolution, "R", None)
     if isinstance(s.P, LU):             # CPU(): the Jacobi vector was replaced by the factorisation - combine, then factorise anew
-        collect_evolution_LHS_into(s.A, None, params, ts, evolution.M, evolution.Kh, evolution.Kv, getattr(evolution, "S", None))
+        collect_evolution_LHS_into(s.A, None, params, ts, evolution.M, evolution.Kh, evolution.Kv, S, R)
         s.P = LU(s.A)
         return evolution
-    collect_evolution_LHS_into(s.A, s.P, params, ts, evolution.M, evolution.Kh, evolution.Kv, getattr(evolution, "S", None))
+    collect_evolution_LHS_into(s.A, s.P, params, ts, evolution.M, evolution.Kh, evolution.Kv, S, R)
     return evolution

@@ -12,7 +12,8 @@ import numpy as np
 
 from . import _lib as L
 from .architectures import CPU, GPU, DeviceVector
-from .evolution import EvolutionToolkit, collect_evolution_LHS, collect_evolution_LHS_into, evolution_parameter
+from .evolution import (EvolutionToolkit, collect_evolution_LHS, collect_evolution_LHS_into, evolution_parameter, lhs_timestepper,
+                        scheme_constant)
 from .inversion import InversionToolkit, build_A_inversion, invert as invert_toolkit
 from .iterative_solvers import iterative_solve
 from .timesteppers import BDF1, BDF2, update_dt, update_t
@@ -69,6 +70,7 @@ class Model:
         self.stats = []
         self.tracers = None         # tracers.PassiveTracers(model, ...): run() steps them directly after evolve()
         self.surface_forcing = None # forcing.SurfaceForcing(model, ...): run() applies it at t_{n+1} before evolve()
+        self.interior_forcing = None  # interior.InteriorForcing(model, ...): run() applies it at t_{n+1} before evolve()
         self.averages = None        # averages.TimeAverages(model, ...): run() folds every new level into it
         self._prev = None
         self._u_view = inversion.solver.x.view(0, fe_data.dofs.nu)     # x[1:nu] = u (p_inversion = [p_u; nu + p_p])
@@ -122,9 +124,17 @@ def evolve(model: Model, x_inv_prev: DeviceVector, b_prev: DeviceVector):
         # src/model.jl:251-261 (with the S of an attached restoring condition; CPU(): a factorisation is renewed, not read as a Jacobi vector)
         collect_evolution_LHS(ev, prm, frc, ts)
     x_inv = model.inversion.solver.x
+    rhs_flux = ev.rhs_flux
+    if getattr(ev, "rhs_src", None) is not None:
+        # the volume load of an attached interior.InteriorForcing, with the constant c of the left-hand side the solver holds (the
+        # matrix just recombined above, else the step's own): npg_fe_evolution_rhs multiplies this vector by dt
+        lhs_ts = ts if frc.conv_param.is_on or ts.adaptive else lhs_timestepper(ev, ts, model.step_index)
+        if getattr(ev, "_rhs_flux_src", None) is None:
+            ev._rhs_flux_src = DeviceVector(model.arch.ctx, len(ev.rhs_flux))
+        rhs_flux = ev._rhs_flux_src.lincomb([1.0, scheme_constant(lhs_ts) / ts.dt], [ev.rhs_flux, ev.rhs_src])
     # (mesh-partitioned models: the element kernels write every local row, the solver reads the owned ones - a view)
     fe.evolution_rhs(_scheme(ts), ts.dt, prm.N2, theta, model.b_vec, b_prev, x_inv, x_inv_prev, ev.rhs_diff,
-                     ev.rhs_flux, ev.rhs_M, ev.rhs_h, ev.rhs_v, getattr(solver, "y_full", solver.y))   # src/model.jl:269-278
+                     rhs_flux, ev.rhs_M, ev.rhs_h, ev.rhs_v, getattr(solver, "y_full", solver.y))   # src/model.jl:269-278
     iterative_solve(solver)                                                                    # src/model.jl:279
     return model
 
@@ -160,6 +170,8 @@ def run(model: Model, n_info=10, n_save=float("inf"), n_plot=float("inf"), advec
             collect_evolution_LHS(model.evolution, prm, frc, ts)                                # src/model.jl:134-137
         if getattr(model, "surface_forcing", None):
             model.surface_forcing.apply(model, ts.t + ts.dt)      # both solves of the step produce level n + 1: the forcing at t_{n+1}
+        if getattr(model, "interior_forcing", None):
+            model.interior_forcing.apply(model, ts.t + ts.dt)
         pv["x_curr"].copy_from(inv_x)                                                           # src/model.jl:140-141
         pv["b_curr"].copy_from(b)
         evolve(model, pv["x_prev"], pv["b_prev"])                                               # src/model.jl:144

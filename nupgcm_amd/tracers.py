@@ -70,6 +70,9 @@ class PassiveTracers:
         if getattr(getattr(model, "surface_forcing", None), "restoring", False):
             raise NotImplementedError("PassiveTracers on a model with a restoring surface condition (SurfaceForcing(restoring=...)) is out "
                                       "of scope: the tracers share the evolution's matrix and would be restored towards 0")
+        if getattr(getattr(model, "interior_forcing", None), "restoring", False):
+            raise NotImplementedError("PassiveTracers on a model with a sponge (InteriorForcing(restoring=...)) is out of scope: the "
+                                      "tracers share the evolution's matrix and would be restored towards 0")
         self.specs = [_spec(t) for t in tracers]
         if not self.specs:
             raise ValueError("PassiveTracers: at least one tracer is needed")
