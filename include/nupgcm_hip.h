@@ -928,6 +928,32 @@ int npg_tracers_rhs(npg_tracers *T, int scheme, double dt, double theta, const n
                     const npg_vec *x_inv, const npg_vec *x_inv_prev, const npg_vec *rhs_diff1_or_null,
                     const npg_vec *flux_or_null, npg_vec *y);
 
+/* ---- isoneutral mixing of the passive tracers: the rotated diffusion tensor of the running buoyancy --------------------------------
+ * (csrc/redi_core.h).  With B = N2 z + b' in mesh coordinates, at a quadrature point
+ *    Bz+ = max(d_z B, bz_min),   S = -grad_h B / Bz+,   S <- S min(1, slope_max / |S|),
+ *    K = kappa_iso [1 0 S_x; 0 1 S_y; S_x S_y |S|^2] + kappa_v z z'.
+ * npg_tracers_set_isoneutral copies kappa_iso[nq][ncell] (the engine's [q][cell] layout; NULL switches the mode off) and allocates the
+ * three tensor tables kxz = kappa_iso S_x, kyz = kappa_iso S_y, kzz = kappa_iso |S|^2 in the same layout.
+ * npg_tracers_isoneutral_update rebuilds them from b (one launch, one lane per cell) and counts the points floored by bz_min and
+ * clipped by slope_max (per-workgroup partial counts folded in workgroup order; no atomics).
+ * npg_tracers_isoneutral_matrix assembles on the buoyancy pattern (one launch, sixteen lanes per CSR row, no atomics, the same bits on
+ * every call)
+ *    K[i][j] = sum_q w_q ( kappa_iso (g_ix g_jx + g_iy g_jy) + kxz (g_ix g_jz + g_iz g_jx) + kyz (g_iy g_jz + g_iz g_jy) + kzz g_iz g_jz ),
+ * free columns only: the Dirichlet lift is per tracer and goes through npg_tracers_rhs.  With S = 0 it adds exact zeros to the
+ * NPG_MAT_KH form.  Tables and matrix are fp64 whatever npg_fe_set_precision says.
+ * With the mode on, the second integral of npg_tracers_rhs becomes  int ( c_D phi_i + theta ( K (grad c_D + gamma_k z) ) . grad phi_i ),
+ * K with kzz + kappa_v, in every cell where the tracer has a non-zero Dirichlet value or gamma_k != 0, and theta gamma_k rhs_diff1 is
+ * NOT added (rhs_diff1 may be NULL).  npg_tracers_rhs after npg_tracers_set_isoneutral and before an update is NPG_EINVAL.
+ * Refused (NPG_EINVAL + message, before anything is launched): a non-finite or negative kappa_iso, slope_max < 0 or non-finite,
+ * bz_min <= 0 or non-finite, an embedded 2-D engine, a matrix that is not on the buoyancy pattern, a vector of the wrong length.
+ * npg_tracers_isoneutral_info: the counts of the last update, the number of points, state 0 = off, 1 = set, 2 = updated.
+ * npg_tracers_isoneutral_tables downloads the three tables ([nq][ncell] each) of the last update. */
+int npg_tracers_set_isoneutral(npg_tracers *T, const double *kappa_iso_or_null, double slope_max, double bz_min);
+int npg_tracers_isoneutral_update(npg_tracers *T, double N2, const npg_vec *b);
+int npg_tracers_isoneutral_matrix(npg_tracers *T, npg_csr *K);
+int npg_tracers_isoneutral_info(npg_tracers *T, int64_t *nfloored, int64_t *nclipped, int64_t *npoints, int *state);
+int npg_tracers_isoneutral_tables(npg_tracers *T, double *kxz, double *kyz, double *kzz);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (new work: the reference is single-device) ----------------- */
 #define NPG_UNIQUE_ID_BYTES 128
 int npg_comm_unique_id(void *id128);                                  /* rank 0 makes it, the launcher broadcasts it */

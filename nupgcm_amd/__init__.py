@@ -27,7 +27,7 @@ from .sampling import (GridDiagnostics, GridIntegrals, GridSamples, Located, Poi
 from .sections import Section, SectionFluxes, SectionMaps, SectionRecorder, SectionTransports
 from .surfaces import BuoyancySurfaces, SurfaceMaps, SurfaceRecorder, column_depth
 from .timesteppers import BDF1, BDF2, update_dt, update_t
-from .tracers import PassiveTracers, TracerSpec
+from .tracers import Isoneutral, PassiveTracers, TracerSpec
 from .watermass import BuoyancyClasses, ClassRecorder, ClassTable, MixingTable
 
 __all__ = [n for n in dir() if not n.startswith("_")]

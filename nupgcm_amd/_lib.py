@@ -192,6 +192,9 @@ def _declare(L, partial=False):
         "npg_surfaces_compute": [P, P, P, D, VP, C.c_int, P, P],
         "npg_tracers_create": [P, C.c_int, PP], "npg_tracers_destroy": [P], "npg_tracers_set": [P, C.c_int, VP, D, D],
         "npg_tracers_rhs": [P, C.c_int, D, D, P, P, P, P, P, P, P],
+        "npg_tracers_set_isoneutral": [P, VP, D, D], "npg_tracers_isoneutral_update": [P, D, P], "npg_tracers_isoneutral_matrix": [P, P],
+        "npg_tracers_isoneutral_info": [P, C.POINTER(I64), C.POINTER(I64), C.POINTER(I64), C.POINTER(C.c_int)],
+        "npg_tracers_isoneutral_tables": [P, VP, VP, VP],
         "npg_comm_unique_id": [VP], "npg_comm_init": [P, VP, C.c_int, C.c_int],
         "npg_comm_allreduce_sum": [P, C.POINTER(D), C.c_int], "npg_comm_info": [P, C.c_char_p, C.c_size_t], "npg_comm_disable_peer": [P], "npg_comm_allreduce_vec": [P, P],
         "npg_comm_allgather_segments": [P, P, C.c_int, VP, VP, VP, VP, P],
@@ -264,4 +267,5 @@ NPG_NCLS = 8
 NPG_NMIX = 8
 NPG_NSURF = 9
 NPG_CG_MULTI_MAX = 32
+NPG_REDI_OFF, NPG_REDI_SET, NPG_REDI_UPDATED = range(3)
 NPG_MAT_M, NPG_MAT_KH, NPG_MAT_KV, NPG_MAT_A, NPG_MAT_B = 1, 2, 3, 4, 5

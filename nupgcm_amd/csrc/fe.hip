@@ -140,35 +140,7 @@ __global__ void __launch_bounds__(kBlock) k_gather_rows(const int64_t *gptr, con
     }
 }
 
-// ---- matrix assembly ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int64_t csr_slot(const int64_t *rowptr, const int32_t *col, int32_t row, int32_t c) {
-    int64_t lo = rowptr[row], hi = rowptr[row + 1] - 1;
-    while (lo <= hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        const int32_t v = col[mid];
-        if (v == c) return mid;
-        if (v < c) lo = mid + 1; else hi = mid - 1;
-    }
-    return -1;
-}
-
-// a row owner adds into its own row: no atomic, contributions arrive in the fixed order of its adjacency list
-__device__ __forceinline__ void row_add(const int64_t *rowptr, const int32_t *col, double *val, int32_t row, int32_t c,
-                                        double v, int *missing) {
-    const int64_t s = csr_slot(rowptr, col, row, c);
-    if (s >= 0) val[s] += v;
-    else if (v != 0.0) atomicAdd(missing, 1);    // a numerically non-zero entry outside the pattern is an error
-}
-
-// physical gradient of buoyancy basis function i at quadrature point q
-template <typename R, int NB>
-__device__ __forceinline__ void grad_b(const FeTablesT<R> &t, const R *G, int q, int i, R &gx, R &gy, R &gz) {
-    const R *dn = &t.dNb[(q * NB + i) * 4];
-    gx = dn[0] * G[0] + dn[1] * G[3] + dn[2] * G[6] + dn[3] * G[9];
-    gy = dn[0] * G[1] + dn[1] * G[4] + dn[2] * G[7] + dn[3] * G[10];
-    gz = dn[0] * G[2] + dn[1] * G[5] + dn[2] * G[8] + dn[3] * G[11];
-}
-
+// ---- matrix assembly (csr_slot, row_add, grad_b: fe_dev.h) ---------------------------------------------------------------
 template <typename R>
 __device__ __forceinline__ void grad_u(const FeTablesT<R> &t, const R *G, int q, int i, R &gx, R &gy, R &gz) {
     const R *dn = &t.dN2[(q * 10 + i) * 4];
@@ -182,7 +154,7 @@ __device__ __forceinline__ void grad_u(const FeTablesT<R> &t, const R *G, int q,
 // for each pair every lane evaluates its quadrature point's share of the local row, the shares are summed over the lanes in
 // the fixed order of the DPP tree, and the sums go into the group's own CSR row (slots by binary search) - no atomics, the
 // same bits on every run.  The three component rows of a velocity node repeat the friction integral: a set-up cost.
-constexpr int kQL = 16;      // lanes per row = kMaxQ
+// (kQL = 16 lanes per row: fe_dev.h)
 
 // M / Kh / Kv: rows = buoyancy DoFs; gptr / gidx = the inverted index of the vector assembly (i * ncell + cell)
 template <typename R, int NB>

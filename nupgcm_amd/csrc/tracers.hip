@@ -9,11 +9,20 @@
 //                           keep 3 nq columns of doubles beside the staged tables within 64 KiB; no instance uses scratch.
 //   k_tracers_gather        pass 2, one thread per (tracer, row): the row's local entries through the engine's inverted index in cell
 //                           order, + theta Gamma_k rhs_diff1[r] + dt flux_k[r].  No atomics: the same bits on every call.
+// Isoneutral mixing (npg_tracers_set_isoneutral, redi_core.h): the tracers' own rotated diffusion tensor.
+//   k_redi_update<NB>       one lane per cell, shape tables in LDS as k_coeff_from_bz: grad B at the cell's quadrature points, the floor
+//                           and the clip, the three tensor tables, and the workgroup's floored / clipped counts (wave sums folded in
+//                           wave order: no atomics).
+//   k_redi_matrix<NB>       K_iso on the buoyancy pattern with the skeleton of k_assemble_b: sixteen lanes own a CSR row, lane =
+//                           quadrature point, the row's (cell, local DoF) pairs in cell order, the DPP tree, row_add.  fp64 always.
+//   k_tracers_local_iso     pass 1 with the rotated tensor in the second integral (cell_tracers<R, NB, true>); the instances of
+//                           k_tracers_local are not touched by the flag.
 #include <cmath>
 
 #include "common.h"
 #include "device_utils.h"
 #include "fe_dev.h"
+#include "redi_core.h"
 #include "tracers_core.h"
 
 static_assert(npg::kTrMaxQ == npg::kMaxQ, "a lane column holds the engine's largest rule");
@@ -40,6 +49,95 @@ __global__ void __launch_bounds__(kTrBlock) __attribute__((amdgpu_waves_per_eu(2
     const TracerCells<DevCells> cells{cell_view(d)};
     LaneColumn<R> uq{reinterpret_cast<R *>(uq_lds) + threadIdx.x};
     cell_tracers<R, NB>(t, cells, uq, d.nq, bdf2 != 0, dt, theta, xi, xip, ts, cell);
+}
+
+// the mode's tables, [nq][ncell] each
+struct RediDev {
+    const double *kiso, *kxz, *kyz, *kzz;
+};
+
+template <typename R, int NB>
+__global__ void __launch_bounds__(kTrBlock) __attribute__((amdgpu_waves_per_eu(2))) k_tracers_local_iso(FeDev d, RediDev rd, int bdf2, double dt, double theta,
+                                                              const double *xi, const double *xip, TracerSet ts) {
+    __shared__ FeTablesT<R> t;
+    stage_tables(d, t);
+    extern __shared__ double uq_lds[];
+    const int64_t cell = blockIdx.x * (int64_t)kTrBlock + threadIdx.x;
+    if (cell >= d.ncell) return;
+    const RediCells<DevCells> cells{cell_view(d), rd.kiso, rd.kxz, rd.kyz, rd.kzz};
+    LaneColumn<R> uq{reinterpret_cast<R *>(uq_lds) + threadIdx.x};
+    cell_tracers<R, NB, true>(t, cells, uq, d.nq, bdf2 != 0, dt, theta, xi, xip, ts, cell);
+}
+
+// counts[2 blockIdx.x + {0, 1}] = the workgroup's floored / clipped points
+template <int NB>
+__global__ void __launch_bounds__(kBlock) k_redi_update(FeDev d, double N2, const double *b, const double *kiso, double slope_max, double bz_min,
+                                                        double *kxz, double *kyz, double *kzz, int32_t *counts) {
+    __shared__ FeTables t;
+    __shared__ int32_t shc[2 * (kBlock / kWave)];
+    stage_tables(d, t);
+    const int64_t cell = blockIdx.x * (int64_t)kBlock + threadIdx.x;
+    int nfloor = 0, nclip = 0;
+    if (cell < d.ncell) cell_redi_update<NB>(t, cell_view(d), d.nq, N2, b, kiso, slope_max, bz_min, cell, kxz, kyz, kzz, nfloor, nclip);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        nfloor += __shfl_xor(nfloor, off, kWave);
+        nclip += __shfl_xor(nclip, off, kWave);
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) shc[2 * (threadIdx.x / kWave)] = nfloor, shc[2 * (threadIdx.x / kWave) + 1] = nclip;
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        int32_t s = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) s += shc[2 * w + threadIdx.x];
+        counts[2 * (size_t)blockIdx.x + threadIdx.x] = s;
+    }
+}
+
+template <int NB>
+__global__ void __launch_bounds__(kBlock) k_redi_matrix(FeDev d, RediDev rd, const int64_t *gptr, const int32_t *gidx, int64_t nrows,
+                                                        const int64_t *rowptr, const int32_t *col, double *val, int *missing) {
+    __shared__ FeTables t;
+    stage_tables(d, t);
+    const int64_t r = (blockIdx.x * (int64_t)kBlock + threadIdx.x) / kQL;
+    const int q = threadIdx.x % kQL;
+    if (r >= nrows) return;                                  // whole lane groups leave together
+    const int32_t row = (int32_t)r;
+    const bool on = q < d.nq;
+    for (int64_t k = gptr[r]; k < gptr[r + 1]; ++k) {
+        const int64_t cell = gidx[k] % d.ncell;
+        const int i = (int)(gidx[k] / d.ncell);
+        double acc[NB];
+#pragma unroll
+        for (int j = 0; j < NB; ++j) acc[j] = 0.0;
+        if (on) {
+            const double w = t.qw[q] * d.wdet[cell];
+            const size_t o = (size_t)q * d.ncell + cell;
+            const double ki = rd.kiso[o], kxz = rd.kxz[o], kyz = rd.kyz[o], kzz = rd.kzz[o];
+            double G[12];
+#pragma unroll
+            for (int e = 0; e < 12; ++e) G[e] = d.G[(size_t)e * d.ncell + cell];
+            double gix, giy, giz;
+            grad_b<double, NB>(t, G, q, i, gix, giy, giz);
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+                double gx, gy, gz;
+                grad_b<double, NB>(t, G, q, j, gx, gy, gz);
+                acc[j] = redi_entry(w, ki, kxz, kyz, kzz, gix, giy, giz, gx, gy, gz);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NB; ++j) acc[j] = group_sum_dpp<kQL>(acc[j]);
+        // lane j adds column j; Dirichlet columns are skipped (their lift is per tracer: the right-hand side)
+        double mine = 0.0;
+#pragma unroll
+        for (int j = 0; j < NB; ++j) mine = (q == j) ? acc[j] : mine;
+        if (q < NB) {
+            const int32_t c = d.cb[(size_t)q * d.ncell + cell];
+            if (c >= 0) row_add(rowptr, col, val, row, c, mine, missing);
+        }
+        __builtin_amdgcn_s_waitcnt(0);                       // this cell's stores are out before the next cell's loads
+    }
 }
 
 // out[k][r], k = blockIdx.y
@@ -69,7 +167,128 @@ struct npg_tracers {
     DevBuf<double> source;           // [ntracer]
     std::vector<double> h_gamma;
     std::vector<uint8_t> h_lift;     // tracer k has a non-zero Dirichlet value
+    // isoneutral mixing (npg_tracers_set_isoneutral): kappa_iso and the tensor tables [nq][ncell], the update's per-workgroup counts
+    int iso = kRediOff;
+    double slope_max = 0.0, bz_min = 0.0;
+    DevBuf<double> kiso, kxz, kyz, kzz;
+    DevBuf<int32_t> counts;          // [2 iso_grid]
+    DevBuf<int> missing;
+    int iso_grid = 0;
 };
+
+static bool engine_is_flat(const npg_fe *fe, int *rc) {   // an embedded 2-D engine pads its triangles to tetrahedra: N1[q][3] = 0
+    std::vector<double> n1((size_t)fe->d.nq * 4);
+    *rc = hipMemcpy(n1.data(), fe->d.N1, n1.size() * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess ? NPG_OK : NPG_EHIP;
+    bool flat = true;
+    for (int q = 0; q < fe->d.nq; ++q) flat = flat && n1[(size_t)q * 4 + 3] == 0.0;
+    return flat;
+}
+
+NPG_API int npg_tracers_set_isoneutral(npg_tracers *T, const double *kappa_iso_or_null, double slope_max, double bz_min) {
+    NPG_REQUIRE(T, "npg_tracers_set_isoneutral: NULL handle");
+    npg_fe *fe = T->fe;
+    NPG_HIP(hipSetDevice(T->ctx->device));
+    const size_t npts = (size_t)fe->d.nq * fe->d.ncell;
+    RediCheck a{"npg_tracers_set_isoneutral"};
+    a.set = true, a.kiso = kappa_iso_or_null, a.npts = (int64_t)npts, a.slope_max = slope_max, a.bz_min = bz_min;
+    int rc = NPG_OK;
+    a.flat = engine_is_flat(fe, &rc);
+    NPG_REQUIRE(rc == NPG_OK, "npg_tracers_set_isoneutral: reading the engine's shape tables failed");
+    NPG_REQUIRE_OK(check_redi(a));
+    NPG_HIP(hipStreamSynchronize(T->ctx->stream));          // kernels that read the tables run on ctx->stream
+    if (!kappa_iso_or_null) {
+        T->iso = kRediOff;
+        T->kiso.reset(), T->kxz.reset(), T->kyz.reset(), T->kzz.reset(), T->counts.reset(), T->missing.reset();
+        return NPG_OK;
+    }
+    T->iso_grid = (int)((fe->d.ncell + kBlock - 1) / kBlock);
+    NPG_HIP(T->kiso.upload(kappa_iso_or_null, npts));       // [nq][ncell]: the engine's own [q][cell] layout
+    NPG_HIP(T->kxz.zeros(npts));
+    NPG_HIP(T->kyz.zeros(npts));
+    NPG_HIP(T->kzz.zeros(npts));
+    NPG_HIP(T->counts.zeros((size_t)2 * T->iso_grid));
+    NPG_HIP(T->missing.zeros(1));
+    T->slope_max = slope_max, T->bz_min = bz_min;
+    T->iso = kRediSet;
+    return NPG_OK;
+}
+
+NPG_API int npg_tracers_isoneutral_update(npg_tracers *T, double N2, const npg_vec *b) {
+    NPG_REQUIRE(T && b, "npg_tracers_isoneutral_update: NULL argument");
+    npg_fe *fe = T->fe;
+    RediCheck a{"npg_tracers_isoneutral_update"};
+    a.need = kRediSet, a.state = T->iso, a.n_b = fe->n_b, a.vec_n = b->n, a.N2 = N2;
+    NPG_REQUIRE_OK(check_redi(a));
+    NPG_REQUIRE(b->ctx == fe->ctx, "npg_tracers_isoneutral_update: arguments of different contexts");
+    NPG_HIP(hipSetDevice(T->ctx->device));
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(T->iso_grid), dim3(kBlock), 0, T->ctx->stream, fe->d, N2, b->d, T->kiso, T->slope_max, T->bz_min,
+                           T->kxz, T->kyz, T->kzz, T->counts);
+    };
+    fe->d.nb == 10 ? go(k_redi_update<10>) : go(k_redi_update<4>);
+    NPG_HIP(hipGetLastError());
+    T->iso = kRediUpdated;
+    return NPG_OK;
+}
+
+NPG_API int npg_tracers_isoneutral_matrix(npg_tracers *T, npg_csr *K) {
+    NPG_REQUIRE(T && K, "npg_tracers_isoneutral_matrix: NULL argument");
+    npg_fe *fe = T->fe;
+    RediCheck a{"npg_tracers_isoneutral_matrix"};
+    a.need = kRediUpdated, a.state = T->iso, a.n_b = fe->n_b, a.mat_m = K->m, a.mat_n = K->n;
+    a.mat_plain = K->nnode() == 0 && K->lb.nblocks == 0 && !K->uperm;
+    NPG_REQUIRE_OK(check_redi(a));
+    NPG_REQUIRE(K->ctx == fe->ctx, "npg_tracers_isoneutral_matrix: arguments of different contexts");
+    NPG_HIP(hipSetDevice(T->ctx->device));
+    hipStream_t st = T->ctx->stream;
+    const FeDev &d = fe->d;
+    NPG_HIP(hipMemsetAsync(K->val, 0, (size_t)K->nnz * sizeof(double), st));
+    NPG_HIP(hipMemsetAsync(T->missing, 0, sizeof(int), st));
+    const RediDev rd{T->kiso, T->kxz, T->kyz, T->kzz};
+    const int grid = (int)((K->m * kQL + kBlock - 1) / kBlock);
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, st, d, rd, fe->gptr, fe->gidx, K->m, K->rowptr, K->col, K->val, T->missing);
+    };
+    d.nb == 10 ? go(k_redi_matrix<10>) : go(k_redi_matrix<4>);
+    NPG_HIP(hipGetLastError());
+    int miss = 0;
+    NPG_HIP(hipMemcpyAsync(&miss, T->missing, sizeof(int), hipMemcpyDeviceToHost, st));
+    NPG_HIP(hipStreamSynchronize(st));
+    NPG_REQUIRE(miss == 0, "npg_tracers_isoneutral_matrix: %d non-zero local entries fall outside the matrix's pattern: it is not the buoyancy pattern",
+                miss);
+    return csr_repack(K);
+}
+
+NPG_API int npg_tracers_isoneutral_tables(npg_tracers *T, double *kxz, double *kyz, double *kzz) {
+    NPG_REQUIRE(T && kxz && kyz && kzz, "npg_tracers_isoneutral_tables: NULL argument");
+    RediCheck a{"npg_tracers_isoneutral_tables"};
+    a.need = kRediUpdated, a.state = T->iso;
+    NPG_REQUIRE_OK(check_redi(a));
+    NPG_HIP(hipSetDevice(T->ctx->device));
+    NPG_HIP(hipStreamSynchronize(T->ctx->stream));
+    const size_t bytes = (size_t)T->fe->d.nq * T->fe->d.ncell * sizeof(double);
+    NPG_HIP(hipMemcpy(kxz, T->kxz, bytes, hipMemcpyDeviceToHost));
+    NPG_HIP(hipMemcpy(kyz, T->kyz, bytes, hipMemcpyDeviceToHost));
+    NPG_HIP(hipMemcpy(kzz, T->kzz, bytes, hipMemcpyDeviceToHost));
+    return NPG_OK;
+}
+
+NPG_API int npg_tracers_isoneutral_info(npg_tracers *T, int64_t *nfloored, int64_t *nclipped, int64_t *npoints, int *state) {
+    NPG_REQUIRE(T, "npg_tracers_isoneutral_info: NULL handle");
+    int64_t nf = 0, ncl = 0;
+    if (T->iso == kRediUpdated) {
+        NPG_HIP(hipSetDevice(T->ctx->device));
+        std::vector<int32_t> h((size_t)2 * T->iso_grid);
+        NPG_HIP(hipStreamSynchronize(T->ctx->stream));
+        NPG_HIP(hipMemcpy(h.data(), T->counts, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int g = 0; g < T->iso_grid; ++g) nf += h[(size_t)2 * g], ncl += h[(size_t)2 * g + 1];      // workgroup order
+    }
+    if (nfloored) *nfloored = nf;
+    if (nclipped) *nclipped = ncl;
+    if (npoints) *npoints = T->iso == kRediOff ? 0 : (int64_t)T->fe->d.nq * T->fe->d.ncell;
+    if (state) *state = T->iso;
+    return NPG_OK;
+}
 
 NPG_API int npg_tracers_destroy(npg_tracers *T) {
     if (!T) return NPG_OK;
@@ -140,13 +359,19 @@ NPG_API int npg_tracers_rhs(npg_tracers *T, int scheme, double dt, double theta,
     NPG_REQUIRE(!rhs_diff1_or_null || rhs_diff1_or_null->n == nb, "npg_tracers_rhs: rhs_diff1 must have n_b = %lld entries", (long long)nb);
     NPG_REQUIRE(!flux_or_null || flux_or_null->n == K * nb, "npg_tracers_rhs: flux must have ntracer * n_b = %lld entries",
                 (long long)(K * nb));
+    const bool iso = T->iso != kRediOff;
+    if (iso) {
+        RediCheck a{"npg_tracers_rhs"};
+        a.need = kRediUpdated, a.state = T->iso;
+        NPG_REQUIRE_OK(check_redi(a));
+    }
     bool lift = false;
     for (int k = 0; k < K; ++k) {
-        NPG_REQUIRE(T->h_gamma[(size_t)k] == 0.0 || rhs_diff1_or_null,
+        NPG_REQUIRE(iso || T->h_gamma[(size_t)k] == 0.0 || rhs_diff1_or_null,
                     "npg_tracers_rhs: tracer %d has a background gradient (gamma = %g) but rhs_diff1 is NULL", k, T->h_gamma[(size_t)k]);
-        lift = lift || T->h_lift[(size_t)k];
+        lift = lift || T->h_lift[(size_t)k] || (iso && T->h_gamma[(size_t)k] != 0.0);
     }
-    NPG_REQUIRE(!lift || (fe->d.kh && fe->d.kv),
+    NPG_REQUIRE(!lift || ((iso || fe->d.kh) && fe->d.kv),
                 "npg_tracers_rhs: a tracer has non-zero Dirichlet values but the coefficients kappa_h / kappa_v have not been set");
     for (const npg_vec *v : {c, c_prev, x_inv, x_inv_prev, rhs_diff1_or_null, flux_or_null, (const npg_vec *)y})
         NPG_REQUIRE(!v || v->ctx == fe->ctx, "npg_tracers_rhs: arguments of different contexts");
@@ -160,12 +385,20 @@ NPG_API int npg_tracers_rhs(npg_tracers *T, int scheme, double dt, double theta,
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kTrBlock), lds, st, d, (int)(scheme == NPG_BDF2), dt, theta, x_inv->d, x_inv_prev->d, ts);
     };
-    if (d.nb == 10) f32 ? go(k_tracers_local<float, 10>) : go(k_tracers_local<double, 10>);
+    const RediDev rd{T->kiso, T->kxz, T->kyz, T->kzz};
+    auto go_iso = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kTrBlock), lds, st, d, rd, (int)(scheme == NPG_BDF2), dt, theta, x_inv->d, x_inv_prev->d, ts);
+    };
+    if (iso) {
+        if (d.nb == 10) f32 ? go_iso(k_tracers_local_iso<float, 10>) : go_iso(k_tracers_local_iso<double, 10>);
+        else f32 ? go_iso(k_tracers_local_iso<float, 4>) : go_iso(k_tracers_local_iso<double, 4>);
+    } else if (d.nb == 10) f32 ? go(k_tracers_local<float, 10>) : go(k_tracers_local<double, 10>);
     else f32 ? go(k_tracers_local<float, 4>) : go(k_tracers_local<double, 4>);
     NPG_HIP(hipGetLastError());
     const int ggrid = (int)std::min<int64_t>(2048, (nb + kBlock - 1) / kBlock);
+    // (the mode on: the background gradient's diffusion went through the rotated tensor in pass 1; rhs_diff1 is not added)
     hipLaunchKernelGGL(k_tracers_gather, dim3(ggrid, K), dim3(kBlock), 0, st, fe->gptr, fe->gidx, nb, ts, theta, dt,
-                       rhs_diff1_or_null ? rhs_diff1_or_null->d : nullptr, flux_or_null ? flux_or_null->d : nullptr, y->d);
+                       rhs_diff1_or_null && !iso ? rhs_diff1_or_null->d : nullptr, flux_or_null ? flux_or_null->d : nullptr, y->d);
     NPG_HIP(hipGetLastError());
     return NPG_OK;
 }

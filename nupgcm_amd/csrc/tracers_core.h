@@ -50,7 +50,11 @@ struct TracerCells : View {
     NPG_HD size_t loc(int i, int64_t c) const { return this->at(i, this->nb, c); }
 };
 
-template <typename R, int NB, class S, class T, class U>
+// ISO (npg_tracers_set_isoneutral, redi_core.h): T is a RediCells view and the second integral becomes
+//    int ( c_D phi_i + theta ( K (grad c_D + Gamma_k z) ) . grad phi_i ),      K = the rotated tensor with kzz + kappa_v,
+// evaluated in every cell where the tracer has a non-zero Dirichlet value or Gamma_k != 0.  ISO = false: the instances are what they
+// were before the flag existed.
+template <typename R, int NB, bool ISO = false, class S, class T, class U>
 NPG_HD void cell_tracers(const S &s, const T &t, U &uq, int nq, bool bdf2, double dt, double theta, const double *xi, const double *xip,
                          const TracerSet &ts, int64_t c) {
     const double c1 = bdf2 ? 4.0 / 3.0 : 1.0, c2 = bdf2 ? -1.0 / 3.0 : 0.0, e1 = bdf2 ? 2.0 : 1.0, e2 = bdf2 ? -1.0 : 0.0;
@@ -112,7 +116,7 @@ NPG_UNROLL
 NPG_UNROLL
             for (int i = 0; i < NB; ++i) acc[i] += (double)(wq * s.Nb[q * NB + i]);
         }
-        if (lift) {
+        if (lift || (ISO && gam != (R)0)) {
             R cd[NB];
 NPG_UNROLL
             for (int i = 0; i < NB; ++i) {
@@ -131,10 +135,21 @@ NPG_UNROLL
                     gl3 += dn[3] * cd[i];
                 }
                 const R w = s.qw[q] * wdet;
-                const R kh = rth * (R)t.kh(q, c), kv = rth * (R)t.kv(q, c);
-                const R ax = kh * (gl0 * G[0] + gl1 * G[3] + gl2 * G[6] + gl3 * G[9]);
-                const R ay = kh * (gl0 * G[1] + gl1 * G[4] + gl2 * G[7] + gl3 * G[10]);
-                const R az = kv * (gl0 * G[2] + gl1 * G[5] + gl2 * G[8] + gl3 * G[11]);
+                R ax, ay, az;
+                if constexpr (ISO) {
+                    const R ki = (R)t.kiso(q, c), kxz = (R)t.kxz(q, c), kyz = (R)t.kyz(q, c), kzz = (R)t.kzz(q, c) + (R)t.kv(q, c);
+                    const R gx = gl0 * G[0] + gl1 * G[3] + gl2 * G[6] + gl3 * G[9];
+                    const R gy = gl0 * G[1] + gl1 * G[4] + gl2 * G[7] + gl3 * G[10];
+                    const R gz = (gl0 * G[2] + gl1 * G[5] + gl2 * G[8] + gl3 * G[11]) + gam;
+                    ax = rth * (ki * gx + kxz * gz);
+                    ay = rth * (ki * gy + kyz * gz);
+                    az = rth * ((kxz * gx + kyz * gy) + kzz * gz);
+                } else {
+                    const R kh = rth * (R)t.kh(q, c), kv = rth * (R)t.kv(q, c);
+                    ax = kh * (gl0 * G[0] + gl1 * G[3] + gl2 * G[6] + gl3 * G[9]);
+                    ay = kh * (gl0 * G[1] + gl1 * G[4] + gl2 * G[7] + gl3 * G[10]);
+                    az = kv * (gl0 * G[2] + gl1 * G[5] + gl2 * G[8] + gl3 * G[11]);
+                }
 NPG_UNROLL
                 for (int i = 0; i < NB; ++i) {
                     const R *dn = &s.dNb[(q * NB + i) * 4];

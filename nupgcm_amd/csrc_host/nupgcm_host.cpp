@@ -2469,6 +2469,7 @@ NPG_API int npg_surfaces_compute(npg_surfaces *S, const npg_vec *x_inv, const np
 
 // ---- passive tracers carried by the flow (csrc/tracers.hip on the host): the per-cell arithmetic is the SAME code
 // (csrc/tracers_core.h); pass 2 walks the engine's inverted index in cell order, as gather_rows does. ----------------------------------
+#include "../csrc/redi_core.h"
 #include "../csrc/tracers_core.h"
 
 struct npg_tracers {
@@ -2477,6 +2478,11 @@ struct npg_tracers {
     int64_t n_diri = 0;
     std::vector<double> loc, diri, gamma, source;        // [K][ncell][nb], [K][n_diri], [K], [K]
     std::vector<uint8_t> lift;
+    // isoneutral mixing (csrc/redi_core.h): kappa_iso and the tensor tables [ncell][nq], the counts of the last update
+    int iso = npg::kRediOff;
+    double slope_max = 0.0, bz_min = 0.0;
+    std::vector<double> kiso, kxz, kyz, kzz;
+    int64_t nfloor = 0, nclip = 0;
 };
 namespace {
 struct HostTrVel {       // a cell's velocities at the quadrature points
@@ -2537,29 +2543,152 @@ NPG_API int npg_tracers_rhs(npg_tracers *T, int scheme, double dt, double theta,
             (long long)fe->n_inv);
     REQUIRE(!rhs_diff1_or_null || rhs_diff1_or_null->n == nb, "npg_tracers_rhs: rhs_diff1 must have n_b = %lld entries", (long long)nb);
     REQUIRE(!flux_or_null || flux_or_null->n == K * nb, "npg_tracers_rhs: flux must have ntracer * n_b = %lld entries", (long long)(K * nb));
+    const bool iso = T->iso != npg::kRediOff;
+    if (iso) {
+        npg::RediCheck a{"npg_tracers_rhs"};
+        a.need = npg::kRediUpdated, a.state = T->iso;
+        REQUIRE_OK(npg::check_redi(a));
+    }
     bool lift = false;
     for (int k = 0; k < K; ++k) {
-        REQUIRE(T->gamma[(size_t)k] == 0.0 || rhs_diff1_or_null,
+        REQUIRE(iso || T->gamma[(size_t)k] == 0.0 || rhs_diff1_or_null,
                 "npg_tracers_rhs: tracer %d has a background gradient (gamma = %g) but rhs_diff1 is NULL", k, T->gamma[(size_t)k]);
-        lift = lift || T->lift[(size_t)k];
+        lift = lift || T->lift[(size_t)k] || (iso && T->gamma[(size_t)k] != 0.0);
     }
-    REQUIRE(!lift || (!fe->coef[1].empty() && !fe->coef[2].empty()),
+    REQUIRE(!lift || ((iso || !fe->coef[1].empty()) && !fe->coef[2].empty()),
             "npg_tracers_rhs: a tracer has non-zero Dirichlet values but the coefficients kappa_h / kappa_v have not been set");
     const HostShape s = host_shape(fe);
     const npg::TracerCells<HostView> t{host_view(fe)};
+    const npg::RediCells<HostView> ti{host_view(fe), T->kiso.data(), T->kxz.data(), T->kyz.data(), T->kzz.data()};
     const npg::TracerSet ts{K, nb, T->n_diri, nc * fe->nb, c->d, c_prev->d, T->diri.data(), T->gamma.data(), T->source.data(), T->loc.data()};
     const bool bdf2 = scheme == NPG_BDF2;
 #pragma omp parallel for schedule(static)
     for (int64_t cell = 0; cell < nc; ++cell) {
         HostTrVel uq;
-        if (fe->nb == 10) npg::cell_tracers<double, 10>(s, t, uq, fe->nq, bdf2, dt, theta, x_inv->d, x_inv_prev->d, ts, cell);
+        if (iso) {
+            if (fe->nb == 10) npg::cell_tracers<double, 10, true>(s, ti, uq, fe->nq, bdf2, dt, theta, x_inv->d, x_inv_prev->d, ts, cell);
+            else npg::cell_tracers<double, 4, true>(s, ti, uq, fe->nq, bdf2, dt, theta, x_inv->d, x_inv_prev->d, ts, cell);
+        } else if (fe->nb == 10) npg::cell_tracers<double, 10>(s, t, uq, fe->nq, bdf2, dt, theta, x_inv->d, x_inv_prev->d, ts, cell);
         else npg::cell_tracers<double, 4>(s, t, uq, fe->nq, bdf2, dt, theta, x_inv->d, x_inv_prev->d, ts, cell);
     }
 #pragma omp parallel for schedule(static) collapse(2)
     for (int k = 0; k < K; ++k)
         for (int64_t r = 0; r < nb; ++r)
             y->d[(size_t)k * nb + r] = npg::tracer_row(fe->gptr.data(), fe->gidx.data(), T->loc.data() + (size_t)k * ts.loc_stride, r,
-                                                       theta * T->gamma[(size_t)k], dt, rhs_diff1_or_null ? rhs_diff1_or_null->d : nullptr,
+                                                       theta * T->gamma[(size_t)k], dt, rhs_diff1_or_null && !iso ? rhs_diff1_or_null->d : nullptr,
                                                        flux_or_null ? flux_or_null->d + (size_t)k * nb : nullptr);
+    return NPG_OK;
+}
+
+// ---- isoneutral mixing of the tracers (csrc/tracers.hip on the host; the arithmetic is csrc/redi_core.h) ------------------------------
+NPG_API int npg_tracers_set_isoneutral(npg_tracers *T, const double *kappa_iso_or_null, double slope_max, double bz_min) {
+    REQUIRE(T, "npg_tracers_set_isoneutral: NULL handle");
+    npg_fe *fe = T->fe;
+    const int64_t nc = fe->ncell;
+    const int nq = fe->nq;
+    npg::RediCheck a{"npg_tracers_set_isoneutral"};
+    a.set = true, a.kiso = kappa_iso_or_null, a.npts = nc * nq, a.slope_max = slope_max, a.bz_min = bz_min;
+    a.flat = true;
+    for (int q = 0; q < nq; ++q) a.flat = a.flat && fe->N1[(size_t)q * 4 + 3] == 0.0;
+    REQUIRE_OK(npg::check_redi(a));
+    if (!kappa_iso_or_null) {
+        T->iso = npg::kRediOff;
+        T->kiso.clear(), T->kxz.clear(), T->kyz.clear(), T->kzz.clear();
+        return NPG_OK;
+    }
+    T->kiso.resize((size_t)nc * nq);
+    for (int64_t c = 0; c < nc; ++c)                       // [nq][ncell] -> the host tables' [cell][q]
+        for (int q = 0; q < nq; ++q) T->kiso[(size_t)c * nq + q] = kappa_iso_or_null[(size_t)q * nc + c];
+    T->kxz.assign((size_t)nc * nq, 0.0), T->kyz.assign((size_t)nc * nq, 0.0), T->kzz.assign((size_t)nc * nq, 0.0);
+    T->slope_max = slope_max, T->bz_min = bz_min;
+    T->nfloor = T->nclip = 0;
+    T->iso = npg::kRediSet;
+    return NPG_OK;
+}
+NPG_API int npg_tracers_isoneutral_update(npg_tracers *T, double N2, const npg_vec *b) {
+    REQUIRE(T && b, "npg_tracers_isoneutral_update: NULL argument");
+    npg_fe *fe = T->fe;
+    npg::RediCheck a{"npg_tracers_isoneutral_update"};
+    a.need = npg::kRediSet, a.state = T->iso, a.n_b = fe->n_b, a.vec_n = b->n, a.N2 = N2;
+    REQUIRE_OK(npg::check_redi(a));
+    const HostShape s = host_shape(fe);
+    const HostView t = host_view(fe);
+    int64_t nfloor = 0, nclip = 0;
+#pragma omp parallel for schedule(static) reduction(+ : nfloor, nclip)
+    for (int64_t cell = 0; cell < fe->ncell; ++cell) {
+        int nf = 0, ncl = 0;
+        if (fe->nb == 10)
+            npg::cell_redi_update<10>(s, t, fe->nq, N2, b->d, T->kiso.data(), T->slope_max, T->bz_min, cell, T->kxz.data(), T->kyz.data(),
+                                      T->kzz.data(), nf, ncl);
+        else
+            npg::cell_redi_update<4>(s, t, fe->nq, N2, b->d, T->kiso.data(), T->slope_max, T->bz_min, cell, T->kxz.data(), T->kyz.data(),
+                                     T->kzz.data(), nf, ncl);
+        nfloor += nf, nclip += ncl;
+    }
+    T->nfloor = nfloor, T->nclip = nclip;
+    T->iso = npg::kRediUpdated;
+    return NPG_OK;
+}
+NPG_API int npg_tracers_isoneutral_matrix(npg_tracers *T, npg_csr *K) {
+    REQUIRE(T && K, "npg_tracers_isoneutral_matrix: NULL argument");
+    npg_fe *fe = T->fe;
+    npg::RediCheck a{"npg_tracers_isoneutral_matrix"};
+    a.need = npg::kRediUpdated, a.state = T->iso, a.n_b = fe->n_b, a.mat_m = K->m, a.mat_n = K->n;
+    REQUIRE_OK(npg::check_redi(a));
+    const int nb = fe->nb, nq = fe->nq;
+    std::fill(K->val.begin(), K->val.end(), 0.0);
+    int64_t missing = 0;
+#pragma omp parallel for schedule(dynamic, 64) reduction(+ : missing)
+    for (int64_t r = 0; r < K->m; ++r) {
+        for (int64_t k = fe->gptr[(size_t)r]; k < fe->gptr[(size_t)r + 1]; ++k) {
+            const int64_t cell = fe->gidx[(size_t)k] / nb;
+            const int i = (int)(fe->gidx[(size_t)k] % nb);
+            const double *G = &fe->G[(size_t)cell * 12];
+            double acc[10] = {0};
+            for (int q = 0; q < nq; ++q) {
+                const double w = fe->qw[(size_t)q] * fe->wdet[(size_t)cell];
+                const size_t o = (size_t)cell * nq + q;
+                double gi[3];
+                grad_of(fe->dNb.data(), nb, G, q, i, gi);
+                for (int j = 0; j < nb; ++j) {
+                    double gj[3];
+                    grad_of(fe->dNb.data(), nb, G, q, j, gj);
+                    acc[j] += npg::redi_entry(w, T->kiso[o], T->kxz[o], T->kyz[o], T->kzz[o], gi[0], gi[1], gi[2], gj[0], gj[1], gj[2]);
+                }
+            }
+            for (int j = 0; j < nb; ++j) {
+                const int32_t c = fe->cb[(size_t)cell * nb + j];
+                if (c < 0) continue;                       // Dirichlet columns: the lift is per tracer (npg_tracers_rhs)
+                const int64_t sl = slot_of(K, r, c);
+                if (sl >= 0) K->val[(size_t)sl] += acc[j];
+                else if (acc[j] != 0.0) ++missing;
+            }
+        }
+    }
+    REQUIRE(missing == 0, "npg_tracers_isoneutral_matrix: %lld non-zero local entries fall outside the matrix's pattern: it is not the buoyancy pattern",
+            (long long)missing);
+    return NPG_OK;
+}
+NPG_API int npg_tracers_isoneutral_tables(npg_tracers *T, double *kxz, double *kyz, double *kzz) {
+    REQUIRE(T && kxz && kyz && kzz, "npg_tracers_isoneutral_tables: NULL argument");
+    npg::RediCheck a{"npg_tracers_isoneutral_tables"};
+    a.need = npg::kRediUpdated, a.state = T->iso;
+    REQUIRE_OK(npg::check_redi(a));
+    const int64_t nc = T->fe->ncell;
+    const int nq = T->fe->nq;
+    for (int64_t c = 0; c < nc; ++c)
+        for (int q = 0; q < nq; ++q) {
+            const size_t o = (size_t)c * nq + q, e = (size_t)q * nc + c;
+            kxz[e] = T->kxz[o], kyz[e] = T->kyz[o], kzz[e] = T->kzz[o];
+        }
+    return NPG_OK;
+}
+NPG_API int npg_tracers_isoneutral_info(npg_tracers *T, int64_t *nfloored, int64_t *nclipped, int64_t *npoints, int *state) {
+    REQUIRE(T, "npg_tracers_isoneutral_info: NULL handle");
+    const bool up = T->iso == npg::kRediUpdated;
+    if (nfloored) *nfloored = up ? T->nfloor : 0;
+    if (nclipped) *nclipped = up ? T->nclip : 0;
+    if (npoints) *npoints = T->iso == npg::kRediOff ? 0 : T->fe->ncell * T->fe->nq;
+    if (state) *state = T->iso;
     return NPG_OK;
 }

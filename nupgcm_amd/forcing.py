@@ -113,7 +113,7 @@ class SurfaceForcing:
     `.detach()` restores the static vectors and the left-hand side without S.  `.tables(t)`: the blended point tables of tau_x, tau_y,
     flux (nface, 9) - what BoundaryIntegrals.set_coeff takes.  `.S`: the surface matrix (DeviceCSR, pattern "b") or None.
     Refused: mesh-partitioned and replicated-distributed models, embedded 2-D meshes (NotImplementedError); restoring together with
-    model.tracers (the tracers share solver.A and would be restored towards 0: out of scope); restoring or a non-zero flux where a
+    model.tracers (the tracers share solver.A and would be restored towards 0: out of scope - isoneutral tracers have a matrix of their own and are accepted); restoring or a non-zero flux where a
     buoyancy Dirichlet node lies on a forced face, non-finite values, negative gamma, a toolkit without b_lift (ValueError).  A failed
     constructor leaves the model as it was."""
 
@@ -126,9 +126,9 @@ class SurfaceForcing:
                              "lift without the wind is not known")
         if getattr(model, "surface_forcing", None) is not None:
             raise ValueError("SurfaceForcing: the model already has a surface forcing - detach() it first")
-        if restoring is not None and getattr(model, "tracers", None) is not None:
+        if restoring is not None and getattr(model, "tracers", None) is not None and getattr(model.tracers, "isoneutral", None) is None:
             raise NotImplementedError("SurfaceForcing(restoring=...) on a model with passive tracers is out of scope: the tracers share "
-                                      "the evolution's matrix and would be restored towards 0")
+                                      "the evolution's matrix and would be restored towards 0")   # (isoneutral tracers have their own)
         self.model = model
         fed, frc = model.fe_data, model.forcings
         m = fed.mesh

@@ -46,7 +46,7 @@ class InteriorForcing:
     at the points; `.key_weights(t)`; `.info()`; `.budget(model, t)`: dict(volume, source, restoring) = int dV, int Q dV,
     int gamma (b* - b) dV over the kept cells for the device-resident b (one deterministic device pass, three doubles downloaded).
     Refused: mesh-partitioned and replicated-distributed models, embedded 2-D meshes, a time-dependent gamma, restoring together with
-    model.tracers (NotImplementedError; a pure source and tracers get along); non-finite values, negative gamma, a second
+    model.tracers (NotImplementedError; a pure source and tracers get along, and so do isoneutral tracers: their matrix is their own); non-finite values, negative gamma, a second
     InteriorForcing on the model, a mask of the wrong shape or dtype (ValueError).  A failed constructor leaves the model as it was.
     The 11-point rule has a negative weight: keep gamma smooth on the scale of a cell (see the module's caveat)."""
 
@@ -56,9 +56,9 @@ class InteriorForcing:
             raise ValueError("InteriorForcing: the model has no EvolutionToolkit")
         if getattr(model, "interior_forcing", None) is not None:
             raise ValueError("InteriorForcing: the model already has an interior forcing - detach() it first")
-        if restoring is not None and getattr(model, "tracers", None) is not None:
+        if restoring is not None and getattr(model, "tracers", None) is not None and getattr(model.tracers, "isoneutral", None) is None:
             raise NotImplementedError("InteriorForcing(restoring=...) on a model with passive tracers is out of scope: the tracers share "
-                                      "the evolution's matrix and would be restored towards 0")
+                                      "the evolution's matrix and would be restored towards 0")   # (isoneutral tracers have their own)
         self.model = model
         fed = model.fe_data
         m = fed.mesh
