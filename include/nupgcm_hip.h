@@ -954,6 +954,31 @@ int npg_tracers_isoneutral_matrix(npg_tracers *T, npg_csr *K);
 int npg_tracers_isoneutral_info(npg_tracers *T, int64_t *nfloored, int64_t *nclipped, int64_t *npoints, int *state);
 int npg_tracers_isoneutral_tables(npg_tracers *T, double *kxz, double *kyz, double *kzz);
 
+/* ---- the tracers' transport operator as a matrix: equilibria and implicit-advection steps with a frozen flow ----------------------
+ * (csrc/transport_core.h).  With W = w_q |J| and u(q) = scale sum_a N2[q][a] u_a,
+ *    C[i][j] = sum_{cells, q} W phi_i(q) ( u(q) . grad phi_j(q) ),
+ *    g_k[i]  = int ( S_k - u_z gamma_k - u . grad c_D,k - lambda_k c_D,k ) phi_i
+ *              - kappa_hat int ( kappa_h grad_h c_D,k . grad_h phi_i + kappa_v d_z c_D,k d_z phi_i ) + kappa_hat gamma_k rhs_diff1[i] + flux_k[i],
+ * c_D,k the tracer's Dirichlet values (npg_tracers_set), so that for any c, any dt and lambda = 0
+ *    npg_tracers_rhs(NPG_BDF1, dt, dt kappa_hat, c, c, x, x) = M c + dt (g - C c)          over the free rows, to summation rounding.
+ * npg_tracers_transport_update writes the three velocity tables ux, uy, uz [nq][ncell] from x_inv = [u; p] (one launch, one lane per
+ * cell).  npg_tracers_transport_matrix assembles C on the buoyancy pattern (one launch, sixteen lanes per CSR row, no atomics, the
+ * same bits on every call; free columns only: the Dirichlet lift is in the load; scale = 0 gives exact zeros).
+ * npg_tracers_transport_load writes the K loads (one fused element launch that reads the velocity tables once per cell, and the
+ * gather of npg_tracers_rhs); decay = lambda[K] on the host or NULL, rhs_diff1 is needed when a tracer has gamma != 0, the engine's
+ * kappa_h / kappa_v tables when one has a non-zero Dirichlet value.  All fp64 whatever npg_fe_set_precision says.
+ * Refused (NPG_EINVAL + message, before anything is launched, outputs untouched): a non-finite scale, an x_inv of the wrong length, a
+ * matrix that is not on the buoyancy pattern, a negative or non-finite decay rate or kappa_hat, a matrix / load / tables call before an
+ * update, an embedded 2-D engine, handles of different contexts.
+ * npg_tracers_transport_info: state 0 = no tables, 1 = updated; umax = the largest |u| over the points of the last update.
+ * npg_tracers_transport_tables downloads the three tables ([nq][ncell] each). */
+int npg_tracers_transport_update(npg_tracers *T, const npg_vec *x_inv, double scale);
+int npg_tracers_transport_matrix(npg_tracers *T, npg_csr *C);
+int npg_tracers_transport_load(npg_tracers *T, double kappa_hat, const double *decay_or_null, const npg_vec *rhs_diff1_or_null,
+                               const npg_vec *flux_or_null, npg_vec *out);
+int npg_tracers_transport_info(npg_tracers *T, int *state, double *umax);
+int npg_tracers_transport_tables(npg_tracers *T, double *ux, double *uy, double *uz);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (new work: the reference is single-device) ----------------- */
 #define NPG_UNIQUE_ID_BYTES 128
 int npg_comm_unique_id(void *id128);                                  /* rank 0 makes it, the launcher broadcasts it */

@@ -28,6 +28,7 @@ from .sections import Section, SectionFluxes, SectionMaps, SectionRecorder, Sect
 from .surfaces import BuoyancySurfaces, SurfaceMaps, SurfaceRecorder, column_depth
 from .timesteppers import BDF1, BDF2, update_dt, update_t
 from .tracers import Isoneutral, PassiveTracers, TracerSpec
+from .transport import TracerTransport
 from .watermass import BuoyancyClasses, ClassRecorder, ClassTable, MixingTable
 
 __all__ = [n for n in dir() if not n.startswith("_")]

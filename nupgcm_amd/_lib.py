@@ -195,6 +195,9 @@ def _declare(L, partial=False):
         "npg_tracers_set_isoneutral": [P, VP, D, D], "npg_tracers_isoneutral_update": [P, D, P], "npg_tracers_isoneutral_matrix": [P, P],
         "npg_tracers_isoneutral_info": [P, C.POINTER(I64), C.POINTER(I64), C.POINTER(I64), C.POINTER(C.c_int)],
         "npg_tracers_isoneutral_tables": [P, VP, VP, VP],
+        "npg_tracers_transport_update": [P, P, D], "npg_tracers_transport_matrix": [P, P],
+        "npg_tracers_transport_load": [P, D, VP, P, P, P], "npg_tracers_transport_info": [P, C.POINTER(C.c_int), C.POINTER(D)],
+        "npg_tracers_transport_tables": [P, VP, VP, VP],
         "npg_comm_unique_id": [VP], "npg_comm_init": [P, VP, C.c_int, C.c_int],
         "npg_comm_allreduce_sum": [P, C.POINTER(D), C.c_int], "npg_comm_info": [P, C.c_char_p, C.c_size_t], "npg_comm_disable_peer": [P], "npg_comm_allreduce_vec": [P, P],
         "npg_comm_allgather_segments": [P, P, C.c_int, VP, VP, VP, VP, P],
@@ -268,4 +271,5 @@ NPG_NMIX = 8
 NPG_NSURF = 9
 NPG_CG_MULTI_MAX = 32
 NPG_REDI_OFF, NPG_REDI_SET, NPG_REDI_UPDATED = range(3)
+NPG_TRANSPORT_OFF, NPG_TRANSPORT_UPDATED = range(2)
 NPG_MAT_M, NPG_MAT_KH, NPG_MAT_KV, NPG_MAT_A, NPG_MAT_B = 1, 2, 3, 4, 5

@@ -17,6 +17,14 @@
 //                           quadrature point, the row's (cell, local DoF) pairs in cell order, the DPP tree, row_add.  fp64 always.
 //   k_tracers_local_iso     pass 1 with the rotated tensor in the second integral (cell_tracers<R, NB, true>); the instances of
 //                           k_tracers_local are not touched by the flag.
+// The transport operator as a matrix (npg_tracers_transport_*, transport_core.h): equilibria and implicit steps.
+//   k_transport_velocity    one lane per cell, shape tables in LDS as k_redi_update: the three velocity tables ux, uy, uz at the cell's
+//                           quadrature points from its 30 velocity values.
+//   k_transport_matrix<NB>  C on the buoyancy pattern with the skeleton of k_redi_matrix: sixteen lanes own a CSR row, lane =
+//                           quadrature point, three tables and three products per pair.  fp64 always, no atomics.
+//   k_transport_load<NB>    one lane per cell: the local loads of all K tracers (cell_transport_load); the cell's velocities are read
+//                           from the tables once into the lane's LDS column (as k_tracers_local), then a run-time loop over the
+//                           tracers.  The rows are then gathered by k_tracers_gather.
 #include <cmath>
 
 #include "common.h"
@@ -24,6 +32,7 @@
 #include "fe_dev.h"
 #include "redi_core.h"
 #include "tracers_core.h"
+#include "transport_core.h"
 
 static_assert(npg::kTrMaxQ == npg::kMaxQ, "a lane column holds the engine's largest rule");
 
@@ -140,6 +149,76 @@ __global__ void __launch_bounds__(kBlock) k_redi_matrix(FeDev d, RediDev rd, con
     }
 }
 
+// the velocity tables, [nq][ncell] each
+struct TransportDev {
+    const double *ux, *uy, *uz;
+};
+
+__global__ void __launch_bounds__(kBlock) k_transport_velocity(FeDev d, double scale, const double *xi, double *ux, double *uy, double *uz) {
+    __shared__ FeTables t;
+    stage_tables(d, t);
+    const int64_t cell = blockIdx.x * (int64_t)kBlock + threadIdx.x;
+    if (cell < d.ncell) cell_transport_velocity(t, cell_view(d), d.nq, scale, xi, cell, ux, uy, uz);
+}
+
+template <int NB>
+__global__ void __launch_bounds__(kBlock) k_transport_matrix(FeDev d, TransportDev td, const int64_t *gptr, const int32_t *gidx, int64_t nrows,
+                                                             const int64_t *rowptr, const int32_t *col, double *val, int *missing) {
+    __shared__ FeTables t;
+    stage_tables(d, t);
+    const int64_t r = (blockIdx.x * (int64_t)kBlock + threadIdx.x) / kQL;
+    const int q = threadIdx.x % kQL;
+    if (r >= nrows) return;                                  // whole lane groups leave together
+    const int32_t row = (int32_t)r;
+    const bool on = q < d.nq;
+    for (int64_t k = gptr[r]; k < gptr[r + 1]; ++k) {
+        const int64_t cell = gidx[k] % d.ncell;
+        const int i = (int)(gidx[k] / d.ncell);
+        double acc[NB];
+#pragma unroll
+        for (int j = 0; j < NB; ++j) acc[j] = 0.0;
+        if (on) {
+            const double w = t.qw[q] * d.wdet[cell];
+            const size_t o = (size_t)q * d.ncell + cell;
+            const double ux = td.ux[o], uy = td.uy[o], uz = td.uz[o];
+            const double phi = t.Nb[q * NB + i];
+            double G[12];
+#pragma unroll
+            for (int e = 0; e < 12; ++e) G[e] = d.G[(size_t)e * d.ncell + cell];
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+                double gx, gy, gz;
+                grad_b<double, NB>(t, G, q, j, gx, gy, gz);
+                acc[j] = transport_entry(w, phi, ux, uy, uz, gx, gy, gz);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NB; ++j) acc[j] = group_sum_dpp<kQL>(acc[j]);
+        // lane j adds column j; Dirichlet columns are skipped (their lift is per tracer: the load)
+        double mine = 0.0;
+#pragma unroll
+        for (int j = 0; j < NB; ++j) mine = (q == j) ? acc[j] : mine;
+        if (q < NB) {
+            const int32_t c = d.cb[(size_t)q * d.ncell + cell];
+            if (c >= 0) row_add(rowptr, col, val, row, c, mine, missing);
+        }
+        __builtin_amdgcn_s_waitcnt(0);                       // this cell's stores are out before the next cell's loads
+    }
+}
+
+// (kTrBlock lanes and the nq x 3 velocities of a lane in a column of dynamic LDS, as k_tracers_local)
+template <int NB>
+__global__ void __launch_bounds__(kTrBlock) k_transport_load(FeDev d, TransportDev td, double kappa_hat, const double *decay, TracerSet ts) {
+    __shared__ FeTables t;
+    stage_tables(d, t);
+    extern __shared__ double uq_lds[];                                   // 3 nq kTrBlock doubles
+    const int64_t cell = blockIdx.x * (int64_t)kTrBlock + threadIdx.x;
+    if (cell >= d.ncell) return;
+    const TransportCells<DevCells> cells{cell_view(d), td.ux, td.uy, td.uz};
+    LaneColumn<double> uq{uq_lds + threadIdx.x};
+    cell_transport_load<NB>(t, cells, uq, d.nq, kappa_hat, decay, ts, cell);
+}
+
 // out[k][r], k = blockIdx.y
 __global__ void __launch_bounds__(kBlock) k_tracers_gather(const int64_t *gptr, const int32_t *gidx, int64_t n, TracerSet ts,
                                                            double theta, double dt, const double *rhs_diff1, const double *flux,
@@ -174,6 +253,10 @@ struct npg_tracers {
     DevBuf<int32_t> counts;          // [2 iso_grid]
     DevBuf<int> missing;
     int iso_grid = 0;
+    // the transport operator (npg_tracers_transport_update): the velocity tables [nq][ncell], the decay rates of the last load
+    int transport = kTransportOff;
+    int flat = -1;                   // the engine is an embedded 2-D one (-1: not looked at yet)
+    DevBuf<double> tux, tuy, tuz, decay;
 };
 
 static bool engine_is_flat(const npg_fe *fe, int *rc) {   // an embedded 2-D engine pads its triangles to tetrahedra: N1[q][3] = 0
@@ -287,6 +370,136 @@ NPG_API int npg_tracers_isoneutral_info(npg_tracers *T, int64_t *nfloored, int64
     if (nclipped) *nclipped = ncl;
     if (npoints) *npoints = T->iso == kRediOff ? 0 : (int64_t)T->fe->d.nq * T->fe->d.ncell;
     if (state) *state = T->iso;
+    return NPG_OK;
+}
+
+// ---- the transport operator as a matrix (transport_core.h) ----------------------------------------------------------------------------
+NPG_API int npg_tracers_transport_update(npg_tracers *T, const npg_vec *x_inv, double scale) {
+    NPG_REQUIRE(T && x_inv, "npg_tracers_transport_update: NULL argument");
+    npg_fe *fe = T->fe;
+    NPG_HIP(hipSetDevice(T->ctx->device));
+    if (T->flat < 0) {
+        int rc = NPG_OK;
+        const bool flat = engine_is_flat(fe, &rc);
+        NPG_REQUIRE(rc == NPG_OK, "npg_tracers_transport_update: reading the engine's shape tables failed");
+        T->flat = flat;
+    }
+    TransportCheck a{"npg_tracers_transport_update"};
+    a.same_ctx = x_inv->ctx == fe->ctx;
+    a.update = true, a.scale = scale, a.n_inv = fe->n_inv, a.vec_n = x_inv->n, a.flat = T->flat != 0;
+    NPG_REQUIRE_OK(check_transport(a));
+    const FeDev &d = fe->d;
+    const size_t npts = (size_t)d.nq * d.ncell;
+    if (!T->tux) {
+        NPG_HIP(T->tux.zeros(npts));
+        NPG_HIP(T->tuy.zeros(npts));
+        NPG_HIP(T->tuz.zeros(npts));
+        NPG_HIP(T->decay.zeros((size_t)T->ntracer));
+    }
+    const int grid = (int)((d.ncell + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_transport_velocity, dim3(grid), dim3(kBlock), 0, T->ctx->stream, d, scale, x_inv->d, T->tux, T->tuy, T->tuz);
+    NPG_HIP(hipGetLastError());
+    T->transport = kTransportUpdated;
+    return NPG_OK;
+}
+
+NPG_API int npg_tracers_transport_matrix(npg_tracers *T, npg_csr *Cm) {
+    NPG_REQUIRE(T && Cm, "npg_tracers_transport_matrix: NULL argument");
+    npg_fe *fe = T->fe;
+    TransportCheck a{"npg_tracers_transport_matrix"};
+    a.same_ctx = Cm->ctx == fe->ctx;
+    a.need = kTransportUpdated, a.state = T->transport, a.n_b = fe->n_b, a.mat_m = Cm->m, a.mat_n = Cm->n;
+    a.mat_plain = Cm->nnode() == 0 && Cm->lb.nblocks == 0 && !Cm->uperm;
+    NPG_REQUIRE_OK(check_transport(a));
+    NPG_HIP(hipSetDevice(T->ctx->device));
+    hipStream_t st = T->ctx->stream;
+    const FeDev &d = fe->d;
+    if (!T->missing) NPG_HIP(T->missing.zeros(1));          // (shared with the isoneutral mode, which frees it when switched off)
+    NPG_HIP(hipMemsetAsync(Cm->val, 0, (size_t)Cm->nnz * sizeof(double), st));
+    NPG_HIP(hipMemsetAsync(T->missing, 0, sizeof(int), st));
+    const TransportDev td{T->tux, T->tuy, T->tuz};
+    const int grid = (int)((Cm->m * kQL + kBlock - 1) / kBlock);
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, st, d, td, fe->gptr, fe->gidx, Cm->m, Cm->rowptr, Cm->col, Cm->val, T->missing);
+    };
+    d.nb == 10 ? go(k_transport_matrix<10>) : go(k_transport_matrix<4>);
+    NPG_HIP(hipGetLastError());
+    int miss = 0;
+    NPG_HIP(hipMemcpyAsync(&miss, T->missing, sizeof(int), hipMemcpyDeviceToHost, st));
+    NPG_HIP(hipStreamSynchronize(st));
+    NPG_REQUIRE(miss == 0, "npg_tracers_transport_matrix: %d non-zero local entries fall outside the matrix's pattern: it is not the buoyancy pattern",
+                miss);
+    return csr_repack(Cm);
+}
+
+NPG_API int npg_tracers_transport_load(npg_tracers *T, double kappa_hat, const double *decay_or_null, const npg_vec *rhs_diff1_or_null,
+                                       const npg_vec *flux_or_null, npg_vec *out) {
+    NPG_REQUIRE(T && out, "npg_tracers_transport_load: NULL argument");
+    npg_fe *fe = T->fe;
+    const int K = T->ntracer;
+    const int64_t nb = fe->n_b;
+    TransportCheck a{"npg_tracers_transport_load"};
+    for (const npg_vec *v : {rhs_diff1_or_null, flux_or_null, (const npg_vec *)out}) a.same_ctx = a.same_ctx && (!v || v->ctx == fe->ctx);
+    a.load = true, a.kappa_hat = kappa_hat, a.decay = decay_or_null, a.ntracer = K, a.n_b = nb;
+    a.need = kTransportUpdated, a.state = T->transport;
+    a.out_n = out->n, a.flux_n = flux_or_null ? flux_or_null->n : -1, a.diff1_n = rhs_diff1_or_null ? rhs_diff1_or_null->n : -1;
+    bool lift = false;
+    for (int k = 0; k < K; ++k) {
+        a.need_diff1 = a.need_diff1 || T->h_gamma[(size_t)k] != 0.0;
+        lift = lift || T->h_lift[(size_t)k];
+    }
+    a.need_coeff = lift && !(fe->d.kh && fe->d.kv);
+    NPG_REQUIRE_OK(check_transport(a));
+    NPG_HIP(hipSetDevice(T->ctx->device));
+    hipStream_t st = T->ctx->stream;
+    if (decay_or_null) {
+        NPG_HIP(hipStreamSynchronize(st));                  // an earlier load on the stream may still read the rates
+        NPG_HIP(hipMemcpy(T->decay, decay_or_null, (size_t)K * sizeof(double), hipMemcpyHostToDevice));
+    }
+    const FeDev &d = fe->d;
+    TracerSet ts{K, nb, T->n_diri, (int64_t)d.nb * d.ncell, nullptr, nullptr, T->diri, T->gamma, T->source, T->loc};
+    const TransportDev td{T->tux, T->tuy, T->tuz};
+    const int grid = (int)((d.ncell + kTrBlock - 1) / kTrBlock);
+    const size_t lds = (size_t)3 * d.nq * kTrBlock * sizeof(double);
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kTrBlock), lds, st, d, td, kappa_hat, decay_or_null ? (const double *)T->decay : nullptr, ts);
+    };
+    d.nb == 10 ? go(k_transport_load<10>) : go(k_transport_load<4>);
+    NPG_HIP(hipGetLastError());
+    const int ggrid = (int)std::min<int64_t>(2048, (nb + kBlock - 1) / kBlock);
+    // (tracer_row with theta = kappa_hat and dt = 1: + kappa_hat gamma_k rhs_diff1 + flux_k)
+    hipLaunchKernelGGL(k_tracers_gather, dim3(ggrid, K), dim3(kBlock), 0, st, fe->gptr, fe->gidx, nb, ts, kappa_hat, 1.0,
+                       rhs_diff1_or_null ? rhs_diff1_or_null->d : nullptr, flux_or_null ? flux_or_null->d : nullptr, out->d);
+    NPG_HIP(hipGetLastError());
+    return NPG_OK;
+}
+
+NPG_API int npg_tracers_transport_tables(npg_tracers *T, double *ux, double *uy, double *uz) {
+    NPG_REQUIRE(T && ux && uy && uz, "npg_tracers_transport_tables: NULL argument");
+    TransportCheck a{"npg_tracers_transport_tables"};
+    a.need = kTransportUpdated, a.state = T->transport;
+    NPG_REQUIRE_OK(check_transport(a));
+    NPG_HIP(hipSetDevice(T->ctx->device));
+    NPG_HIP(hipStreamSynchronize(T->ctx->stream));
+    const size_t bytes = (size_t)T->fe->d.nq * T->fe->d.ncell * sizeof(double);
+    NPG_HIP(hipMemcpy(ux, T->tux, bytes, hipMemcpyDeviceToHost));
+    NPG_HIP(hipMemcpy(uy, T->tuy, bytes, hipMemcpyDeviceToHost));
+    NPG_HIP(hipMemcpy(uz, T->tuz, bytes, hipMemcpyDeviceToHost));
+    return NPG_OK;
+}
+
+NPG_API int npg_tracers_transport_info(npg_tracers *T, int *state, double *umax) {
+    NPG_REQUIRE(T, "npg_tracers_transport_info: NULL handle");
+    double um = 0.0;
+    if (umax && T->transport == kTransportUpdated) {
+        const size_t npts = (size_t)T->fe->d.nq * T->fe->d.ncell;
+        std::vector<double> x(npts), y(npts), z(npts);
+        const int rc = npg_tracers_transport_tables(T, x.data(), y.data(), z.data());
+        if (rc != NPG_OK) return rc;
+        for (size_t o = 0; o < npts; ++o) um = std::max(um, std::sqrt(x[o] * x[o] + y[o] * y[o] + z[o] * z[o]));
+    }
+    if (state) *state = T->transport;
+    if (umax) *umax = um;
     return NPG_OK;
 }
 

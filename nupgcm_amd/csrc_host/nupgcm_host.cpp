@@ -2471,6 +2471,7 @@ NPG_API int npg_surfaces_compute(npg_surfaces *S, const npg_vec *x_inv, const np
 // (csrc/tracers_core.h); pass 2 walks the engine's inverted index in cell order, as gather_rows does. ----------------------------------
 #include "../csrc/redi_core.h"
 #include "../csrc/tracers_core.h"
+#include "../csrc/transport_core.h"
 
 struct npg_tracers {
     npg_fe *fe = nullptr;
@@ -2483,6 +2484,9 @@ struct npg_tracers {
     double slope_max = 0.0, bz_min = 0.0;
     std::vector<double> kiso, kxz, kyz, kzz;
     int64_t nfloor = 0, nclip = 0;
+    // the transport operator (csrc/transport_core.h): the velocity tables [ncell][nq]
+    int transport = npg::kTransportOff;
+    std::vector<double> tux, tuy, tuz;
 };
 namespace {
 struct HostTrVel {       // a cell's velocities at the quadrature points
@@ -2681,6 +2685,125 @@ NPG_API int npg_tracers_isoneutral_tables(npg_tracers *T, double *kxz, double *k
             const size_t o = (size_t)c * nq + q, e = (size_t)q * nc + c;
             kxz[e] = T->kxz[o], kyz[e] = T->kyz[o], kzz[e] = T->kzz[o];
         }
+    return NPG_OK;
+}
+// ---- the tracers' transport operator as a matrix (csrc/tracers.hip on the host; the arithmetic is csrc/transport_core.h) -----------------
+NPG_API int npg_tracers_transport_update(npg_tracers *T, const npg_vec *x_inv, double scale) {
+    REQUIRE(T && x_inv, "npg_tracers_transport_update: NULL argument");
+    npg_fe *fe = T->fe;
+    const int64_t nc = fe->ncell;
+    const int nq = fe->nq;
+    npg::TransportCheck a{"npg_tracers_transport_update"};
+    a.same_ctx = x_inv->ctx == fe->ctx;
+    a.update = true, a.scale = scale, a.n_inv = fe->n_inv, a.vec_n = x_inv->n;
+    a.flat = true;
+    for (int q = 0; q < nq; ++q) a.flat = a.flat && fe->N1[(size_t)q * 4 + 3] == 0.0;
+    REQUIRE_OK(npg::check_transport(a));
+    T->tux.resize((size_t)nc * nq), T->tuy.resize((size_t)nc * nq), T->tuz.resize((size_t)nc * nq);
+    const HostShape s = host_shape(fe);
+    const HostView t = host_view(fe);
+#pragma omp parallel for schedule(static)
+    for (int64_t cell = 0; cell < nc; ++cell)
+        npg::cell_transport_velocity(s, t, nq, scale, x_inv->d, cell, T->tux.data(), T->tuy.data(), T->tuz.data());
+    T->transport = npg::kTransportUpdated;
+    return NPG_OK;
+}
+NPG_API int npg_tracers_transport_matrix(npg_tracers *T, npg_csr *Cm) {
+    REQUIRE(T && Cm, "npg_tracers_transport_matrix: NULL argument");
+    npg_fe *fe = T->fe;
+    npg::TransportCheck a{"npg_tracers_transport_matrix"};
+    a.same_ctx = Cm->ctx == fe->ctx;
+    a.need = npg::kTransportUpdated, a.state = T->transport, a.n_b = fe->n_b, a.mat_m = Cm->m, a.mat_n = Cm->n;
+    REQUIRE_OK(npg::check_transport(a));
+    const int nb = fe->nb, nq = fe->nq;
+    std::fill(Cm->val.begin(), Cm->val.end(), 0.0);
+    int64_t missing = 0;
+#pragma omp parallel for schedule(dynamic, 64) reduction(+ : missing)
+    for (int64_t r = 0; r < Cm->m; ++r) {
+        for (int64_t k = fe->gptr[(size_t)r]; k < fe->gptr[(size_t)r + 1]; ++k) {
+            const int64_t cell = fe->gidx[(size_t)k] / nb;
+            const int i = (int)(fe->gidx[(size_t)k] % nb);
+            const double *G = &fe->G[(size_t)cell * 12];
+            double acc[10] = {0};
+            for (int q = 0; q < nq; ++q) {
+                const double w = fe->qw[(size_t)q] * fe->wdet[(size_t)cell];
+                const size_t o = (size_t)cell * nq + q;
+                const double phi = fe->Nb[(size_t)q * nb + i];
+                for (int j = 0; j < nb; ++j) {
+                    double gj[3];
+                    grad_of(fe->dNb.data(), nb, G, q, j, gj);
+                    acc[j] += npg::transport_entry(w, phi, T->tux[o], T->tuy[o], T->tuz[o], gj[0], gj[1], gj[2]);
+                }
+            }
+            for (int j = 0; j < nb; ++j) {
+                const int32_t c = fe->cb[(size_t)cell * nb + j];
+                if (c < 0) continue;                       // Dirichlet columns: the lift is per tracer (the load)
+                const int64_t sl = slot_of(Cm, r, c);
+                if (sl >= 0) Cm->val[(size_t)sl] += acc[j];
+                else if (acc[j] != 0.0) ++missing;
+            }
+        }
+    }
+    REQUIRE(missing == 0, "npg_tracers_transport_matrix: %lld non-zero local entries fall outside the matrix's pattern: it is not the buoyancy pattern",
+            (long long)missing);
+    return NPG_OK;
+}
+NPG_API int npg_tracers_transport_load(npg_tracers *T, double kappa_hat, const double *decay_or_null, const npg_vec *rhs_diff1_or_null,
+                                       const npg_vec *flux_or_null, npg_vec *out) {
+    REQUIRE(T && out, "npg_tracers_transport_load: NULL argument");
+    npg_fe *fe = T->fe;
+    const int K = T->ntracer;
+    const int64_t nb = fe->n_b, nc = fe->ncell;
+    npg::TransportCheck a{"npg_tracers_transport_load"};
+    for (const npg_vec *v : {rhs_diff1_or_null, flux_or_null, (const npg_vec *)out}) a.same_ctx = a.same_ctx && (!v || v->ctx == fe->ctx);
+    a.load = true, a.kappa_hat = kappa_hat, a.decay = decay_or_null, a.ntracer = K, a.n_b = nb;
+    a.need = npg::kTransportUpdated, a.state = T->transport;
+    a.out_n = out->n, a.flux_n = flux_or_null ? flux_or_null->n : -1, a.diff1_n = rhs_diff1_or_null ? rhs_diff1_or_null->n : -1;
+    bool lift = false;
+    for (int k = 0; k < K; ++k) {
+        a.need_diff1 = a.need_diff1 || T->gamma[(size_t)k] != 0.0;
+        lift = lift || T->lift[(size_t)k];
+    }
+    a.need_coeff = lift && (fe->coef[1].empty() || fe->coef[2].empty());
+    REQUIRE_OK(npg::check_transport(a));
+    const HostShape s = host_shape(fe);
+    const npg::TransportCells<HostView> t{host_view(fe), T->tux.data(), T->tuy.data(), T->tuz.data()};
+    const npg::TracerSet ts{K, nb, T->n_diri, nc * fe->nb, nullptr, nullptr, T->diri.data(), T->gamma.data(), T->source.data(), T->loc.data()};
+#pragma omp parallel for schedule(static)
+    for (int64_t cell = 0; cell < nc; ++cell) {
+        HostTrVel uq;
+        if (fe->nb == 10) npg::cell_transport_load<10>(s, t, uq, fe->nq, kappa_hat, decay_or_null, ts, cell);
+        else npg::cell_transport_load<4>(s, t, uq, fe->nq, kappa_hat, decay_or_null, ts, cell);
+    }
+#pragma omp parallel for schedule(static) collapse(2)
+    for (int k = 0; k < K; ++k)
+        for (int64_t r = 0; r < nb; ++r)
+            out->d[(size_t)k * nb + r] = npg::tracer_row(fe->gptr.data(), fe->gidx.data(), T->loc.data() + (size_t)k * ts.loc_stride, r,
+                                                         kappa_hat * T->gamma[(size_t)k], 1.0, rhs_diff1_or_null ? rhs_diff1_or_null->d : nullptr,
+                                                         flux_or_null ? flux_or_null->d + (size_t)k * nb : nullptr);
+    return NPG_OK;
+}
+NPG_API int npg_tracers_transport_tables(npg_tracers *T, double *ux, double *uy, double *uz) {
+    REQUIRE(T && ux && uy && uz, "npg_tracers_transport_tables: NULL argument");
+    npg::TransportCheck a{"npg_tracers_transport_tables"};
+    a.need = npg::kTransportUpdated, a.state = T->transport;
+    REQUIRE_OK(npg::check_transport(a));
+    const int64_t nc = T->fe->ncell;
+    const int nq = T->fe->nq;
+    for (int64_t c = 0; c < nc; ++c)
+        for (int q = 0; q < nq; ++q) {
+            const size_t o = (size_t)c * nq + q, e = (size_t)q * nc + c;
+            ux[e] = T->tux[o], uy[e] = T->tuy[o], uz[e] = T->tuz[o];
+        }
+    return NPG_OK;
+}
+NPG_API int npg_tracers_transport_info(npg_tracers *T, int *state, double *umax) {
+    REQUIRE(T, "npg_tracers_transport_info: NULL handle");
+    double um = 0.0;
+    if (T->transport == npg::kTransportUpdated)
+        for (size_t o = 0; o < T->tux.size(); ++o) um = std::max(um, std::sqrt(T->tux[o] * T->tux[o] + T->tuy[o] * T->tuy[o] + T->tuz[o] * T->tuz[o]));
+    if (state) *state = T->transport;
+    if (umax) *umax = um;
     return NPG_OK;
 }
 NPG_API int npg_tracers_isoneutral_info(npg_tracers *T, int64_t *nfloored, int64_t *nclipped, int64_t *npoints, int *state) {
