@@ -905,6 +905,36 @@ int npg_surfaces_segments(const npg_surfaces *S, int32_t *cell, double *z_top, d
 int npg_surfaces_compute(npg_surfaces *S, const npg_vec *x_inv, const npg_vec *b, double N2, const double *levels, int nlev,
                          npg_vec *out, npg_vec *cols);
 
+/* ---- column integrals (the reference: scratch/postprocess.jl, compute_U_V / compute_gamma / compute_JEBAR on sampled grids) ---
+ * The exact vertical integrals of the state over fixed columns (x_j, y_j), and the state at the columns' ends (csrc/columns_core.h,
+ * DESIGN.md 32).  npg_columns_create tiles the columns exactly as npg_surfaces_create does (the same segments, bit for bit; the same
+ * rules for a dry column), and npg_columns_info / _columns / _segments read the tiling as their npg_surfaces_* namesakes do.  xy[ncol][2]
+ * is host memory (copied); the engine and the locator must outlive the handle.  Refused: NULL arguments, ncol < 1, arguments of
+ * different contexts, a partitioned locator, a locator of another mesh (an embedded 2-D engine has none), 2^31 segments or more.
+ * npg_columns_compute: along a segment every integrand is a polynomial in z of degree <= 5, integrated exactly by the 3-point
+ * Gauss-Legendre rule at z_bot + s (z_top - z_bot), s = 1/2 (1 - sqrt(3/5)), 1/2, 1/2 (1 + sqrt(3/5)), weights 5/18, 8/18, 5/18; the
+ * terms of a column's segments are added top to bottom from 0.0.  out[NPG_NCOLI + NPG_NCOLE][ncol]:
+ *    0 thickness | 1-3 int u_x, u_y, u_z | 4 int b' | 5 int z b' | 6 int p | 7, 8 int d_x p, d_y p | 9, 10 int d_x b', d_y b' |
+ *    11, 12 int z d_x b', z d_y b' | 13 int (u_x^2 + u_y^2) / 2 | 14-16 int u_x b', u_y b', u_z b' |
+ *    17-24 at the bottom (the last segment's cell, z_bot): p, b', d_z b', d_x p, d_y p, d_z p, d_x z_bot, d_y z_bot |
+ *    25-30 at the top (the first segment's cell, z_top): p, b', u_x, u_y, d_x z_top, d_y z_top.
+ * The slopes of z_bot and z_top are those of the cell's face the column leaves through: - G_ix / G_iz of the constraint lambda_i >= 0
+ * that bounds the column's interval in the cell (at a tie the lowest i).  The fields are evaluated as npg_fe_sample evaluates them.
+ * A dry column: NaN in every channel.  segments_out (may be NULL): the terms themselves, [NPG_NCOLI][nseg].  The same bits on every
+ * call, and the same bits from both libraries.  Validation (NPG_EINVAL + message) happens before anything is launched or written. */
+typedef struct npg_columns npg_columns;
+#define NPG_NCOLI 17
+#define NPG_NCOLE 14
+int npg_columns_create(npg_fe *fe, npg_locator *loc, const double *xy, int64_t ncol, npg_columns **out);
+int npg_columns_destroy(npg_columns *C);
+/* the number of segments, the most of one column and the number of dry columns; any may be NULL */
+int npg_columns_info(const npg_columns *C, int64_t *nseg, int64_t *max_per_col, int64_t *ndry);
+/* per column (host arrays, any may be NULL): z_top, z_bot (NaN where dry) and the number of segments */
+int npg_columns_columns(const npg_columns *C, double *z_top, double *z_bot, int32_t *nseg);
+/* the segments themselves, column after column (host arrays of npg_columns_info's nseg entries, any may be NULL) */
+int npg_columns_segments(const npg_columns *C, int32_t *cell, double *z_top, double *z_bot);
+int npg_columns_compute(npg_columns *C, const npg_vec *x_inv, const npg_vec *b, npg_vec *out, npg_vec *segments_out);
+
 /* ---- passive tracers carried by the flow (new work: the reference evolves b' alone) -------------------------------------------
  * K scalars stepped with the model's own advection-diffusion operator: the same BDF scheme, the same matrix M + theta (Kh + Kv) and the
  * same velocity extrapolation as b' (csrc/tracers_core.h).  Tracer k has nodal values c (free DoFs in the buoyancy

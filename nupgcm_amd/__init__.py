@@ -26,6 +26,7 @@ from .sampling import (GridDiagnostics, GridIntegrals, GridSamples, Located, Poi
                        sample_slice, sample_to_grid, zonal_mean, zonal_width)
 from .sections import Section, SectionFluxes, SectionMaps, SectionRecorder, SectionTransports
 from .surfaces import BuoyancySurfaces, SurfaceMaps, SurfaceRecorder, column_depth
+from .columns import ColumnIntegrals, ColumnMaps, ColumnRecorder
 from .timesteppers import BDF1, BDF2, update_dt, update_t
 from .tracers import Isoneutral, PassiveTracers, TracerSpec
 from .transport import TracerTransport

@@ -190,6 +190,9 @@ def _declare(L, partial=False):
         "npg_surfaces_info": [P, C.POINTER(I64), C.POINTER(I64), C.POINTER(I64)], "npg_surfaces_columns": [P, VP, VP, VP],
         "npg_surfaces_segments": [P, VP, VP, VP],
         "npg_surfaces_compute": [P, P, P, D, VP, C.c_int, P, P],
+        "npg_columns_create": [P, P, VP, I64, PP], "npg_columns_destroy": [P],
+        "npg_columns_info": [P, C.POINTER(I64), C.POINTER(I64), C.POINTER(I64)], "npg_columns_columns": [P, VP, VP, VP],
+        "npg_columns_segments": [P, VP, VP, VP], "npg_columns_compute": [P, P, P, P, P],
         "npg_tracers_create": [P, C.c_int, PP], "npg_tracers_destroy": [P], "npg_tracers_set": [P, C.c_int, VP, D, D],
         "npg_tracers_rhs": [P, C.c_int, D, D, P, P, P, P, P, P, P],
         "npg_tracers_set_isoneutral": [P, VP, D, D], "npg_tracers_isoneutral_update": [P, D, P], "npg_tracers_isoneutral_matrix": [P, P],
@@ -269,6 +272,7 @@ NPG_SEC_KH, NPG_SEC_KV = 0, 1
 NPG_NCLS = 8
 NPG_NMIX = 8
 NPG_NSURF = 9
+NPG_NCOLI, NPG_NCOLE = 17, 14
 NPG_CG_MULTI_MAX = 32
 NPG_REDI_OFF, NPG_REDI_SET, NPG_REDI_UPDATED = range(3)
 NPG_TRANSPORT_OFF, NPG_TRANSPORT_UPDATED = range(2)

@@ -2467,6 +2467,107 @@ NPG_API int npg_surfaces_compute(npg_surfaces *S, const npg_vec *x_inv, const np
     return NPG_OK;
 }
 
+// ---- column integrals (csrc/columns.hip on the host): the tiling, a segment's terms, the order of the fold and the end values are
+// the SAME code (csrc/columns_core.h), looped over the columns with OpenMP ---------------------------------------------------------------
+#include "../csrc/columns_core.h"
+static_assert(NPG_NCOLI == npg::kNColI && NPG_NCOLE == npg::kNColE, "NPG_NCOLI / NPG_NCOLE of the header and columns_core.h must agree");
+
+struct npg_columns {
+    npg_ctx *ctx = nullptr;
+    npg_fe *fe = nullptr;
+    npg_locator *loc = nullptr;
+    int64_t ncol = 0;
+    std::vector<double> xy;
+    npg::ColumnTables t;
+};
+
+NPG_API int npg_columns_create(npg_fe *fe, npg_locator *loc, const double *xy, int64_t ncol, npg_columns **out) {
+    const bool null_arg = !(fe && loc && xy && out);
+    REQUIRE_OK(npg::check_columns_create(null_arg, ncol, null_arg || loc->ctx == fe->ctx, false, null_arg ? 0 : loc->ncell,
+                                         null_arg ? 0 : fe->ncell));
+    npg_columns *S = new npg_columns();
+    S->ctx = fe->ctx, S->fe = fe, S->loc = loc, S->ncol = ncol;
+    S->xy.assign(xy, xy + 2 * ncol);
+    const char *err = npg::build_columns(loc->t.geo.data(), loc->ncell, loc->t.grid.lo[2], loc->t.grid.hi[2], xy, ncol, S->t);
+    if (err) {
+        delete S;
+        REQUIRE(false, "npg_columns_create: %s", err);
+    }
+    *out = S;
+    return NPG_OK;
+}
+NPG_API int npg_columns_destroy(npg_columns *S) {
+    delete S;
+    return NPG_OK;
+}
+NPG_API int npg_columns_info(const npg_columns *S, int64_t *nseg, int64_t *max_per_col, int64_t *ndry) {
+    REQUIRE(S, "npg_columns_info: NULL handle");
+    if (nseg) *nseg = S->t.col_ptr[(size_t)S->ncol];
+    if (max_per_col) *max_per_col = S->t.max_per_col;
+    if (ndry) *ndry = S->t.ndry;
+    return NPG_OK;
+}
+NPG_API int npg_columns_columns(const npg_columns *S, double *z_top, double *z_bot, int32_t *nseg) {
+    REQUIRE(S, "npg_columns_columns: NULL handle");
+    for (int64_t j = 0; j < S->ncol; ++j) {
+        const int64_t s0 = S->t.col_ptr[(size_t)j], s1 = S->t.col_ptr[(size_t)j + 1];
+        if (z_top) z_top[j] = s1 > s0 ? S->t.seg_ztop[(size_t)s0] : NAN;
+        if (z_bot) z_bot[j] = s1 > s0 ? S->t.seg_zbot[(size_t)s1 - 1] : NAN;
+        if (nseg) nseg[j] = (int32_t)(s1 - s0);
+    }
+    return NPG_OK;
+}
+NPG_API int npg_columns_segments(const npg_columns *S, int32_t *cell, double *z_top, double *z_bot) {
+    REQUIRE(S, "npg_columns_segments: NULL handle");
+    if (cell) std::copy(S->t.seg_cell.begin(), S->t.seg_cell.end(), cell);
+    if (z_top) std::copy(S->t.seg_ztop.begin(), S->t.seg_ztop.end(), z_top);
+    if (z_bot) std::copy(S->t.seg_zbot.begin(), S->t.seg_zbot.end(), z_bot);
+    return NPG_OK;
+}
+namespace {
+template <int NB>
+void columns_compute(const npg_columns *S, const double *xu, const double *xb, double *out, double *seg_out) {
+    const HostView t = host_view(S->fe);
+    const npg::ColumnTables &ct = S->t;
+    const double *geo = S->loc->t.geo.data();
+    const int64_t ncol = S->ncol;
+    const size_t nseg = (size_t)ct.col_ptr[(size_t)ncol];
+#pragma omp parallel for schedule(dynamic, 64)
+    for (int64_t j = 0; j < ncol; ++j) {
+        const int64_t s0 = ct.col_ptr[(size_t)j], s1 = ct.col_ptr[(size_t)j + 1];
+        if (s1 == s0) {
+            for (int ch = 0; ch < npg::kNColI + npg::kNColE; ++ch) out[(size_t)ch * ncol + j] = NAN;
+            continue;
+        }
+        const double x = S->xy[2 * (size_t)j], y = S->xy[2 * (size_t)j + 1];
+        double acc[npg::kNColI], term[npg::kNColI];
+        for (int ch = 0; ch < npg::kNColI; ++ch) acc[ch] = 0.0;
+        for (int64_t s = s0; s < s1; ++s) {            // top to bottom from 0.0: the fold of columns_core.h
+            const int64_t c = ct.seg_cell[(size_t)s];
+            npg::segment_terms<NB>(t, geo + (size_t)c * npg::kGeoStride, xu, xb, c, x, y, ct.seg_ztop[(size_t)s], ct.seg_zbot[(size_t)s], term, 1);
+            for (int ch = 0; ch < npg::kNColI; ++ch) {
+                acc[ch] += term[ch];
+                if (seg_out) seg_out[(size_t)ch * nseg + (size_t)s] = term[ch];
+            }
+        }
+        for (int ch = 0; ch < npg::kNColI; ++ch) out[(size_t)ch * ncol + j] = acc[ch];
+        npg::column_ends<NB>(t, geo, xu, xb, x, y, ct.seg_cell[(size_t)s0], ct.seg_ztop[(size_t)s0], ct.seg_cell[(size_t)s1 - 1],
+                             ct.seg_zbot[(size_t)s1 - 1], out + (size_t)npg::kNColI * ncol + j, (size_t)ncol);
+    }
+}
+}  // namespace
+NPG_API int npg_columns_compute(npg_columns *S, const npg_vec *x_inv, const npg_vec *b, npg_vec *out, npg_vec *segments_out) {
+    const bool null_arg = !(S && x_inv && b && out);
+    REQUIRE_OK(npg::check_columns_compute(
+        null_arg, null_arg || (x_inv->ctx == S->ctx && b->ctx == S->ctx && out->ctx == S->ctx && (!segments_out || segments_out->ctx == S->ctx)),
+        null_arg ? 0 : S->fe->n_inv, null_arg ? 0 : S->fe->n_b, null_arg ? 0 : x_inv->n, null_arg ? 0 : b->n, null_arg ? 0 : out->n,
+        segments_out ? segments_out->n : -1, null_arg ? 0 : S->ncol, null_arg ? 0 : S->t.col_ptr[(size_t)S->ncol]));
+    double *seg = segments_out && segments_out->n ? segments_out->d : nullptr;
+    if (S->fe->nb == 10) columns_compute<10>(S, x_inv->d, b->d, out->d, seg);
+    else columns_compute<4>(S, x_inv->d, b->d, out->d, seg);
+    return NPG_OK;
+}
+
 // ---- passive tracers carried by the flow (csrc/tracers.hip on the host): the per-cell arithmetic is the SAME code
 // (csrc/tracers_core.h); pass 2 walks the engine's inverted index in cell order, as gather_rows does. ----------------------------------
 #include "../csrc/redi_core.h"
