@@ -285,6 +285,9 @@ int64_t npg_gmres_history(npg_gmres *ws, double *buf, int64_t cap);
  * Arnoldi launch, workgroups of the row / orthogonalisation kernels, rows, memory, lazy second-pass sums.  Returns the number of
  * entries written (0 before the first solve and after a solve that failed). */
 int npg_gmres_last_config(const npg_gmres *ws, int32_t *cfg, int n);
+/* The widest step, in basis columns, that the last solve's plan gave to the resident fused row launch: 20 (every instance), 16
+ * (NPG_GMRES_FUSED_COLS=16, or a row grid admitted for the one-pass instances only) or 0 (the separate launches; no solve yet). */
+int npg_gmres_fused_cols(const npg_gmres *ws);
 
 /* CgWorkspace(n, n, VT)  (src/evolution.jl:120) */
 int npg_cg_create(npg_ctx *ctx, int64_t n, npg_cg **out);

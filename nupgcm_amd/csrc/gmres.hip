@@ -101,7 +101,7 @@ struct GDev {
                           // into the row Q1 points at, which also takes hcol1 / wnorm2 out of the orthogonalisation kernel
     int vdots;            // ... and, with the fp32-stored basis, column j is formed where it is first read: the dots kernel of
                           // step j computes it from wt and T[j].beta and stores it, the Arnoldi kernel's epilogue stores w only
-    int fusedrows;        // ... and steps of up to kFusedMaxCols columns run dots, fold and update as ONE resident launch
+    int fusedrows;        // ... and steps of up to GmresPlan::fused_cols columns run dots, fold and update as ONE resident launch
                           // (k_gmres_rows_fused), which keeps a thread's last trips on chip across a grid-wide hand-off
     struct RowsHandOff *ho;   // that hand-off's counters, generation and status word (monotonic: nothing is reset between launches)
     Snap *C, *T;
@@ -773,7 +773,7 @@ __global__ void __launch_bounds__(kRB) k_gmres_fold_first(GDev d, int j, double 
 }
 
 // ---- one resident launch for the Gram-Schmidt sums, their fold and the update (one GPU, fast kernels, fp32-stored basis) ----
-// k_gmres_rows_fused does, for a step of at most kFusedMaxCols columns, the work of k_gmres_dots_rows<., float, true>,
+// k_gmres_rows_fused<C> does, for a step of at most C <= kFusedMaxCols columns, the work of k_gmres_dots_rows<., float, true>,
 // k_gmres_fold_first and k_gmres_orth_rows<., true, float> - same grid, same rows per thread, same partial rows, same orders of
 // summation, so no bit of any result changes - and keeps what the update would read a second time on chip:
 //   phase 1  the dots pass.  A thread's trips rotate through B register buffers (trip t lives in buffer t % B; trip t + B - 1 is
@@ -789,7 +789,15 @@ __global__ void __launch_bounds__(kRB) k_gmres_fold_first(GDev d, int j, double 
 // arrivals), so a replayed graph needs no memset node.  Every workgroup must be resident: the host launches this kernel only on a
 // grid the occupancy query admits (rows_fused_blocks_per_cu).  The poll is bounded by the wall clock: on expiry the workgroup sets
 // the status word and leaves; a launch that finds it set does nothing; npg_gmres_solve reports it as an error.
-constexpr int kFusedMaxCols = 16;   // (an instance for 20 columns with two register buffers spills: 168 registers + 164 B of scratch)
+// The instances of up to kFusedOnePassCols columns stream a trip's columns at once.  Two register buffers of 20 columns spill (168
+// registers + 164 B of scratch), so the widest instance splits phase 1 by COLUMNS, not by trips:
+//   pass a   streams columns [0, H) and w for all trips in ascending order and copies those entries of the last B trips to LDS;
+//   pass b   streams columns [H, C), w and wt for all trips in ascending order, forms v_j (j >= H) as the one-pass loop does and
+//            ends with the last B trips' entries of those columns and their w pair in registers.
+// Every sum still takes its trips in ascending order and ||w||^2 is summed once (pass b), so the partial row keeps its bits; phase 2
+// subtracts the columns of a kept trip in ascending order, [0, H) from LDS and [H, C) from the registers.  w is read once more.
+constexpr int kFusedMaxCols = 20;
+constexpr int kFusedOnePassCols = 16;
 constexpr int kHoLine = 16;                      // 8-byte words per 128-byte line: every polled word has a line of its own
 constexpr int kHoShards = kRB / 32;              // = the slices of reduce_partials<kRB / 32, kMaxRowsI>
 struct RowsHandOff {
@@ -802,18 +810,23 @@ struct RowsHandOff {
 constexpr long long kHandOffTicks = 200000000;   // wall_clock64() counts at 100 MHz: two seconds, against a launch of ~50 us
 
 // register buffers B and LDS trips L of the instance for C columns: B (2C + 8) + 2C registers in phase 1, L (8C + 16) bytes of LDS
-// per thread (three workgroups per CU: 168 registers and ~53 KB)
-template <int C> struct FusedGeom { static constexpr int B = C <= 8 ? 4 : C <= 12 ? 3 : 2, L = C <= 8 ? 2 : 1; };
+// per thread (three workgroups per CU: 168 registers and ~53 KB).  H > 0: two passes, columns [0, H) in pass a - then the L = B trips
+// in LDS are the SAME trips as those in registers (B (2 (C - H) + 8) + 2C registers in pass b, 8 L H bytes of LDS per thread)
+template <int C> struct FusedGeom {
+    static constexpr int B = C <= 8 ? 4 : C <= 12 ? 3 : 2, L = C <= 8 ? 2 : C <= kFusedOnePassCols ? 1 : 2;
+    static constexpr int H = C <= kFusedOnePassCols ? 0 : C / 2;
+};
+constexpr int kFusedPassADepth = 3;              // register buffers of pass a (it keeps nothing in registers)
 static_assert(kFusedMaxCols % 4 == 0, "instances come in steps of four columns");
 
 #define NPG_LD_AGENT(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 #define NPG_ST_AGENT(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 
-template <int C>
+template <int C, int K0 = 0>
 struct RowTrip {
     float2 v[C];
     double w0, w1;
-    // the loads of RowPair<., VD>::load, for C columns (VD: t = wt of the two rows, column j is not read)
+    // the loads of RowPair<., VD>::load, for the C columns from K0 on (VD: t = wt of the two rows, column j is not read)
     template <bool VD>
     __device__ __forceinline__ void load(const GDev &d, int64_t blk, int j, double2 &t) {
         const int64_t r0 = 2 * (blk * kRB + threadIdx.x);
@@ -823,7 +836,7 @@ struct RowTrip {
 #pragma unroll
         for (int k = 0; k < C; ++k) {
             float2 f = make_float2(0.f, 0.f);
-            if (k <= jl) f = *reinterpret_cast<const float2 *>(d.Vf + (size_t)k * (size_t)d.ldv + (size_t)rc);
+            if (K0 + k <= jl) f = *reinterpret_cast<const float2 *>(d.Vf + (size_t)(K0 + k) * (size_t)d.ldv + (size_t)rc);
             if (!two) f.y = 0.f;
             v[k] = f;
         }
@@ -836,10 +849,13 @@ struct RowTrip {
 
 template <int C>
 __global__ void __launch_bounds__(kRB, 3) k_gmres_rows_fused(GDev d, int j) {
-    constexpr int B = FusedGeom<C>::B, L = FusedGeom<C>::L;
+    constexpr int B = FusedGeom<C>::B, L = FusedGeom<C>::L, H = FusedGeom<C>::H;
+    constexpr bool kTwo = H > 0;                               // phase 1 in two passes over the columns
+    constexpr int CB = C - H;                                  // columns [H, C) go through the register buffers
     static_assert(kMaxG == kHoShards * kMaxRowsI && kMaxRowsI % kHoShards == 0, "a shard is one slice of the fold");
-    __shared__ float2 lds_v[L * C * kRB];
-    __shared__ double lds_w[L * 2 * kRB];
+    static_assert(!kTwo || L == B, "two passes: a kept trip has one half in LDS and the other in registers");
+    __shared__ float2 lds_v[L * (kTwo ? H : C) * kRB];
+    __shared__ double lds_w[kTwo ? 1 : L * 2 * kRB];           // (two passes: the w pair of a kept trip is in registers)
     __shared__ double tmp[(kRB / 32) * kKP];
     __shared__ double red[kKP];
     __shared__ int sh_role, sh_ok;
@@ -862,18 +878,42 @@ __global__ void __launch_bounds__(kRB, 3) k_gmres_rows_fused(GDev d, int j) {
     const int64_t nblk = ((int64_t)d.n + 2 * kRB - 1) / (2 * kRB);
     const int nt = (int64_t)blockIdx.x < nblk ? (int)((nblk - 1 - blockIdx.x) / G) + 1 : 0;      // this workgroup's trips
     const int nreg = nt < B ? nt : B;                          // trips [nt - nreg, nt) end the pass in registers,
-    const int nlds = nt - nreg < L ? nt - nreg : L;            // [ne, ne + nlds) in LDS,
+    const int nlds = kTwo ? 0 : (nt - nreg < L ? nt - nreg : L);      // [ne, ne + nlds) in LDS (two passes: half of the last nreg),
     const int ne = nt - nreg - nlds;                           // [0, ne) are read again
     auto blk_of = [&](int t) { return (int64_t)blockIdx.x + (int64_t)t * G; };
 
     // ---- phase 1: v_j, the sums and ||w||^2 ----
-    RowTrip<C> buf[B];
+    RowTrip<CB, H> buf[B];
     double2 unused;
     double nrm = 0.0;
     {
         double acc[C];
 #pragma unroll
         for (int k = 0; k < C; ++k) acc[k] = 0.0;
+        if constexpr (kTwo) {
+            // pass a: the sums of columns [0, H) (all of them stored: H <= j), trip after trip; the last nreg trips' entries to LDS
+            constexpr int PA = kFusedPassADepth;
+            RowTrip<H> ba[PA];
+#pragma unroll
+            for (int s = 0; s < PA - 1; ++s)
+                if (s < nt) ba[s].template load<false>(d, blk_of(s), j, unused);
+            for (int base = 0; base < nt; base += PA) {
+#pragma unroll
+                for (int s = 0; s < PA; ++s) {
+                    const int t = base + s;
+                    if (t < nt) {
+                        if (t + PA - 1 < nt) ba[(s + PA - 1) % PA].template load<false>(d, blk_of(t + PA - 1), j, unused);
+                        const RowTrip<H> &cur = ba[s];
+#pragma unroll
+                        for (int k = 0; k < H; ++k) acc[k] += (double)cur.v[k].x * cur.w0 + (double)cur.v[k].y * cur.w1;
+                        if (t >= ne) {
+#pragma unroll
+                            for (int k = 0; k < H; ++k) lds_v[((t - ne) * H + k) * kRB + tid] = cur.v[k];
+                        }
+                    }
+                }
+            }
+        }
         double2 tq[B];
         const double inv_beta = 1.0 / Tj->beta;                // (T[j]: written by the Arnoldi launch before this one)
 #pragma unroll
@@ -886,7 +926,7 @@ __global__ void __launch_bounds__(kRB, 3) k_gmres_rows_fused(GDev d, int j) {
                 if (t < nt) {
                     const int sp = (s + B - 1) % B;            // the buffer of trip t - 1, whose arithmetic is done
                     if (t + B - 1 < nt) {
-                        if (t - 1 >= ne) {                     // (then t - 1 < ne + nlds: trip t - 1 is not among the last B)
+                        if (!kTwo && t - 1 >= ne) {            // (then t - 1 < ne + nlds: trip t - 1 is not among the last B)
                             const int sl = t - 1 - ne;
 #pragma unroll
                             for (int k = 0; k < C; ++k) lds_v[(sl * C + k) * kRB + tid] = buf[sp].v[k];
@@ -895,7 +935,7 @@ __global__ void __launch_bounds__(kRB, 3) k_gmres_rows_fused(GDev d, int j) {
                         }
                         buf[sp].template load<true>(d, blk_of(t + B - 1), j, tq[sp]);      // in flight during this trip's arithmetic
                     }
-                    RowTrip<C> &cur = buf[s];
+                    RowTrip<CB, H> &cur = buf[s];
                     const int64_t r0 = 2 * (blk_of(t) * kRB + tid);
                     const bool valid = r0 < d.n, two = r0 + 1 < d.n;
                     float2 vj = make_float2((float)(tq[s].x * inv_beta), (float)(tq[s].y * inv_beta));
@@ -908,10 +948,10 @@ __global__ void __launch_bounds__(kRB, 3) k_gmres_rows_fused(GDev d, int j) {
                     }
                     if (!two) vj.y = 0.f;
 #pragma unroll
-                    for (int k = 0; k < C; ++k)
-                        if (k == j) cur.v[k] = vj;             // (wave-uniform)
+                    for (int k = 0; k < CB; ++k)
+                        if (H + k == j) cur.v[k] = vj;         // (wave-uniform)
 #pragma unroll
-                    for (int k = 0; k < C; ++k) acc[k] += (double)cur.v[k].x * cur.w0 + (double)cur.v[k].y * cur.w1;
+                    for (int k = 0; k < CB; ++k) acc[H + k] += (double)cur.v[k].x * cur.w0 + (double)cur.v[k].y * cur.w1;
                     nrm += cur.w0 * cur.w0 + cur.w1 * cur.w1;
                 }
             }
@@ -1073,7 +1113,7 @@ __global__ void __launch_bounds__(kRB, 3) k_gmres_rows_fused(GDev d, int j) {
     }
 #pragma unroll
     for (int sl = 0; sl < L; ++sl) {
-        if (sl < nlds) {
+        if (!kTwo && sl < nlds) {
 #pragma unroll
             for (int k = 0; k < C; ++k) early.v[k] = lds_v[(sl * C + k) * kRB + tid];
             early.w0 = lds_w[(sl * 2 + 0) * kRB + tid];
@@ -1087,8 +1127,21 @@ __global__ void __launch_bounds__(kRB, 3) k_gmres_rows_fused(GDev d, int j) {
         for (int ro = 0; ro < B; ++ro) {
             if (ro == rot) {
 #pragma unroll
-                for (int r = 0; r < B; ++r)
-                    if (r < nreg) update(buf[(ro + r) % B], tr + r);
+                for (int r = 0; r < B; ++r) {
+                    if (r >= nreg) continue;
+                    if constexpr (kTwo) {                       // columns [0, H) as pass a left them in LDS slot r, then the registers
+                        const RowTrip<CB, H> &kept = buf[(ro + r) % B];
+#pragma unroll
+                        for (int k = 0; k < H; ++k) early.v[k] = lds_v[(r * H + k) * kRB + tid];
+#pragma unroll
+                        for (int k = 0; k < CB; ++k) early.v[H + k] = kept.v[k];
+                        early.w0 = kept.w0;
+                        early.w1 = kept.w1;
+                        update(early, tr + r);
+                    } else {
+                        update(buf[(ro + r) % B], tr + r);
+                    }
+                }
             }
         }
     }
@@ -1259,7 +1312,7 @@ using namespace npg;
 constexpr int kCfgLen = 18;
 
 // The environment switches that are read ONCE per process, by the first solve (DESIGN.md 4.2 lists every switch; NPG_GMRES_ONEFOLD,
-// NPG_GMRES_FUSEDROWS and NPG_HALO_OVERLAP_VERBOSE are read at every solve, where they are used)
+// NPG_GMRES_FUSEDROWS, NPG_GMRES_FUSED_COLS and NPG_HALO_OVERLAP_VERBOSE are read at every solve, where they are used)
 struct GmresKnobs {
     int split = env_int("NPG_GMRES_SPLIT", -1);
     int basis = env_int("NPG_GMRES_BASIS", 0);
@@ -1302,6 +1355,7 @@ struct GmresPlan {
     int reserve;                // ... CUs that the interior launch leaves free (RCCL)
     int grid_int, grid_bnd;     // ... workgroups of the interior and of the boundary launch
     int64_t xg_floats;          // floats of the gather-layout copy GDev::xg (0: the copy is not used)
+    int fused_cols;             // steps of up to this many columns (j < fused_cols) take the fused row launch (0: none does)
 };
 
 struct npg_gmres {
@@ -1348,7 +1402,9 @@ struct npg_gmres {
     int64_t n_ghost = 0;
     RowsHandOff *ho = nullptr;    // hand-off state of k_gmres_rows_fused (allocated and zeroed on first use)
     unsigned long long *h_ho = nullptr;   // pinned, two slots: its status word as each cycle left it
-    int fused_blocks = -1;        // workgroups of that kernel per CU (rows_fused_blocks_per_cu), -1: not asked yet
+    int fused_blocks[2] = {-1, -1};   // workgroups of that kernel per CU (rows_fused_blocks_per_cu), -1: not asked yet:
+                                  // [0] over the one-pass instances, [1] over all of them
+    int fused_cols = 0;           // GmresPlan::fused_cols of the last solve's plan (npg_gmres_fused_cols)
     bool fused_off = false;       // a hand-off has timed out: the workspace keeps to the separate launches
     int32_t cfg[kCfgLen] = {};    // the kernel instances the last solve launched (npg_gmres_last_config)
     bool have_cfg = false;
@@ -1392,7 +1448,8 @@ static void launch_rows_fused(const GDev &d, int j, hipStream_t st) {
         case 1: hipLaunchKernelGGL(k_gmres_rows_fused<4>, dim3(d.GR), dim3(kRB), 0, st, d, j); break;
         case 2: hipLaunchKernelGGL(k_gmres_rows_fused<8>, dim3(d.GR), dim3(kRB), 0, st, d, j); break;
         case 3: hipLaunchKernelGGL(k_gmres_rows_fused<12>, dim3(d.GR), dim3(kRB), 0, st, d, j); break;
-        default: hipLaunchKernelGGL(k_gmres_rows_fused<16>, dim3(d.GR), dim3(kRB), 0, st, d, j); break;
+        case 4: hipLaunchKernelGGL(k_gmres_rows_fused<16>, dim3(d.GR), dim3(kRB), 0, st, d, j); break;
+        default: hipLaunchKernelGGL(k_gmres_rows_fused<20>, dim3(d.GR), dim3(kRB), 0, st, d, j); break;
     }
 }
 // Workgroups of k_gmres_rows_fused that one CU holds at a time, over the instances: the occupancy query's answer, corrected as it
@@ -1407,9 +1464,11 @@ static int rows_fused_blocks() {
     }
     return nb;
 }
-static int rows_fused_blocks_per_cu() {
+// `cols`: the widest instance a cycle will launch (kFusedOnePassCols or kFusedMaxCols) - the minimum is over the instances up to it.
+static int rows_fused_blocks_per_cu(int cols) {
     constexpr int kSgprMax = 112;
-    const int api = std::min({rows_fused_blocks<4>(), rows_fused_blocks<8>(), rows_fused_blocks<12>(), rows_fused_blocks<16>()});
+    int api = std::min({rows_fused_blocks<4>(), rows_fused_blocks<8>(), rows_fused_blocks<12>(), rows_fused_blocks<16>()});
+    if (cols > kFusedOnePassCols) api = std::min(api, rows_fused_blocks<20>());
     return std::min({api, 8, 800 / ((kSgprMax + 15) / 16 * 16 + 16)});
 }
 
@@ -1489,7 +1548,7 @@ static int launch_cycle_L(const GmresPlan &p, hipStream_t st, hipEvent_t *pev, n
         if (dist && (rc = halo_exchange_raw(ws->halo, d.wt, g32, d.gslot, d.xg.p))) return rc;
         if (d.split) {
             launch_arnoldi_split<L>(d, p.grid, j, 0, p.a_nt, st, pev ? pev[2 * j] : nullptr, pev ? pev[2 * j + 1] : nullptr);
-            if (d.fusedrows && j < kFusedMaxCols) {
+            if (j < p.fused_cols) {
                 launch_rows_fused(d, j, st);     // sums, fold and update in one resident launch
                 continue;
             }
@@ -1707,9 +1766,18 @@ static void gmres_plan(GmresPlan &p, npg_gmres *ws, const npg_csr *A, int precon
     // NPG_GMRES_FUSEDROWS=0: the separate launches).  It is the onefold arrangement in one kernel, so it selects that arrangement
     // for the cycle's other steps too; NPG_GMRES_ONEFOLD=0 chooses among the separate launches, i.e. with NPG_GMRES_FUSEDROWS=0 or
     // where the fused kernel does not apply.  Only on a grid that is resident as a whole: the hand-off waits for every workgroup.
+    // NPG_GMRES_FUSED_COLS: the widest fused step - 20 (the default: every instance) or 16 (the one-pass instances only; steps of
+    // 17-20 columns then take the separate launches, as they do where the grid is admitted for the one-pass instances alone).
     if (!dist && d.split && d.fast && d.Vf && !d.rev && !ws->fused_off && env_int("NPG_GMRES_FUSEDROWS", 1) != 0) {
-        if (ws->fused_blocks < 0) ws->fused_blocks = rows_fused_blocks_per_cu();
-        if (d.GR <= ctx->num_cu * ws->fused_blocks) d.fusedrows = d.onefold = d.vdots = 1;
+        if (ws->fused_blocks[0] < 0) {
+            ws->fused_blocks[0] = rows_fused_blocks_per_cu(kFusedOnePassCols);
+            ws->fused_blocks[1] = rows_fused_blocks_per_cu(kFusedMaxCols);
+        }
+        const bool wide = env_int("NPG_GMRES_FUSED_COLS", kFusedMaxCols) > kFusedOnePassCols && d.GR <= ctx->num_cu * ws->fused_blocks[1];
+        if (wide || d.GR <= ctx->num_cu * ws->fused_blocks[0]) {
+            d.fusedrows = d.onefold = d.vdots = 1;
+            p.fused_cols = wide ? kFusedMaxCols : kFusedOnePassCols;
+        }
     }
     const bool one1 = dist || d.onefold;        // (slot 0 of the all-reduced rows is free on one GPU)
     d.Q1 = one1 ? ws->Rg : d.P1;
@@ -1936,11 +2004,11 @@ static int run_cycles(npg_gmres *ws, GmresPlan &p, int64_t max_cycles, Snap &las
     if (trace)
         fprintf(stderr,
                 "[npg gmres] %s: %lld cycle launches, %.1f us host time per launch, %d iterations, %.1f us wall per "
-                "iteration, %d second GS passes, fused rows %d (row grid %d, %d workgroups per CU admitted)\n",
+                "iteration, %d second GS passes, fused rows %d up to %d columns (row grid %d, %d workgroups per CU admitted)\n",
                 p.use_graph ? "graph" : "eager", (long long)n_launch, 1e6 * t_launch / (double)n_launch, last.iter,
                 1e6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() /
                     std::max(1, last.iter),
-                last.nreorth, p.d.fusedrows, p.d.GR, ws->fused_blocks);
+                last.nreorth, p.d.fusedrows, p.fused_cols, p.d.GR, ws->fused_blocks[p.fused_cols > kFusedOnePassCols ? 1 : 0]);
     return NPG_OK;
 }
 
@@ -1953,6 +2021,7 @@ static int gmres_report(npg_gmres *ws, const GmresPlan &p, const Snap &last, std
                                   p.a_nt, p.grid, d.split ? d.GR : d.G2, d.n, d.mem, d.lazy2, d.fusedrows};
     memcpy(ws->cfg, cfg, sizeof cfg);
     ws->have_cfg = true;
+    ws->fused_cols = p.fused_cols;
     // a replayed cycle reports communication timeouts through the status word only
     if (int rc = p.dist ? comm_check(ws->ctx) : NPG_OK) return rc;
     if (stats) {
@@ -2103,6 +2172,8 @@ NPG_API int npg_gmres_last_config(const npg_gmres *ws, int32_t *cfg, int n) {
     memcpy(cfg, ws->cfg, (size_t)k * sizeof(int32_t));
     return k;
 }
+
+NPG_API int npg_gmres_fused_cols(const npg_gmres *ws) { return (ws && ws->have_cfg) ? ws->fused_cols : 0; }
 
 NPG_API int64_t npg_gmres_history(npg_gmres *ws, double *buf, int64_t cap) {
     if (!ws || !buf || cap <= 0) return 0;

@@ -102,6 +102,11 @@ class GmresWorkspace(_Workspace):
         k = L.lib().npg_gmres_last_config(self.h, L.ptr(buf), buf.size)
         return {name: int(v) for name, v in zip(self.CONFIG_KEYS, buf[:k])}
 
+    def fused_cols(self):
+        """the widest step, in basis columns, that the last solve gave to the resident fused row launch (npg_gmres_fused_cols):
+        20, 16 (NPG_GMRES_FUSED_COLS=16) or 0 (separate launches, or no solve yet)"""
+        return int(L.lib().npg_gmres_fused_cols(self.h))
+
     def set_split(self, mode):
         """-1: by size (default), 0: fused Arnoldi kernel, 1: split kernels + column-major basis (npg_gmres_set_split)"""
         L.check(L.lib().npg_gmres_set_split(self.h, int(mode)))
