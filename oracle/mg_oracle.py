@@ -1,5 +1,5 @@
-"""ORACLE (test infrastructure) - host restatement of the multigrid V-cycle and the flexible GMRES of
-nupgcm_amd/csrc/mg.hip, in numpy / scipy.
+"""ORACLE (test infrastructure) - host restatement of the multigrid V-cycle (nupgcm_amd/csrc/mg.hip) and
+the flexible GMRES (nupgcm_amd/csrc/fgmres.hip), in numpy / scipy.
 
 This is NEW work with no counterpart in the reference (its only non-diagonal preconditioner is the experimental
 BlockDiagonalPreconditioner of /root/reference/src/preconditioners.jl:53-125): there is nothing of the reference to pin it

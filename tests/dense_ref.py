@@ -1,4 +1,4 @@
-"""Inputs, extended-precision reference and componentwise error bounds for the explicit dense inverse of nupgcm_amd/csrc/mg.hip
+"""Inputs, extended-precision reference and componentwise error bounds for the explicit dense inverse of nupgcm_amd/csrc/dense_inv.hip
 (k_dense_gemv_part<double> / k_dense_gemv_part4 / k_dense_gemv_part8h + k_dense_gemv_sum) - the yardstick of
 tests/test_gpu_dense_inverse.py, guarded without a GPU by tests/test_dense_ref.py.
 

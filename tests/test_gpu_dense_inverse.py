@@ -1,4 +1,4 @@
-"""The explicit dense inverse of csrc/mg.hip at the edge sizes of its kernels, against an extended-precision reference with
+"""The explicit dense inverse of csrc/dense_inv.hip at the edge sizes of its kernels, against an extended-precision reference with
 derived componentwise bounds (tests/dense_ref.py): k_dense_gemv_part<double>, k_dense_gemv_part4 (fp32 storage),
 k_dense_gemv_part8h (column-scaled fp16 storage), k_dense_gemv_sum, k_to_float_ld, k_to_half_ld, k_col_absmax.
 

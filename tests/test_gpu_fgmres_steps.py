@@ -1,4 +1,4 @@
-"""The row kernels of the flexible GMRES in csrc/mg.hip - k_mdot<NG>, k_mupdate<NG>, k_sum_partials, k_combine_z - in every
+"""The row kernels of the flexible GMRES in csrc/fgmres.hip - k_mdot<NG>, k_mupdate<NG>, k_sum_partials, k_combine_z - in every
 instance and at their edges, iteration by iteration against oracle.mg_oracle.fgmres (no preconditioner).
 
   memory 1, 8, 9, 16, 17, 23     the edges of by_groups (NG = 1: k <= 8, NG = 2: k <= 16, NG = 3 beyond) and the creation limit

@@ -1,4 +1,4 @@
-"""General preconditioners of the inversion on the GPU (csrc/mg.hip) through the C ABI: flexible GMRES, the multigrid V-cycle
+"""General preconditioners of the inversion on the GPU (csrc/mg.hip, dense_inv.hip, fgmres.hip) through the C ABI: flexible GMRES, the multigrid V-cycle
 (new work) and the reference's BlockDiagonalPreconditioner (src/preconditioners.jl:53-125).
 
 What is checked: (1) FGMRES against the host restatement iteration by iteration; (2) one V-cycle against the host restatement
@@ -380,6 +380,51 @@ def test_preconditioner_abi_argument_errors(arch):
     with pytest.raises(L.DeviceError, match="broke down"):
         Pb.apply(r, z)
     lib.npg_precond_destroy(pc) if pc else None
+
+
+def test_refused_set_calls_leave_the_level_and_the_block_unset(arch):
+    """setters commit on success: a set call the library refuses half-way leaves the level / block unset, so the corrected call
+    is accepted and the handle then applies exactly what a fresh handle does (bit for bit).  The multigrid level is refused
+    through S: valid shapes, but stored by node records, which npg_csr_inv_diag does not take.  (No application between the
+    refused and the corrected call: that is not a state the library promises anything about.)"""
+    from nupgcm_amd import _lib as L
+    ctx = arch.ctx
+    lib = L.lib()
+    I = npg.on_architecture(arch, sp.csr_matrix(sp.eye(12)))
+    G = npg.on_architecture(arch, sp.csr_matrix(np.ones((8, 4))))
+    D = npg.on_architecture(arch, sp.csr_matrix(np.ones((4, 8))))
+    Di = npg.on_architecture(arch, sp.csr_matrix(sp.eye(8)))
+    # S: one full node ({K, C} block on rows 0-1, K on row 2) and one plain row behind it - the structure npg_csr_block_nodes takes
+    Sh = sp.csr_matrix(np.array([[2.0, 0.5, 0, 0], [-0.5, 2.0, 0, 0], [0, 0, 2.0, 0], [0, 0, 0, 3.0]]))
+    S, Sb = npg.on_architecture(arch, Sh), npg.on_architecture(arch, Sh)
+    assert Sb.block_nodes(1, 0) and Sb.storage()[0] > 0 and S.storage()[0] == 0       # the conversion really happened
+    r = npg.DeviceVector.from_host(ctx, np.sin(np.arange(12) * 0.37) + 0.1)
+
+    def one_level():
+        P = mgm.GeneralPreconditioner(ctx, L.NPG_PC_MG, 1)
+        L.check(lib.npg_precond_mg_set_params(P.h, 2.5, 0.7, 3, 2, 2, 2))              # (two smoothing steps are the whole cycle)
+        return P
+    P, Pf = one_level(), one_level()
+    assert lib.npg_precond_mg_set_level(P.h, 0, I.h, 8, G.h, D.h, Di.h, Sb.h, None, None) != 0
+    assert b"npg_csr_inv_diag: the matrix is stored by node records" in lib.npg_last_error()
+    assert lib.npg_precond_mg_set_level(P.h, 0, I.h, 8, G.h, D.h, Di.h, S.h, None, None) == 0, lib.npg_last_error()
+    assert lib.npg_precond_mg_set_level(Pf.h, 0, I.h, 8, G.h, D.h, Di.h, S.h, None, None) == 0
+    z = P.apply(r, npg.DeviceVector(ctx, 12)).to_host()
+    zf = Pf.apply(r, npg.DeviceVector(ctx, 12)).to_host()
+    assert np.all(np.isfinite(zf)) and np.any(zf != 0.0) and z.tobytes() == zf.tobytes()
+
+    # the block-diagonal kind: a non-square A behind a valid offset is refused, the corrected call is accepted
+    A2 = npg.on_architecture(arch, sp.csr_matrix(sp.eye(12) * 2.0))
+    jac = npg.DeviceVector.from_host(ctx, np.full(12, 0.5))
+    Pb, Pbf = (mgm.GeneralPreconditioner(ctx, L.NPG_PC_BLOCKDIAG, 1) for _ in range(2))
+    assert lib.npg_precond_blockdiag_set(Pb.h, 0, 0, G.h, jac.h, 12, 1e-10, 1e-10) != 0 and b"square" in lib.npg_last_error()
+    assert lib.npg_precond_blockdiag_set(Pb.h, 0, 0, A2.h, jac.h, 12, 1e-10, 1e-10) == 0, lib.npg_last_error()
+    assert lib.npg_precond_blockdiag_set(Pbf.h, 0, 0, A2.h, jac.h, 12, 1e-10, 1e-10) == 0
+    z = Pb.apply(r, npg.DeviceVector(ctx, 12)).to_host()
+    zf = Pbf.apply(r, npg.DeviceVector(ctx, 12)).to_host()
+    # (A = 2 I: the inner CG stops at |A x - r| <= 1e-10 (1 + |r|), i.e. |x - r / 2| <= 0.5e-10 (1 + |r|) < 1e-9 |r|, |r| = 2.5)
+    rh = r.to_host()
+    assert np.linalg.norm(zf - 0.5 * rh) < 1e-9 * np.linalg.norm(rh) and z.tobytes() == zf.tobytes()
 
 
 def test_zline_smoother_on_the_channel_basin(arch):
