@@ -466,6 +466,12 @@ int npg_fe_evolution_rhs(npg_fe *fe, int scheme, double dt, double N2, double th
 /* advection part alone (for parity tests of src/model.jl:292-300) */
 int npg_fe_advection_rhs(npg_fe *fe, int scheme, double dt, double N2, const npg_vec *b, const npg_vec *b_prev,
                          const npg_vec *x_inv, const npg_vec *x_inv_prev, npg_vec *out);
+/* The tangent of the advection load:
+ * out_i = int ( u_base . grad db + du . grad b_base + du_z N2 ) phi_i over the free buoyancy DoFs.  b_base / x_base are read
+ * through the engine's Dirichlet tables (as npg_fe_advection_rhs reads b / x_inv); db / dx are perturbations: a negative
+ * table entry reads 0.  Always fp64, whatever npg_fe_set_precision says. */
+int npg_fe_tangent_rhs(npg_fe *fe, double N2, const npg_vec *b_base, const npg_vec *x_base,
+                       const npg_vec *db, const npg_vec *dx, npg_vec *out);
 
 /* Matrix (re)assembly into an existing CSR pattern (values are overwritten).
  * which: */

@@ -110,6 +110,12 @@ class DeviceFE:
                                              out.h))
         return out
 
+    def tangent_rhs(self, N2, b_base, x_base, db, dx, out):
+        """out_i = int (u_base . grad db + du . grad b_base + du_z N2) phi_i: the tangent of the advection load (npg_fe_tangent_rhs);
+        the base state carries the engine's Dirichlet values, the perturbation none"""
+        L.check(L.lib().npg_fe_tangent_rhs(self.h, float(N2), b_base.h, x_base.h, db.h, dx.h, out.h))
+        return out
+
     def evolution_rhs(self, scheme, dt, N2, theta, b, b_prev, x_inv, x_inv_prev, rhs_diff, rhs_flux, rhs_M, rhs_h, rhs_v,
                       y):
         hh = [None if v is None else v.h for v in (rhs_diff, rhs_flux, rhs_M, rhs_h, rhs_v)]

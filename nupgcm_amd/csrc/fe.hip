@@ -655,6 +655,12 @@ static int gather_pass2(npg_fe *fe, const RhsTerms &rt, npg_vec *out) {
     return NPG_OK;
 }
 
+// pass 2 alone, for a translation unit whose own pass 1 has filled fe->loc on the engine's stream (linearized.hip)
+int npg::fe_gather_rows(npg_fe *fe, npg_vec *out) {
+    RhsTerms rt{};
+    return gather_pass2(fe, rt, out);
+}
+
 NPG_API int npg_fe_advection_rhs(npg_fe *fe, int scheme, double dt, double N2, const npg_vec *b, const npg_vec *b_prev,
                                  const npg_vec *x_inv, const npg_vec *x_inv_prev, npg_vec *out) {
     NPG_REQUIRE(fe, "npg_fe_advection_rhs: NULL handle");

@@ -106,3 +106,8 @@ struct npg_fe {
     double *scratch_vec = nullptr;  // n_b doubles
     int precision = NPG_FE_FP64;    // arithmetic of the element-local work (npg_fe_set_precision)
 };
+
+namespace npg {
+// out[r] = the sum of row r's entries of fe->loc in cell order: fe.hip's k_gather_rows with empty RhsTerms, on the engine's stream
+int fe_gather_rows(npg_fe *fe, npg_vec *out);
+}  // namespace npg

@@ -32,6 +32,7 @@
 
 #include "../../include/nupgcm_hip.h"
 #include "../csrc/cell_view.h"
+#include "../csrc/tangent_core.h"
 
 #define NPG_API extern "C" __attribute__((visibility("default")))
 
@@ -968,6 +969,24 @@ NPG_API int npg_fe_evolution_rhs(npg_fe *fe, int scheme, double dt, double N2, d
     const int rc = advection_pass1(fe, scheme, dt, N2, b, b_prev, x_inv, x_inv_prev);
     if (rc) return rc;
     gather_rows(fe, theta, dt, rhs_diff, rhs_flux, rhs_M, rhs_h, rhs_v, y->d);
+    return NPG_OK;
+}
+// the tangent of the advection load (csrc/linearized.hip on the host; the arithmetic and its order are csrc/tangent_core.h)
+NPG_API int npg_fe_tangent_rhs(npg_fe *fe, double N2, const npg_vec *b_base, const npg_vec *x_base, const npg_vec *db, const npg_vec *dx,
+                               npg_vec *out) {
+    REQUIRE(fe, "npg_fe_tangent_rhs: NULL handle");
+    const bool any_null = !(b_base && x_base && db && dx && out);
+    REQUIRE_OK(npg::check_tangent(any_null, N2, fe->n_inv, fe->n_b, any_null ? 0 : b_base->n, any_null ? 0 : x_base->n, any_null ? 0 : db->n,
+                                  any_null ? 0 : dx->n, any_null ? 0 : out->n, true));
+    const HostShape s = host_shape(fe);
+    const HostView t = host_view(fe);
+    const int64_t nc = fe->ncell;
+#pragma omp parallel for schedule(static)
+    for (int64_t cell = 0; cell < nc; ++cell) {
+        if (fe->nb == 10) npg::cell_tangent<10>(s, t, fe->nq, N2, b_base->d, x_base->d, db->d, dx->d, cell, fe->loc.data());
+        else npg::cell_tangent<4>(s, t, fe->nq, N2, b_base->d, x_base->d, db->d, dx->d, cell, fe->loc.data());
+    }
+    gather_rows(fe, 0.0, 0.0, nullptr, nullptr, nullptr, nullptr, nullptr, out->d);
     return NPG_OK;
 }
 // rhs_diff = -N2 int kappa_v d_z phi_i        (src/evolution.jl:269-278)
