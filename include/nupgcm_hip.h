@@ -472,6 +472,12 @@ int npg_fe_advection_rhs(npg_fe *fe, int scheme, double dt, double N2, const npg
  * table entry reads 0.  Always fp64, whatever npg_fe_set_precision says. */
 int npg_fe_tangent_rhs(npg_fe *fe, double N2, const npg_vec *b_base, const npg_vec *x_base,
                        const npg_vec *db, const npg_vec *dx, npg_vec *out);
+/* The adjoint of the tangent load: for a multiplier lam on the free buoyancy DoFs (a Dirichlet DoF reads 0)
+ * out_b_j = int lam_h u_base . grad phi_j and out_x_(j,a) = int lam_h (d_a b_base + N2 delta_az) phi^u_j (pressure rows: 0), so that
+ * <lam, npg_fe_tangent_rhs(db, dx)> = <out_b, db> + <out_x, dx> at the same base state.  out_b holds n_b, out_x n_inv entries;
+ * neither may be an input.  Always fp64. */
+int npg_fe_tangent_adjoint(npg_fe *fe, double N2, const npg_vec *b_base, const npg_vec *x_base,
+                           const npg_vec *lam, npg_vec *out_b, npg_vec *out_x);
 
 /* Matrix (re)assembly into an existing CSR pattern (values are overwritten).
  * which: */

@@ -16,7 +16,7 @@ from .integrals import BudgetRecorder, Budgets, MeshIntegrals
 from .interior import InteriorForcing
 from .inversion import InversionToolkit, build_A_inversion, build_B_inversion, build_b_inversion
 from .io import save_checkpoint, save_state, save_vtk, set_out_dir, set_state_from_file
-from .linearized import EigenModes, LinearizedModel
+from .linearized import EigenModes, LinearizedModel, ModePairs
 from .iterative_solvers import BatchedCgWorkspace, CgWorkspace, Diagonal, GmresWorkspace, IterativeSolverToolkit, MgsGmresWorkspace, iterative_solve
 from .multigrid import BlockDiagonalPreconditioner, DenseInversePreconditioner, FgmresWorkspace, GeneralPreconditioner, MultigridPreconditioner
 from .model import BlowUp, Model, State, evolve, invert, run, set_b, sync_flow

@@ -116,6 +116,12 @@ class DeviceFE:
         L.check(L.lib().npg_fe_tangent_rhs(self.h, float(N2), b_base.h, x_base.h, db.h, dx.h, out.h))
         return out
 
+    def tangent_adjoint(self, N2, b_base, x_base, lam, out_b, out_x):
+        """(out_b, out_x) with <lam, tangent_rhs(db, dx)> = <out_b, db> + <out_x, dx>: the adjoint of the tangent load at the same
+        base state (npg_fe_tangent_adjoint); the pressure rows of out_x are 0"""
+        L.check(L.lib().npg_fe_tangent_adjoint(self.h, float(N2), b_base.h, x_base.h, lam.h, out_b.h, out_x.h))
+        return out_b, out_x
+
     def evolution_rhs(self, scheme, dt, N2, theta, b, b_prev, x_inv, x_inv_prev, rhs_diff, rhs_flux, rhs_M, rhs_h, rhs_v,
                       y):
         hh = [None if v is None else v.h for v in (rhs_diff, rhs_flux, rhs_M, rhs_h, rhs_v)]

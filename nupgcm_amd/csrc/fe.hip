@@ -661,6 +661,15 @@ int npg::fe_gather_rows(npg_fe *fe, npg_vec *out) {
     return gather_pass2(fe, rt, out);
 }
 
+// and through an inverted index and a local buffer of the caller's choice (tangent_adjoint.hip: gptr / loc, then iptr / loc_inv)
+int npg::fe_gather_index(npg_fe *fe, const int64_t *ptr, const int32_t *idx, const double *loc, int64_t n, npg_vec *out) {
+    NPG_REQUIRE(out && out->n == n, "fe: output vector must have %lld entries", (long long)n);
+    const int grid = std::min(2048, cell_grid(n));
+    hipLaunchKernelGGL(k_gather_rows, dim3(grid), dim3(kBlock), 0, fe->ctx->stream, ptr, idx, loc, n, RhsTerms{}, out->d);
+    NPG_HIP(hipGetLastError());
+    return NPG_OK;
+}
+
 NPG_API int npg_fe_advection_rhs(npg_fe *fe, int scheme, double dt, double N2, const npg_vec *b, const npg_vec *b_prev,
                                  const npg_vec *x_inv, const npg_vec *x_inv_prev, npg_vec *out) {
     NPG_REQUIRE(fe, "npg_fe_advection_rhs: NULL handle");

@@ -95,6 +95,7 @@ struct npg_fe {
     int64_t n_b_diri = 0;           // entries of the buoyancy Dirichlet value table (tracers keep one of their own per tracer)
     std::vector<void *> allocs;
     double *loc = nullptr;          // [nb][ncell]
+    double *loc_inv = nullptr;      // [34][ncell], as iidx addresses it; allocated by the first npg_fe_tangent_adjoint
     int64_t *gptr = nullptr;        // inverted index of the buoyancy rows (vector pass 2, matrix rows)
     int32_t *gidx = nullptr;
     int64_t *iptr = nullptr;        // inverted index of the inversion rows [u; p]: (local DoF l) * ncell + cell
@@ -110,4 +111,6 @@ struct npg_fe {
 namespace npg {
 // out[r] = the sum of row r's entries of fe->loc in cell order: fe.hip's k_gather_rows with empty RhsTerms, on the engine's stream
 int fe_gather_rows(npg_fe *fe, npg_vec *out);
+// the same kernel through any inverted index: out[r] = the sum of loc[idx[k]], ptr[r] <= k < ptr[r + 1], r < n = out->n
+int fe_gather_index(npg_fe *fe, const int64_t *ptr, const int32_t *idx, const double *loc, int64_t n, npg_vec *out);
 }  // namespace npg

@@ -1,0 +1,70 @@
+// The adjoint of the tangent load (npg_fe_tangent_adjoint): for a multiplier lam on the free buoyancy DoFs, g_b and g_x
+// with <lam, T(db, dx)> = <g_b, db> + <g_x, dx> for the T of linearized.hip at the same base state - what the transposed Jacobian of
+// the linearised model (nupgcm_amd/linearized.py: apply_adjoint) needs beside a transposed inversion.  The arithmetic, the order of its
+// sums and the argument checks are tangent_adjoint_core.h's, shared with the host library.
+//   pass 1  k_tangent_adjoint_local<NB>  one lane per cell at kBlock, the shape tables from LDS (stage_tables), the two outputs one after
+//                                        the other so that one of u_base[30] / b_base[NB] is live beside lam[NB]; writes loc[j][cell] and
+//                                        the 30 velocity planes of loc_inv[l][cell]
+//   pass 2  the engine's fixed-order gather of fe.hip, twice: gptr / gidx over loc, iptr / iidx over loc_inv
+// loc_inv (34 ncell doubles, the layout iidx addresses) is allocated by the first call; its four pressure planes are zeroed once and
+// never written, so the pressure rows of g_x are sums of zeros.  No atomics: the bits of the host library on every call.  Always fp64.
+#include "common.h"
+#include "device_utils.h"
+#include "fe_dev.h"
+#include "tangent_adjoint_core.h"
+
+namespace npg {
+
+template <int NB>
+__global__ void __launch_bounds__(kBlock) k_tangent_adjoint_local(FeDev d, double N2, const double *__restrict__ b_base,
+                                                                  const double *__restrict__ x_base, const double *__restrict__ lam,
+                                                                  double *__restrict__ loc_b, double *__restrict__ loc_x) {
+    __shared__ FeTables t;
+    stage_tables(d, t);
+    const int64_t cell = blockIdx.x * (int64_t)kBlock + threadIdx.x;
+    if (cell >= d.ncell) return;
+    cell_tangent_adjoint<NB>(t, cell_view(d), d.nq, N2, b_base, x_base, lam, cell, loc_b, loc_x);
+}
+
+static int ensure_loc_inv(npg_fe *fe) {
+    if (fe->loc_inv) return NPG_OK;
+    const size_t nc = (size_t)fe->d.ncell;
+    double *p = nullptr;
+    NPG_HIP(hipMalloc((void **)&p, 34 * nc * sizeof(double)));
+    const hipError_t e = hipMemsetAsync(p + 30 * nc, 0, 4 * nc * sizeof(double), fe->ctx->stream);
+    if (e != hipSuccess) {      // nothing is kept: the next call starts over
+        hipFree(p);
+        NPG_HIP(e);
+    }
+    fe->allocs.push_back(p);
+    fe->loc_inv = p;
+    return NPG_OK;
+}
+
+}  // namespace npg
+
+using namespace npg;
+
+NPG_API int npg_fe_tangent_adjoint(npg_fe *fe, double N2, const npg_vec *b_base, const npg_vec *x_base, const npg_vec *lam, npg_vec *out_b,
+                                   npg_vec *out_x) {
+    NPG_REQUIRE(fe, "npg_fe_tangent_adjoint: NULL handle");
+    const bool any_null = !(b_base && x_base && lam && out_b && out_x);
+    const bool aliased = !any_null && adjoint_outputs_alias(b_base, x_base, lam, out_b, out_x);
+    NPG_REQUIRE_OK(check_tangent_adjoint(any_null, aliased, N2, fe->n_inv, fe->n_b, any_null ? 0 : b_base->n, any_null ? 0 : x_base->n,
+                                         any_null ? 0 : lam->n, any_null ? 0 : out_b->n, any_null ? 0 : out_x->n,
+                                         any_null || (b_base->ctx == fe->ctx && x_base->ctx == fe->ctx && lam->ctx == fe->ctx &&
+                                                      out_b->ctx == fe->ctx && out_x->ctx == fe->ctx)));
+    NPG_HIP(hipSetDevice(fe->ctx->device));
+    int rc = ensure_loc_inv(fe);
+    if (rc) return rc;
+    const dim3 grid((unsigned)((fe->d.ncell + kBlock - 1) / kBlock)), block(kBlock);
+    if (fe->d.nb == 10)
+        hipLaunchKernelGGL(k_tangent_adjoint_local<10>, grid, block, 0, fe->ctx->stream, fe->d, N2, b_base->d, x_base->d, lam->d, fe->loc,
+                           fe->loc_inv);
+    else
+        hipLaunchKernelGGL(k_tangent_adjoint_local<4>, grid, block, 0, fe->ctx->stream, fe->d, N2, b_base->d, x_base->d, lam->d, fe->loc,
+                           fe->loc_inv);
+    NPG_HIP(hipGetLastError());
+    if ((rc = fe_gather_index(fe, fe->gptr, fe->gidx, fe->loc, fe->n_b, out_b))) return rc;
+    return fe_gather_index(fe, fe->iptr, fe->iidx, fe->loc_inv, fe->n_inv, out_x);
+}

@@ -33,6 +33,7 @@
 #include "../../include/nupgcm_hip.h"
 #include "../csrc/cell_view.h"
 #include "../csrc/tangent_core.h"
+#include "../csrc/tangent_adjoint_core.h"
 
 #define NPG_API extern "C" __attribute__((visibility("default")))
 
@@ -766,6 +767,7 @@ struct npg_fe {
     std::vector<int64_t> gptr, iptr;                                              // inverted indices: row -> (cell, local DoF)
     std::vector<int64_t> gidx, iidx;                                              // cell * nb + i   /   cell * 34 + l
     std::vector<double> coef[4], kv0, hcell, loc;                                 // nu, kappa_h, kappa_v, f: [ncell][nq]
+    std::vector<double> loc_inv;                                                  // [ncell][34], as iidx addresses it (npg_fe_tangent_adjoint)
 };
 static inline double fval(const double *x, const std::vector<double> &diri, int32_t idx) { return npg::field_val(x, diri.data(), idx); }
 namespace {
@@ -987,6 +989,33 @@ NPG_API int npg_fe_tangent_rhs(npg_fe *fe, double N2, const npg_vec *b_base, con
         else npg::cell_tangent<4>(s, t, fe->nq, N2, b_base->d, x_base->d, db->d, dx->d, cell, fe->loc.data());
     }
     gather_rows(fe, 0.0, 0.0, nullptr, nullptr, nullptr, nullptr, nullptr, out->d);
+    return NPG_OK;
+}
+// the adjoint of the tangent load (csrc/tangent_adjoint.hip on the host; the arithmetic and its order are csrc/tangent_adjoint_core.h)
+NPG_API int npg_fe_tangent_adjoint(npg_fe *fe, double N2, const npg_vec *b_base, const npg_vec *x_base, const npg_vec *lam, npg_vec *out_b,
+                                   npg_vec *out_x) {
+    REQUIRE(fe, "npg_fe_tangent_adjoint: NULL handle");
+    const bool any_null = !(b_base && x_base && lam && out_b && out_x);
+    const bool aliased = !any_null && npg::adjoint_outputs_alias(b_base, x_base, lam, out_b, out_x);
+    REQUIRE_OK(npg::check_tangent_adjoint(any_null, aliased, N2, fe->n_inv, fe->n_b, any_null ? 0 : b_base->n, any_null ? 0 : x_base->n,
+                                          any_null ? 0 : lam->n, any_null ? 0 : out_b->n, any_null ? 0 : out_x->n, true));
+    const HostShape s = host_shape(fe);
+    const HostView t = host_view(fe);
+    const int64_t nc = fe->ncell;
+    if (fe->loc_inv.empty()) fe->loc_inv.assign((size_t)nc * 34, 0.0);      // the pressure entries stay the zeros set here
+#pragma omp parallel for schedule(static)
+    for (int64_t cell = 0; cell < nc; ++cell) {
+        if (fe->nb == 10) npg::cell_tangent_adjoint<10>(s, t, fe->nq, N2, b_base->d, x_base->d, lam->d, cell, fe->loc.data(), fe->loc_inv.data());
+        else npg::cell_tangent_adjoint<4>(s, t, fe->nq, N2, b_base->d, x_base->d, lam->d, cell, fe->loc.data(), fe->loc_inv.data());
+    }
+    gather_rows(fe, 0.0, 0.0, nullptr, nullptr, nullptr, nullptr, nullptr, out_b->d);
+    const int64_t n = fe->n_inv;
+#pragma omp parallel for schedule(static)
+    for (int64_t r = 0; r < n; ++r) {
+        double acc = 0.0;
+        for (int64_t k = fe->iptr[(size_t)r]; k < fe->iptr[(size_t)r + 1]; ++k) acc += fe->loc_inv[(size_t)fe->iidx[(size_t)k]];
+        out_x->d[r] = acc;
+    }
     return NPG_OK;
 }
 // rhs_diff = -N2 int kappa_v d_z phi_i        (src/evolution.jl:269-278)

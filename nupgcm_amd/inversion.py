@@ -39,7 +39,12 @@ def build_A_inversion(arch, fe_data, params, nu, A=None, structural=False):
     fe.set_coeff("f", params.f)
     if A is None:
         A = fe.new_matrix("A", structural=structural or full)
-    return fe.assemble(L.NPG_MAT_A, A, scale=params.alpha ** 2 * params.eps ** 2, full_stress=full)
+    return assemble_A_inversion(fe, params, A, full)
+
+
+def assemble_A_inversion(fe, params, A, full_stress):
+    """the values of the inversion matrix into the pattern A, from the engine's coefficient tables as they stand"""
+    return fe.assemble(L.NPG_MAT_A, A, scale=params.alpha ** 2 * params.eps ** 2, full_stress=full_stress)
 
 
 def build_B_inversion(arch, fe_data, params, lift=None):
@@ -133,6 +138,7 @@ class InversionToolkit:
         else:
             raise TypeError("InversionToolkit(arch, fe_data, params, forcings) or InversionToolkit(arch, A, P, B, b)")
         self.arch, self.B, self.b = arch, B, b0
+        self.assembled_here = len(args) == 3            # A came from this constructor's own assembly, not from the caller
         N = A.shape[0]
         y = DeviceVector(arch.ctx, N)
         kwargs = dict(atol=atol, rtol=rtol, itmax=itmax, history=history, verbose=int(verbose), restart=restart,

@@ -22,7 +22,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .architectures import CPU, DeviceVector
+from .architectures import CPU, DeviceCSR, DeviceVector
 from .averages import TimeAverages
 from .evolution import collect_evolution_LHS_into, evolution_parameter
 from .iterative_solvers import LU, CgWorkspace, Diagonal, GmresWorkspace, IterativeSolverToolkit, iterative_solve
@@ -42,9 +42,14 @@ class EigenModes:
                after convergence (not the Arnoldi estimate)
     converged  bool (n,): the residual is within the tolerance asked for
     n_applies, n_inversions, n_inner   applications of J, inversions and inner GMRES iterations the call spent
-    dt         the shift-and-invert step: the modes are the ones nearest the shift 1 / dt"""
+    dt         the shift-and-invert step: the modes are the ones nearest the shift 1 / dt
+    side       "right" (J v = sigma M v) or "left" (J' w = sigma M w, i.e. w' J = sigma w' M - no conjugate; the residuals are then
+               those of the transposed pencil, recomputed with LinearizedModel.apply_adjoint)"""
 
-    def __init__(self, sigma, vectors, residuals, converged, n_applies, n_inversions, dt, n_inner=0, n_restarts=0):
+    def __init__(self, sigma, vectors, residuals, converged, n_applies, n_inversions, dt, n_inner=0, n_restarts=0, side="right"):
+        if side not in ("left", "right"):
+            raise ValueError(f"EigenModes: side must be 'left' or 'right', got {side!r}")
+        self.side = side
         self.sigma = np.asarray(sigma, dtype=complex)
         self.vectors = np.asarray(vectors, dtype=complex)
         self.residuals = np.asarray(residuals, dtype=float)
@@ -64,17 +69,19 @@ class EigenModes:
 
     def save(self, path):
         np.savez(path, sigma=self.sigma, vectors=self.vectors, residuals=self.residuals, converged=self.converged,
-                 counts=np.array([self.n_applies, self.n_inversions, self.n_inner, self.n_restarts], dtype=np.int64), dt=self.dt)
+                 counts=np.array([self.n_applies, self.n_inversions, self.n_inner, self.n_restarts], dtype=np.int64), dt=self.dt,
+                 side=self.side)
         return path
 
     @classmethod
     def load(cls, path):
         with np.load(path) as z:
             c = z["counts"]
-            return cls(z["sigma"], z["vectors"], z["residuals"], z["converged"], c[0], c[1], float(z["dt"]), c[2], c[3])
+            side = str(z["side"]) if "side" in z.files else "right"          # a file from before the left modes
+            return cls(z["sigma"], z["vectors"], z["residuals"], z["converged"], c[0], c[1], float(z["dt"]), c[2], c[3], side)
 
     def __repr__(self):
-        return f"EigenModes: {len(self)} modes nearest 1/dt = {1.0 / self.dt:.3e}, sigma = {self.sigma}"
+        return f"EigenModes: {len(self)} {self.side} modes nearest 1/dt = {1.0 / self.dt:.3e}, sigma = {self.sigma}"
 
 
 class LinearizedModel:
@@ -140,6 +147,10 @@ class LinearizedModel:
         self._lhs = self._lhs_P = self._lhs_ws = self._lhs_y = None
         self._gm = None
         self.n_inversions = self.n_applies = self.n_inner = self.n_inversion_iterations = 0
+        # the transposed inversion (A', B', their solver) and the adjoint's work vectors: built by the first adjoint call
+        self.adj_solver = self.B_T = None
+        self._adj = None
+        self.n_adjoint_inversions = self.n_adjoint_applies = 0
 
     # ---- the operator ---------------------------------------------------------------------------------------------------------------
     def invert(self, db: DeviceVector, dx: DeviceVector = None):
@@ -169,6 +180,79 @@ class LinearizedModel:
         self.n_applies += 1
         return out
 
+    # ---- the adjoint operator ------------------------------------------------------------------------------------------
+    def _adjoint(self):
+        """A', B' and a second solver on them, built once: own x, y and workspace, atol = 0 and the model's rtol; the preconditioner
+        follows the model's - Diagonal is symmetric and serves as it is, LU and the dense inverse are rebuilt from A'"""
+        if self._adj is not None:
+            return self._adj
+        from .multigrid import DenseInversePreconditioner, FgmresWorkspace
+        ms = self.model.inversion.solver
+        P = ms.P
+        if not (P is None or isinstance(P, (Diagonal, LU, DenseInversePreconditioner))):
+            raise NotImplementedError(f"LinearizedModel: the adjoint supports the inversion preconditioners Diagonal, LU and "
+                                      f"DenseInversePreconditioner, not {type(P).__name__}: a transposed V-cycle is a follow-up")
+        if getattr(ms.A, "paired", False):
+            # node records are an HBM layout that does not download as CSR: the same entries assembled once more into a plain
+            # pattern, by the routine and the engine that assembled them (constant nu, Laplacian form: what InversionToolkit asks
+            # of a matrix before it calls block_nodes), from the engine's tables as they stand
+            from .inversion import assemble_A_inversion, device_fe
+            frc = self.model.forcings
+            if not getattr(self.model.inversion, "assembled_here", False) or callable(frc.nu) or frc.eddy_param.is_on:
+                raise NotImplementedError("LinearizedModel: the adjoint cannot transpose an inversion matrix stored by node records "
+                                          "unless InversionToolkit assembled it itself with a constant nu: pass a plain A")
+            fe = device_fe(self.arch, self.model.fe_data)
+            A_csr = assemble_A_inversion(fe, self.model.params, fe.new_matrix("A"), False).to_scipy_csr()
+        else:
+            A_csr = ms.A.to_scipy_csr()
+        A_T = DeviceCSR.from_scipy(self.ctx, A_csr.T)           # (from_scipy reads CSC: the transpose of a CSR matrix as it stands)
+        B_T = DeviceCSR.from_scipy(self.ctx, self.B.to_scipy_csr().T)
+        mem = getattr(ms.workspace, "memory", 20)
+        if isinstance(P, LU):
+            P_T = LU(A_T)
+        elif isinstance(P, DenseInversePreconditioner):
+            P_T = DenseInversePreconditioner(self.arch, A_T, storage=P.storage)
+        else:
+            P_T = P
+        ws = (FgmresWorkspace if isinstance(P, DenseInversePreconditioner) else GmresWorkspace)(self.ctx, self.n_inv, memory=mem)
+        kw = dict(self.inv_solver.kwargs)
+        solver = IterativeSolverToolkit(A_T, P_T, DeviceVector(self.ctx, self.n_inv), ws, kw, "Linearised adjoint inversion")
+        self.adj_solver, self.B_T = solver, B_T
+        self._adj = dict(gx=DeviceVector(self.ctx, self.n_inv), gb=DeviceVector(self.ctx, self.nb))
+        return self._adj
+
+    def invert_adjoint(self, g_x: DeviceVector, out: DeviceVector = None):
+        """out = B' A^-T g_x: A' y = g_x from a zero guess, then B' y.  Returns out (default: an own vector)."""
+        adj = self._adjoint()
+        s = self.adj_solver
+        out = adj["gb"] if out is None else out
+        s.y.copy_from(g_x)
+        s.x.fill(0.0)
+        iterative_solve(s)
+        st = s.workspace.stats or {}
+        if not st.get("solved", 1):
+            raise RuntimeError(f"LinearizedModel.invert_adjoint: the transposed inversion did not reach rtol = {self.rtol:g} "
+                               f"(atol = 0): {st}")
+        self.n_inversion_iterations += int(st.get("niter", 0))
+        self.n_inversions += 1
+        self.n_adjoint_inversions += 1
+        self.B_T.mul(s.x, out, alpha=1.0, beta=0.0)
+        return out
+
+    def apply_adjoint(self, lam: DeviceVector, out: DeviceVector = None):
+        """out = J' lam = -g_b - B' A^-T g_x - c (Kh + Kv) lam with (g_b, g_x) the adjoint of the tangent load
+        (npg_fe_tangent_adjoint): <lam, apply(db)> = <apply_adjoint(lam), db>.  Kh and Kv are used as stored (symmetric to rounding)."""
+        out = DeviceVector(self.ctx, self.nb) if out is None else out
+        if out is lam:
+            raise ValueError("LinearizedModel.apply_adjoint: out must not be lam")
+        adj = self._adjoint()
+        self.fe.tangent_adjoint(self.N2, self.b_base, self.x_base, lam, out, adj["gx"])
+        self.Kh.mul(lam, out, alpha=-self.c, beta=-1.0)
+        self.Kv.mul(lam, out, alpha=-self.c, beta=1.0)
+        out.axpby(-1.0, self.invert_adjoint(adj["gx"]), 1.0)
+        self.n_adjoint_applies += 1
+        return out
+
     # ---- the backward-Euler tangent step ----------------------------------------------------------------------------------------------
     def _preconditioner(self, dt):
         """(M + dt c (Kh + Kv))^-1: own matrix, own Jacobi vector or LU, own CG workspace; rebuilt when dt changes"""
@@ -196,19 +280,21 @@ class LinearizedModel:
         z.copy_from(ws.x)
         return z
 
-    def _step_operator(self, dt, w, out):
-        """out = (M - dt J) w"""
-        self.apply(w, out)
+    def _step_operator(self, dt, w, out, adjoint=False):
+        """out = (M - dt J) w, or (M - dt J') w"""
+        (self.apply_adjoint if adjoint else self.apply)(w, out)
         self.M.mul(w, out, alpha=1.0, beta=-dt)
         return out
 
-    def implicit_step(self, v: DeviceVector, dt, out: DeviceVector = None, rtol=None, memory=30, itmax=300):
+    def implicit_step(self, v: DeviceVector, dt, out: DeviceVector = None, rtol=None, memory=30, itmax=300, adjoint=False):
         """out = (M - dt J)^-1 M v: a backward-Euler step of length dt of the tangent model M d_t db = J db.
 
         Restarted GMRES(memory) over DeviceVector operations with modified Gram-Schmidt, right-preconditioned by
         (M + dt c (Kh + Kv))^-1 (GPU(): Jacobi-CG; CPU(): LU) from a zero guess; the directions are kept preconditioned, so an inexact
         CG is harmless.  Stops when the TRUE residual ||(M - dt J) out - M v|| <= rtol ||M v|| (default rtol: 100 x the model's).
-        `last_step` reports dict(niter, npass, rnorm, rnorm0); the inner iterations are also counted in `n_inner`."""
+        `last_step` reports dict(niter, npass, rnorm, rnorm0); the inner iterations are also counted in `n_inner`.
+        adjoint=True solves (M - dt J') out = M v instead - a step of the adjoint model - with the same GMRES, the same true-residual
+        check and the same preconditioner: (M + dt c (Kh + Kv)) is symmetric."""
         dt = float(dt)
         if not (np.isfinite(dt) and dt > 0.0):
             raise ValueError(f"LinearizedModel.implicit_step: dt must be positive, got {dt}")
@@ -216,6 +302,8 @@ class LinearizedModel:
         out = DeviceVector(self.ctx, self.nb) if out is None else out
         if out is v:
             raise ValueError("LinearizedModel.implicit_step: out must not be v")
+        if adjoint:
+            self._adjoint()             # an unsupported preconditioner refuses here, before any work vector is touched
         if self._gm is None or len(self._gm["V"]) < memory + 1:
             self._gm = dict(V=[DeviceVector(self.ctx, self.nb) for _ in range(memory + 1)],
                             Z=[DeviceVector(self.ctx, self.nb) for _ in range(memory)])
@@ -246,7 +334,7 @@ class LinearizedModel:
             # the estimate steers the cycle; a cycle ends a little below the target so that the true residual passes the first time
             while k < memory and est > 0.5 * target and stats["niter"] < itmax:
                 self._precond_apply(dt, V[k], Z[k])
-                self._step_operator(dt, Z[k], w)
+                self._step_operator(dt, Z[k], w, adjoint)
                 for i in range(k + 1):
                     H[i, k] = V[i].dot(w)
                     w.axpby(-H[i, k], V[i], 1.0)
@@ -269,14 +357,14 @@ class LinearizedModel:
             y = np.linalg.solve(np.triu(H[:k, :k]), g[:k]) if k else np.zeros(0)
             for i in range(k):
                 out.axpby(y[i], Z[i], 1.0)
-            self._step_operator(dt, out, r)                 # the true residual
+            self._step_operator(dt, out, r, adjoint)        # the true residual
             r.axpby(1.0, rhs, -1.0)
             rnorm = r.norm()
             stats["rnorm"] = rnorm
         return out
 
     # ---- eigenmodes -------------------------------------------------------------------------------------------------------------------
-    def eigenmodes(self, n, dt, ncv=None, tol=1e-8, maxrestart=60, v0=None, seed=0, inner_rtol=None):
+    def eigenmodes(self, n, dt, ncv=None, tol=1e-8, maxrestart=60, v0=None, seed=0, inner_rtol=None, side="right"):
         """The `n` eigenmodes J v = sigma M v nearest the shift 1 / dt, sorted by descending Re sigma, as EigenModes.
 
         Thick-restart Arnoldi (Krylov-Schur) on P = (M - dt J)^-1 M, the backward-Euler propagator of the tangent model over dt
@@ -290,8 +378,13 @@ class LinearizedModel:
         ||J v - sigma M v|| / (|sigma| ||M v||) of every returned mode, recomputed with `apply`; the Arnoldi estimates only decide when
         to look.  ncv: the size of the Krylov space (default max(20, 2 n + 10), at most nb - 1); v0: a start vector (host, native
         order) instead of the seeded random one; inner_rtol: the tolerance of the shift-and-invert solves (default: from tol / 10 down
-        to the inversions' rtol, tightened by |mu - 1| of the wanted modes - a solve's error e enters a residual as e / |mu - 1|)."""
+        to the inversions' rtol, tightened by |mu - 1| of the wanted modes - a solve's error e enters a residual as e / |mu - 1|).
+        side="left": the modes J' w = sigma M w (w' J = sigma w' M) - the same driver on the adjoint step, residuals recomputed with
+        `apply_adjoint`."""
         import scipy.linalg as sla
+        if side not in ("left", "right"):
+            raise ValueError(f"LinearizedModel.eigenmodes: side must be 'left' or 'right', got {side!r}")
+        left = side == "left"
         n, dt = int(n), float(dt)
         nb = self.nb
         if n < 1 or n >= nb:
@@ -302,8 +395,10 @@ class LinearizedModel:
         if not n + 2 <= m <= nb - 1:
             raise ValueError(f"LinearizedModel.eigenmodes: ncv must lie in [n + 2, nb - 1] = [{n + 2}, {nb - 1}], got {m}")
         inner = max(0.1 * tol, self.rtol) if inner_rtol is None else float(inner_rtol)
+        if left:
+            self._adjoint()
         d = self.model.fe_data.dofs
-        count0 = (self.n_applies, self.n_inversions, self.n_inner)
+        count0 = (self.n_applies + self.n_adjoint_applies, self.n_inversions, self.n_inner)
         V = [DeviceVector(self.ctx, nb) for _ in range(m + 1)]
         W = [DeviceVector(self.ctx, nb) for _ in range(m + 1)]
         if v0 is None:
@@ -323,7 +418,7 @@ class LinearizedModel:
         while True:
             j = k
             while j < m:        # expand: P V[j], orthogonalised twice (modified Gram-Schmidt)
-                self.implicit_step(V[j], dt, w, rtol=inner)
+                self.implicit_step(V[j], dt, w, rtol=inner, adjoint=left)
                 for _ in range(2):
                     for i in range(j + 1):
                         h = V[i].dot(w)
@@ -374,7 +469,7 @@ class LinearizedModel:
             H[p, :p] = bp
             k = p
             if done:
-                result = self._finish(lam[pick], S[:, pick], V, p, dt, tol, count0, restarts)
+                result = self._finish(lam[pick], S[:, pick], V, p, dt, tol, count0, restarts, side)
                 worst = float(result.residuals.max())
                 if result.converged.all() or mm < m or restarts >= maxrestart or tol_a <= 1e-15:
                     return result
@@ -383,8 +478,9 @@ class LinearizedModel:
                     inner = max(0.1 * inner, self.rtol)
             restarts += 1
 
-    def _finish(self, mu, S, V, p, dt, tol, count0, restarts):
+    def _finish(self, mu, S, V, p, dt, tol, count0, restarts, side="right"):
         """the Ritz vectors V[:p] S, normalised, with their true residuals"""
+        op = self.apply_adjoint if side == "left" else self.apply
         d = self.model.fe_data.dofs
         sigma = (1.0 - 1.0 / mu) / dt
         order = np.argsort(-sigma.real, kind="stable")
@@ -396,12 +492,12 @@ class LinearizedModel:
         for i in range(n):
             cplx = abs(sigma[i].imag) > 0.0 or np.abs(S[:, i].imag).max() > 0.0
             _lincomb_many(vr, S[:, i].real, V[:p])
-            Jv = self.apply(vr, a).to_host(d.inv_p_b).astype(complex)
+            Jv = op(vr, a).to_host(d.inv_p_b).astype(complex)
             Mv = self.M.mul(vr, b).to_host(d.inv_p_b).astype(complex)
             v = vr.to_host(d.inv_p_b).astype(complex)
             if cplx:
                 _lincomb_many(vi, S[:, i].imag, V[:p])
-                Jv += 1j * self.apply(vi, a).to_host(d.inv_p_b)
+                Jv += 1j * op(vi, a).to_host(d.inv_p_b)
                 Mv += 1j * self.M.mul(vi, b).to_host(d.inv_p_b)
                 v += 1j * vi.to_host(d.inv_p_b)
             res[i] = np.linalg.norm(Jv - sigma[i] * Mv) / (abs(sigma[i]) * np.linalg.norm(Mv))
@@ -410,8 +506,92 @@ class LinearizedModel:
             vecs[i] = v * (np.conj(big) / abs(big))                  # the largest entry real (and positive)
             if not cplx:
                 vecs[i] = vecs[i].real
-        return EigenModes(sigma, vecs, res, res <= tol, self.n_applies - count0[0], self.n_inversions - count0[1], dt,
-                          self.n_inner - count0[2], restarts)
+        return EigenModes(sigma, vecs, res, res <= tol, self.n_applies + self.n_adjoint_applies - count0[0], self.n_inversions - count0[1],
+                          dt, self.n_inner - count0[2], restarts, side)
+
+    # ---- both sets of modes -----------------------------------------------------------------------------------------------------------
+    def mass_matrix_native(self):
+        """M as a scipy CSR matrix over the free DoFs in native order (the order of EigenModes.vectors)"""
+        p = self.model.fe_data.dofs.inv_p_b
+        return self.M.to_scipy_csr()[p][:, p].tocsr()
+
+    def mode_pairs(self, n, dt, **kw):
+        """The `n` modes nearest 1 / dt from both sides, matched and scaled so that w_i' M v_i = 1, as ModePairs.  **kw: eigenmodes'."""
+        if "side" in kw:
+            raise ValueError("LinearizedModel.mode_pairs: it computes both sides; do not pass side")
+        self._adjoint()
+        right = self.eigenmodes(n, dt, side="right", **kw)
+        left = self.eigenmodes(n, dt, side="left", **kw)
+        return ModePairs.from_modes(right, left, self.mass_matrix_native())
+
+
+class ModePairs:
+    """What LinearizedModel.mode_pairs returns: right modes v_i (J v = sigma M v) and left modes w_i (w' J = sigma w' M) of the same
+    eigenvalues, biorthogonal in the BILINEAR form - w_i' M v_j = 0 for sigma_i != sigma_j, no conjugate - and scaled to w_i' M v_i = 1.
+
+    sigma        complex (n,), from the right modes (sorted by descending real part)
+    sigma_left   the left modes' own eigenvalues, in the matched order
+    right, left  complex (n, nb), native free-DoF order; the right vectors are EigenModes' (unit M-norm), the left carry the scale
+    left_M       (n, nb): row i is w_i' M, what `amplitudes` multiplies with
+    condition    kappa_i = ||w_i||_M ||v_i||_M / |w_i' M v_i| with ||x||_M^2 = x^H M x: 1 for a normal pencil
+    residuals_right, residuals_left, dt   from the two EigenModes"""
+
+    _fields = ("sigma", "sigma_left", "right", "left", "left_M", "condition", "residuals_right", "residuals_left")
+
+    def __init__(self, sigma, sigma_left, right, left, left_M, condition, residuals_right, residuals_left, dt):
+        self.sigma, self.sigma_left = np.asarray(sigma, dtype=complex), np.asarray(sigma_left, dtype=complex)
+        self.right, self.left = np.asarray(right, dtype=complex), np.asarray(left, dtype=complex)
+        self.left_M = np.asarray(left_M, dtype=complex)
+        self.condition = np.asarray(condition, dtype=float)
+        self.residuals_right, self.residuals_left = np.asarray(residuals_right, dtype=float), np.asarray(residuals_left, dtype=float)
+        self.dt = float(dt)
+
+    @classmethod
+    def from_modes(cls, right, left, M):
+        """match the left modes to the right ones by nearest sigma (a conjugate pair may come in either order) and scale them"""
+        if right.side != "right" or left.side != "left" or len(right) != len(left):
+            raise ValueError("ModePairs.from_modes: needs as many left modes as right modes")
+        n, used, order = len(right), set(), []
+        for i in range(n):
+            j = min((j for j in range(n) if j not in used), key=lambda j: abs(right.sigma[i] - left.sigma[j]))
+            used.add(j)
+            order.append(j)
+        V, W = right.vectors, left.vectors[order].copy()
+        MV = (M @ V.T).T                                               # row i: M v_i
+        cond = np.zeros(n)
+        for i in range(n):
+            wMv = W[i] @ MV[i]                                         # bilinear: no conjugate
+            nw = np.sqrt(np.vdot(W[i], M @ W[i]).real)
+            nv = np.sqrt(np.vdot(V[i], MV[i]).real)
+            if wMv == 0.0:
+                raise RuntimeError(f"ModePairs.from_modes: left mode {order[i]} is M-orthogonal to right mode {i}: not the same eigenvalue")
+            cond[i] = nw * nv / abs(wMv)
+            W[i] = W[i] / wMv
+        left_M = (M.T @ W.T).T
+        return cls(right.sigma, left.sigma[order], V, W, left_M, cond, right.residuals, left.residuals[order], right.dt)
+
+    def __len__(self):
+        return len(self.sigma)
+
+    def amplitudes(self, db):
+        """a_i = w_i' M db: the coordinates of db (native order, real or complex) in the right modes"""
+        return self.left_M @ np.asarray(db)
+
+    def reconstruct(self, a):
+        """sum_i a_i v_i"""
+        return np.asarray(a) @ self.right
+
+    def save(self, path):
+        np.savez(path, dt=self.dt, **{k: getattr(self, k) for k in self._fields})
+        return path
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            return cls(*[z[k] for k in cls._fields], float(z["dt"]))
+
+    def __repr__(self):
+        return f"ModePairs: {len(self)} modes nearest 1/dt = {1.0 / self.dt:.3e}, sigma = {self.sigma}, condition = {self.condition}"
 
 
 def _lincomb_many(out, coef, xs):
