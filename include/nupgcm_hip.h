@@ -478,6 +478,26 @@ int npg_fe_tangent_rhs(npg_fe *fe, double N2, const npg_vec *b_base, const npg_v
  * neither may be an input.  Always fp64. */
 int npg_fe_tangent_adjoint(npg_fe *fe, double N2, const npg_vec *b_base, const npg_vec *x_base,
                            const npg_vec *lam, npg_vec *out_b, npg_vec *out_x);
+/* The derivatives of the convection and eddy closures.  With s = alpha (N2 + d_z b_base) at a quadrature point
+ * (b_base through the Dirichlet table, the expression of the two closure updates below):
+ *   tangent_diffusion     out_i = int kappa_eff d_z db d_z phi_i,  kappa_eff = kappa_v(s) + s kappa_v'(s),
+ *                         kappa_v(s) = kappa_v0 + kappa_c (1 + tanh(-s / N2min)) / 2 over the BACKGROUND table (the one npg_fe_set_coeff
+ *                         "kappa_v" last stored); kappa_c = 0 gives the product with the background K_v
+ *   tangent_eddy          out_x_(i,a) = -a2e2 int nu'(s) alpha d_z db ( grad u_a . grad phi_i [+ sum_c d_a u_c d_c phi_i if full_stress] )
+ *                         with u = x_base's velocity: -(dA/dnu)[dnu] x_base on the rows of NPG_MAT_A; the pressure rows are 0
+ *   tangent_eddy_adjoint  out_b with <mu, tangent_eddy(db)> = <out_b, db> for a multiplier mu of n_inv entries
+ * nu(s) = LogSumExp(nu_min, f^2 / sqrt(N2min^2 + s^2)) as npg_fe_update_nu_eddy forms it.  db and mu are perturbations: a Dirichlet DoF
+ * reads 0.  The closure derivatives are evaluated on the fly; no coefficient table is written, and of the tables only the background
+ * kappa_v and f are read.  tanh and exp are evaluated by arithmetic of the library's own, the same bits in both libraries.  An output
+ * must not be an input; N2min > 0 (and smoothing > 0).  Always fp64. */
+int npg_fe_tangent_diffusion(npg_fe *fe, double kappa_c, double N2min, double alpha, double N2, const npg_vec *b_base,
+                             const npg_vec *db, npg_vec *out);
+int npg_fe_tangent_eddy(npg_fe *fe, double a2e2, int full_stress, double N2min, double alpha, double N2, double smoothing,
+                        double nu_min, const npg_vec *b_base, const npg_vec *x_base, const npg_vec *db, npg_vec *out_x);
+int npg_fe_tangent_eddy_adjoint(npg_fe *fe, double a2e2, int full_stress, double N2min, double alpha, double N2, double smoothing,
+                                double nu_min, const npg_vec *b_base, const npg_vec *x_base, const npg_vec *mu, npg_vec *out_b);
+/* the read-back of npg_fe_set_coeff: host_out[ncell][nq] <- the table as it stands (after a closure update: the updated values) */
+int npg_fe_get_coeff(npg_fe *fe, const char *name, double *host_out);
 
 /* Matrix (re)assembly into an existing CSR pattern (values are overwritten).
  * which: */

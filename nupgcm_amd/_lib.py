@@ -151,6 +151,10 @@ def _declare(L, partial=False):
         "npg_fe_advection_rhs": [P, C.c_int, D, D, P, P, P, P, P],
         "npg_fe_tangent_rhs": [P, D, P, P, P, P, P],
         "npg_fe_tangent_adjoint": [P, D, P, P, P, P, P],
+        "npg_fe_tangent_diffusion": [P, D, D, D, D, P, P, P],
+        "npg_fe_tangent_eddy": [P, D, C.c_int, D, D, D, D, D, P, P, P, P],
+        "npg_fe_tangent_eddy_adjoint": [P, D, C.c_int, D, D, D, D, D, P, P, P, P],
+        "npg_fe_get_coeff": [P, C.c_char_p, VP],
         "npg_fe_assemble_matrix": [P, C.c_int, D, C.c_int, P, P], "npg_fe_assemble_rhs_diff": [P, D, P],
         "npg_fe_update_kappa_convection": [P, VP, D, D, D, D, P],
         "npg_fe_update_nu_eddy": [P, D, D, D, D, D, P], "npg_fe_restrict_coeff": [P, P, C.c_char_p], "npg_fe_coeff_cell_mean": [P, C.c_char_p, P], "npg_fe_cfl_ratio": [P, VP, D, P, C.POINTER(D)],

@@ -21,6 +21,11 @@ def eval_at_quad_points(mesh, v):
     return np.full(xq.shape[:2], float(v))
 
 
+# the LogSumExp parameters of the eddy closure (nu_eddy, src/inputs.jl:130-137): the one place the model's refresh (update_nu_eddy) and
+# the linearised model's loads (tangent_eddy, tangent_eddy_adjoint: linearized.py passes them explicitly) take them from
+EDDY_SMOOTHING, EDDY_NU_MIN = 10.0, 1.0
+
+
 class DeviceFE:
     def __init__(self, ctx, fe_data):
         self.ctx, self.fe_data = ctx, fe_data
@@ -122,6 +127,31 @@ class DeviceFE:
         L.check(L.lib().npg_fe_tangent_adjoint(self.h, float(N2), b_base.h, x_base.h, lam.h, out_b.h, out_x.h))
         return out_b, out_x
 
+    def tangent_diffusion(self, kappa_c, N2min, alpha, N2, b_base, db, out):
+        """out = D_v db: the derivative of the vertical diffusion with the convection closure at b_base, over the background kappa_v
+        (npg_fe_tangent_diffusion); kappa_c = 0 gives the background K_v product"""
+        L.check(L.lib().npg_fe_tangent_diffusion(self.h, float(kappa_c), float(N2min), float(alpha), float(N2), b_base.h, db.h, out.h))
+        return out
+
+    def tangent_eddy(self, a2e2, full_stress, N2min, alpha, N2, b_base, x_base, db, out_x, smoothing=EDDY_SMOOTHING, nu_min=EDDY_NU_MIN):
+        """out_x = r_x(db) = -(dA/dnu)[nu'(s) alpha d_z db] x_base: what the eddy closure adds to the right-hand side of the tangent
+        inversion (npg_fe_tangent_eddy); the pressure rows are 0"""
+        L.check(L.lib().npg_fe_tangent_eddy(self.h, float(a2e2), int(bool(full_stress)), float(N2min), float(alpha), float(N2),
+                                            float(smoothing), float(nu_min), b_base.h, x_base.h, db.h, out_x.h))
+        return out_x
+
+    def tangent_eddy_adjoint(self, a2e2, full_stress, N2min, alpha, N2, b_base, x_base, mu, out_b, smoothing=EDDY_SMOOTHING, nu_min=EDDY_NU_MIN):
+        """out_b = g(mu) with <mu, tangent_eddy(db)> = <out_b, db> (npg_fe_tangent_eddy_adjoint)"""
+        L.check(L.lib().npg_fe_tangent_eddy_adjoint(self.h, float(a2e2), int(bool(full_stress)), float(N2min), float(alpha), float(N2),
+                                                    float(smoothing), float(nu_min), b_base.h, x_base.h, mu.h, out_b.h))
+        return out_b
+
+    def get_coeff(self, name):
+        """the coefficient table `name` as it stands, (ncell, nq): the read-back of set_coeff (npg_fe_get_coeff)"""
+        out = np.empty(self.fe_data.mesh.quad_points().shape[:2], dtype=np.float64)
+        L.check(L.lib().npg_fe_get_coeff(self.h, name.encode(), L.ptr(out)))
+        return out
+
     def evolution_rhs(self, scheme, dt, N2, theta, b, b_prev, x_inv, x_inv_prev, rhs_diff, rhs_flux, rhs_M, rhs_h, rhs_v,
                       y):
         hh = [None if v is None else v.h for v in (rhs_diff, rhs_flux, rhs_M, rhs_h, rhs_v)]
@@ -133,7 +163,7 @@ class DeviceFE:
         L.check(L.lib().npg_fe_update_kappa_convection(self.h, None, float(kappa_c), float(N2min), float(alpha),
                                                        float(N2), b.h))
 
-    def update_nu_eddy(self, N2min, alpha, N2, b, smoothing=10.0, nu_min=1.0):
+    def update_nu_eddy(self, N2min, alpha, N2, b, smoothing=EDDY_SMOOTHING, nu_min=EDDY_NU_MIN):
         L.check(L.lib().npg_fe_update_nu_eddy(self.h, float(N2min), float(alpha), float(N2), float(smoothing),
                                               float(nu_min), b.h))
 

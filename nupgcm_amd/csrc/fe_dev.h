@@ -95,7 +95,7 @@ struct npg_fe {
     int64_t n_b_diri = 0;           // entries of the buoyancy Dirichlet value table (tracers keep one of their own per tracer)
     std::vector<void *> allocs;
     double *loc = nullptr;          // [nb][ncell]
-    double *loc_inv = nullptr;      // [34][ncell], as iidx addresses it; allocated by the first npg_fe_tangent_adjoint
+    double *loc_inv = nullptr;      // [34][ncell], as iidx addresses it; allocated by the first call that needs it (fe_ensure_loc_inv)
     int64_t *gptr = nullptr;        // inverted index of the buoyancy rows (vector pass 2, matrix rows)
     int32_t *gidx = nullptr;
     int64_t *iptr = nullptr;        // inverted index of the inversion rows [u; p]: (local DoF l) * ncell + cell
@@ -113,4 +113,6 @@ namespace npg {
 int fe_gather_rows(npg_fe *fe, npg_vec *out);
 // the same kernel through any inverted index: out[r] = the sum of loc[idx[k]], ptr[r] <= k < ptr[r + 1], r < n = out->n
 int fe_gather_index(npg_fe *fe, const int64_t *ptr, const int32_t *idx, const double *loc, int64_t n, npg_vec *out);
+// fe->loc_inv, allocated on first use with its four pressure planes zeroed (tangent_adjoint.hip)
+int fe_ensure_loc_inv(npg_fe *fe);
 }  // namespace npg

@@ -26,7 +26,8 @@ __global__ void __launch_bounds__(kBlock) k_tangent_adjoint_local(FeDev d, doubl
     cell_tangent_adjoint<NB>(t, cell_view(d), d.nq, N2, b_base, x_base, lam, cell, loc_b, loc_x);
 }
 
-static int ensure_loc_inv(npg_fe *fe) {
+// (declared in fe_dev.h: tangent_closures.hip writes its r_x through the same buffer)
+int fe_ensure_loc_inv(npg_fe *fe) {
     if (fe->loc_inv) return NPG_OK;
     const size_t nc = (size_t)fe->d.ncell;
     double *p = nullptr;
@@ -55,7 +56,7 @@ NPG_API int npg_fe_tangent_adjoint(npg_fe *fe, double N2, const npg_vec *b_base,
                                          any_null || (b_base->ctx == fe->ctx && x_base->ctx == fe->ctx && lam->ctx == fe->ctx &&
                                                       out_b->ctx == fe->ctx && out_x->ctx == fe->ctx)));
     NPG_HIP(hipSetDevice(fe->ctx->device));
-    int rc = ensure_loc_inv(fe);
+    int rc = fe_ensure_loc_inv(fe);
     if (rc) return rc;
     const dim3 grid((unsigned)((fe->d.ncell + kBlock - 1) / kBlock)), block(kBlock);
     if (fe->d.nb == 10)

@@ -34,6 +34,7 @@
 #include "../csrc/cell_view.h"
 #include "../csrc/tangent_core.h"
 #include "../csrc/tangent_adjoint_core.h"
+#include "../csrc/tangent_closures_core.h"
 
 #define NPG_API extern "C" __attribute__((visibility("default")))
 
@@ -1016,6 +1017,88 @@ NPG_API int npg_fe_tangent_adjoint(npg_fe *fe, double N2, const npg_vec *b_base,
         for (int64_t k = fe->iptr[(size_t)r]; k < fe->iptr[(size_t)r + 1]; ++k) acc += fe->loc_inv[(size_t)fe->iidx[(size_t)k]];
         out_x->d[r] = acc;
     }
+    return NPG_OK;
+}
+// the derivatives of the convection and eddy closures (csrc/tangent_closures.hip on the host; the arithmetic and its order are
+// csrc/tangent_closures_core.h)
+static void gather_inv_rows(const npg_fe *fe, double *out) {
+    const int64_t n = fe->n_inv;
+#pragma omp parallel for schedule(static)
+    for (int64_t r = 0; r < n; ++r) {
+        double acc = 0.0;
+        for (int64_t k = fe->iptr[(size_t)r]; k < fe->iptr[(size_t)r + 1]; ++k) acc += fe->loc_inv[(size_t)fe->iidx[(size_t)k]];
+        out[r] = acc;
+    }
+}
+NPG_API int npg_fe_tangent_diffusion(npg_fe *fe, double kappa_c, double N2min, double alpha, double N2, const npg_vec *b_base,
+                                     const npg_vec *db, npg_vec *out) {
+    REQUIRE(fe, "npg_fe_tangent_diffusion: NULL handle");
+    const bool any_null = !(b_base && db && out);
+    REQUIRE_OK(npg::check_tangent_diffusion(any_null, !any_null && (out == b_base || out == db), !fe->kv0.empty(), kappa_c, N2min, alpha, N2,
+                                            fe->n_b, any_null ? 0 : b_base->n, any_null ? 0 : db->n, any_null ? 0 : out->n, true));
+    const HostShape s = host_shape(fe);
+    const HostView t = host_view(fe);
+    const npg::ConvClosure cl{kappa_c, N2min};
+    const int64_t nc = fe->ncell;
+#pragma omp parallel for schedule(static)
+    for (int64_t cell = 0; cell < nc; ++cell) {
+        if (fe->nb == 10) npg::cell_tangent_diffusion<10>(s, t, fe->nq, cl, alpha, N2, fe->kv0.data(), b_base->d, db->d, cell, fe->loc.data());
+        else npg::cell_tangent_diffusion<4>(s, t, fe->nq, cl, alpha, N2, fe->kv0.data(), b_base->d, db->d, cell, fe->loc.data());
+    }
+    gather_rows(fe, 0.0, 0.0, nullptr, nullptr, nullptr, nullptr, nullptr, out->d);
+    return NPG_OK;
+}
+NPG_API int npg_fe_tangent_eddy(npg_fe *fe, double a2e2, int full_stress, double N2min, double alpha, double N2, double smoothing,
+                                double nu_min, const npg_vec *b_base, const npg_vec *x_base, const npg_vec *db, npg_vec *out_x) {
+    REQUIRE(fe, "npg_fe_tangent_eddy: NULL handle");
+    const bool any_null = !(b_base && x_base && db && out_x);
+    REQUIRE_OK(npg::check_tangent_eddy(false, any_null, !any_null && (out_x == b_base || out_x == x_base || out_x == db), !fe->coef[3].empty(),
+                                       a2e2, full_stress, N2min, alpha, N2, smoothing, nu_min, fe->n_inv, fe->n_b, any_null ? 0 : b_base->n,
+                                       any_null ? 0 : x_base->n, any_null ? 0 : db->n, any_null ? 0 : out_x->n, true));
+    const HostShape s = host_shape(fe);
+    const HostView t = host_view(fe);
+    const npg::EddyClosure cl{N2min, smoothing, nu_min};
+    const int64_t nc = fe->ncell;
+    if (fe->loc_inv.empty()) fe->loc_inv.assign((size_t)nc * 34, 0.0);      // the pressure entries stay the zeros set here
+    const double *f = fe->coef[3].data();
+#pragma omp parallel for schedule(static)
+    for (int64_t cell = 0; cell < nc; ++cell) {
+        if (fe->nb == 10)
+            npg::cell_tangent_eddy<10>(s, t, fe->nq, a2e2, full_stress, cl, alpha, N2, f, b_base->d, x_base->d, db->d, cell, fe->loc_inv.data());
+        else
+            npg::cell_tangent_eddy<4>(s, t, fe->nq, a2e2, full_stress, cl, alpha, N2, f, b_base->d, x_base->d, db->d, cell, fe->loc_inv.data());
+    }
+    gather_inv_rows(fe, out_x->d);
+    return NPG_OK;
+}
+NPG_API int npg_fe_tangent_eddy_adjoint(npg_fe *fe, double a2e2, int full_stress, double N2min, double alpha, double N2, double smoothing,
+                                        double nu_min, const npg_vec *b_base, const npg_vec *x_base, const npg_vec *mu, npg_vec *out_b) {
+    REQUIRE(fe, "npg_fe_tangent_eddy_adjoint: NULL handle");
+    const bool any_null = !(b_base && x_base && mu && out_b);
+    REQUIRE_OK(npg::check_tangent_eddy(true, any_null, !any_null && (out_b == b_base || out_b == x_base || out_b == mu), !fe->coef[3].empty(),
+                                       a2e2, full_stress, N2min, alpha, N2, smoothing, nu_min, fe->n_inv, fe->n_b, any_null ? 0 : b_base->n,
+                                       any_null ? 0 : x_base->n, any_null ? 0 : mu->n, any_null ? 0 : out_b->n, true));
+    const HostShape s = host_shape(fe);
+    const HostView t = host_view(fe);
+    const npg::EddyClosure cl{N2min, smoothing, nu_min};
+    const int64_t nc = fe->ncell;
+    const double *f = fe->coef[3].data();
+#pragma omp parallel for schedule(static)
+    for (int64_t cell = 0; cell < nc; ++cell) {
+        if (fe->nb == 10)
+            npg::cell_tangent_eddy_adjoint<10>(s, t, fe->nq, a2e2, full_stress, cl, alpha, N2, f, b_base->d, x_base->d, mu->d, cell, fe->loc.data());
+        else
+            npg::cell_tangent_eddy_adjoint<4>(s, t, fe->nq, a2e2, full_stress, cl, alpha, N2, f, b_base->d, x_base->d, mu->d, cell, fe->loc.data());
+    }
+    gather_rows(fe, 0.0, 0.0, nullptr, nullptr, nullptr, nullptr, nullptr, out_b->d);
+    return NPG_OK;
+}
+// the read-back of npg_fe_set_coeff: the table as it stands
+NPG_API int npg_fe_get_coeff(npg_fe *fe, const char *name, double *host_out) {
+    const bool any_null = !(fe && name && host_out);
+    const int k = any_null ? -1 : coef_index(name);
+    REQUIRE_OK(npg::check_get_coeff(any_null, k, any_null ? "" : name, k >= 0 && !fe->coef[k].empty()));
+    memcpy(host_out, fe->coef[k].data(), fe->coef[k].size() * sizeof(double));
     return NPG_OK;
 }
 // rhs_diff = -N2 int kappa_v d_z phi_i        (src/evolution.jl:269-278)

@@ -16,6 +16,18 @@ csrc/tangent_core.h); every application of J costs one inversion.
 LinearizedModel is PASSIVE: it owns its work vectors, its Krylov workspaces, its left-hand side and preconditioner; it reads the model's
 A, P, B, M, Kh, Kv and writes nothing the model owns - u, p, b' and the solvers' warm starts keep their bits.
 
+With the convection or the eddy closure on, kappa_v and nu depend on b and F is no longer quadratic.  closures="tangent"
+differentiates them: -c (Kv b + rhs_v) + c rhs_diff = -(c / alpha) int kappa_v(s) s d_z phi_i with s = alpha (N2 + d_z b) has the
+derivative -c D_v db, (D_v db)_i = int (kappa_v + s kappa_v') d_z db d_z phi_i (npg_fe_tangent_diffusion), and the inversion
+A(nu(b)) x = B b + b0 the tangent A(nu_base) dx = B db + r_x(db), r_x = -(dA / dnu)[nu' alpha d_z db] x_base (npg_fe_tangent_eddy; its
+adjoint g: npg_fe_tangent_eddy_adjoint), on an own copy of A assembled at nu(b_base):
+
+    J db   = -T(b_base, x_base; db, dx) - c Kh db - c D_v db,      dx = A(nu_base)^-1 (B db + r_x(db))
+    J' lam = -g_b - (B' y + g(y)) - c Kh lam - c D_v lam,           y = A(nu_base)^-T g_x .
+
+closures="frozen" accepts such a model and uses its Kv and A as they stand: an operator of the same shape that is NOT the Jacobian
+(on the golden bowl it misses 72 % of max |J db| with the convection closure on).
+
 All solves inside use atol = 0 and the given rtol.  The model's own atol = 1e-6 is an absolute threshold on the 1/h^d-scaled residual: for
 a small db it would accept dx = 0 and make the "linear" operator nonlinear."""
 from __future__ import annotations
@@ -23,6 +35,7 @@ from __future__ import annotations
 import numpy as np
 
 from .architectures import CPU, DeviceCSR, DeviceVector
+from .assembly import EDDY_NU_MIN, EDDY_SMOOTHING
 from .averages import TimeAverages
 from .evolution import collect_evolution_LHS_into, evolution_parameter
 from .iterative_solvers import LU, CgWorkspace, Diagonal, GmresWorkspace, IterativeSolverToolkit, iterative_solve
@@ -85,21 +98,35 @@ class EigenModes:
 
 
 class LinearizedModel:
-    """LinearizedModel(model, base=None, rtol=1e-10): the tangent model about a frozen base state.
+    """LinearizedModel(model, base=None, rtol=1e-10, closures=None): the tangent model about a frozen base state.
 
     base = None: copies of the model's current b_vec and inversion.solver.x; a TimeAverages: copies of its means; a pair (b, x_inv) of
-    DeviceVectors in the solvers' order: copies of them.  rtol: the relative tolerance of every solve inside (atol = 0)."""
+    DeviceVectors in the solvers' order: copies of them.  rtol: the relative tolerance of every solve inside (atol = 0).
+    closures: what to do with a model whose convection or eddy closure is on.  None refuses it.  "frozen" uses the model's Kv and A as
+    they stand and differentiates nothing - not the Jacobian.  "tangent" differentiates both closures: Kv.mul is replaced by
+    npg_fe_tangent_diffusion (the preconditioner of implicit_step stays (M + dt c (Kh + Kv)) on the model's positive Kv); with the eddy
+    closure an own A is assembled at nu(b_base) - the engine's nu table is read back and restored, bit for bit - with an own
+    preconditioner of the model's kind (Diagonal is shared, CPU(): LU, the dense inverse is rebuilt, a multigrid handle is reused as it
+    is), and x_base is solved once more under it so that the base state is consistent: counted in n_inversions - unless the given
+    x_base already meets rtol under the own A (a base handed over from another LinearizedModel), in which case it stands, nothing is
+    solved and nothing is counted.  kappa_eff =
+    kappa_v + s kappa_v' is negative inside a steep tanh transition: the tangent operator may then have growing modes that the frozen
+    one lacks, and implicit_step with dt beyond their growth time does not converge.  A model without closures runs the code it ran,
+    whatever `closures` says."""
 
-    def __init__(self, model, base=None, rtol=1e-10):
+    def __init__(self, model, base=None, rtol=1e-10, closures=None):
+        if closures not in (None, "frozen", "tangent"):
+            raise ValueError(f"LinearizedModel: closures must be None, 'frozen' or 'tangent', got {closures!r}")
         if getattr(model, "comm", None) is not None or getattr(model, "layout", None) is not None \
                 or getattr(model.arch.ctx, "nranks", 1) > 1 or hasattr(model.inversion.solver, "solve"):
             raise NotImplementedError("LinearizedModel: mesh-partitioned and distributed models are not supported")
         if model.evolution is None:
             raise ValueError("LinearizedModel: the model has no EvolutionToolkit")
         frc = model.forcings
-        if frc.conv_param.is_on or frc.eddy_param.is_on:
+        if (frc.conv_param.is_on or frc.eddy_param.is_on) and closures is None:
             raise NotImplementedError("LinearizedModel: the convection and eddy closures are not supported: their coefficients depend on b "
-                                      "and are not differentiated")
+                                      "and are not differentiated (pass closures='tangent' to differentiate them, or closures='frozen' "
+                                      "to keep the model's K_v and A as they stand)")
         if getattr(model, "surface_forcing", None) is not None or getattr(model, "interior_forcing", None) is not None:
             raise NotImplementedError("LinearizedModel: an attached surface_forcing or interior_forcing is not supported: their S / R "
                                       "matrices are not part of the tangent operator yet")
@@ -127,17 +154,25 @@ class LinearizedModel:
             raise ValueError(f"LinearizedModel: the base state must hold {self.nb} buoyancy and {self.n_inv} flow entries, "
                              f"got {len(b)} and {len(x)}")
         self.b_base, self.x_base = b.copy(), x.copy()
+        self.closures = closures
+        # the closures whose derivatives enter the operators (closures="tangent"); None: the coefficient is used as the model holds it
+        self._conv = frc.conv_param if closures == "tangent" and frc.conv_param.is_on else None
+        self._eddy = frc.eddy_param if closures == "tangent" and frc.eddy_param.is_on else None
         # a second solver on the model's A and P: its own x, y and workspace; the model's kwargs with atol = 0 and rtol
         ms = model.inversion.solver
         kw = dict(ms.kwargs)
         kw.update(atol=0.0, rtol=self.rtol)
         mem = getattr(ms.workspace, "memory", 20)
-        if isinstance(ms.P, (Diagonal, LU)) or ms.P is None:
+        A, P = ms.A, ms.P
+        if self._eddy is not None:
+            A, P = self._own_inversion_matrix(ms)
+        self._A_plain = A if self._eddy is not None else None
+        if isinstance(P, (Diagonal, LU)) or P is None:
             ws = GmresWorkspace(self.ctx, self.n_inv, memory=mem)
         else:
             from .multigrid import FgmresWorkspace
             ws = FgmresWorkspace(self.ctx, self.n_inv, memory=mem)
-        self.inv_solver = IterativeSolverToolkit(ms.A, ms.P, DeviceVector(self.ctx, self.n_inv), ws, kw, "Linearised inversion")
+        self.inv_solver = IterativeSolverToolkit(A, P, DeviceVector(self.ctx, self.n_inv), ws, kw, "Linearised inversion")
         self.B = model.inversion.B
         ev = model.evolution
         self.M, self.Kh, self.Kv = ev.M, ev.Kh, ev.Kv
@@ -151,13 +186,99 @@ class LinearizedModel:
         self.adj_solver = self.B_T = None
         self._adj = None
         self.n_adjoint_inversions = self.n_adjoint_applies = 0
+        self._dv = None
+        if self._eddy is not None:
+            self._rx = DeviceVector(self.ctx, self.n_inv)
+            self._solve_base_flow()
+
+    # ---- the closures ----------------------------------------------------------------------------------------------------
+    def _own_inversion_matrix(self, ms):
+        """A at nu(b_base) in the full-stress form the model's own refresh assembles, into a matrix of this object's, and a
+        preconditioner of the model's kind for it.  The engine's nu table is read back first and put back afterwards: the same bits."""
+        from . import _lib as L
+        from .inversion import assemble_A_inversion
+        from .multigrid import DenseInversePreconditioner
+        fe, prm, ep = self.fe, self.model.params, self._eddy
+        keep = fe.get_coeff("nu")
+        try:
+            fe.update_nu_eddy(ep.N2min, prm.alpha, prm.N2, self.b_base, **self._eddy_kw())
+            A = assemble_A_inversion(fe, prm, fe.new_matrix("A", structural=True), True)
+        finally:
+            L.check(L.lib().npg_fe_set_coeff(fe.h, b"nu", L.ptr(keep)))
+        P = ms.P
+        if isinstance(self.arch, CPU):
+            P = LU(A)               # InversionToolkit picks Diagonal there when the eddy closure is on: every solve would factorise
+        elif isinstance(P, DenseInversePreconditioner):
+            P = DenseInversePreconditioner(self.arch, A, storage=P.storage)
+        # Diagonal(1 / h^dim) does not depend on A; a multigrid handle is the model's as it is - inexact for A(nu(b_base)), behind FGMRES
+        return A, P
+
+    def _solve_base_flow(self):
+        """x_base <- A(nu(b_base))^-1 (B b_base + b0) from the given x_base as a guess: the flow that belongs to b_base under the
+        closure, which r_x and the tangent load are taken at.  Counted in n_inversions.
+
+        The Krylov solvers stop relative to the residual they START from: a guess that is already the solution (a base state taken
+        from another LinearizedModel) would ask them for rtol below rounding.  So the residual r of the guess is formed first; the
+        guess stands when ||r|| <= rtol ||y||, and otherwise the correction A e = r is solved from zero down to rtol ||y||."""
+        s = self.inv_solver
+        s.y.copy_from(self.model.inversion.b)
+        self.B.mul(self.b_base, s.y, alpha=1.0, beta=1.0)
+        if isinstance(s.P, LU):
+            iterative_solve(s)
+            self.n_inversions += 1
+            self.x_base.copy_from(s.x)
+            return
+        ynorm = s.y.norm()
+        s.A.mul(self.x_base, s.y, alpha=-1.0, beta=1.0)
+        rnorm = s.y.norm()
+        if rnorm <= self.rtol * ynorm:
+            return
+        s.x.fill(0.0)
+        keep = s.kwargs["rtol"]
+        s.kwargs["rtol"] = min(0.5, self.rtol * ynorm / rnorm)
+        try:
+            iterative_solve(s)
+        finally:
+            s.kwargs["rtol"] = keep
+        st = s.workspace.stats or {}
+        if not st.get("solved", 1):
+            raise RuntimeError(f"LinearizedModel: the inversion of the base state did not reach rtol = {self.rtol:g} (atol = 0): {st}")
+        self.n_inversion_iterations += int(st.get("niter", 0))
+        self.n_inversions += 1
+        self.x_base.axpby(1.0, s.x, 1.0)
+
+    def _eddy_args(self):
+        prm, ep = self.model.params, self._eddy
+        return prm.alpha ** 2 * prm.eps ** 2, True, ep.N2min, prm.alpha, self.N2
+
+    @staticmethod
+    def _eddy_kw():
+        """the LogSumExp parameters, passed explicitly to the update behind the own A and to both loads: the model's (assembly.py)"""
+        return dict(smoothing=EDDY_SMOOTHING, nu_min=EDDY_NU_MIN)
+
+    def _vertical_diffusion(self, v, out):
+        """out <- out - c D_v v: the model's K_v, or with closures="tangent" and convection on the derivative of kappa_v(b) d_z b"""
+        if self._conv is None:
+            self.Kv.mul(v, out, alpha=-self.c, beta=1.0)
+        else:
+            cp, prm = self._conv, self.model.params
+            if self._dv is None:
+                self._dv = DeviceVector(self.ctx, self.nb)
+            self.fe.tangent_diffusion(cp.kappa_c, cp.N2min, prm.alpha, self.N2, self.b_base, v, self._dv)
+            out.axpby(-self.c, self._dv, 1.0)
+        return out
 
     # ---- the operator ---------------------------------------------------------------------------------------------------------------
     def invert(self, db: DeviceVector, dx: DeviceVector = None):
         """dx = L db: A dx = B db from a zero guess - no b0, hence no wind and no Dirichlet lift.  Returns dx (default: an own vector)."""
         s = self.inv_solver
         dx = self._dx if dx is None else dx
-        self.B.mul(db, s.y, alpha=1.0, beta=0.0)
+        if self._eddy is None:
+            self.B.mul(db, s.y, alpha=1.0, beta=0.0)
+        else:                       # A(nu_base) dx = B db + r_x(db): the derivative of nu moves the base flow
+            self.fe.tangent_eddy(*self._eddy_args(), self.b_base, self.x_base, db, self._rx, **self._eddy_kw())
+            s.y.copy_from(self._rx)
+            self.B.mul(db, s.y, alpha=1.0, beta=1.0)
         s.x.fill(0.0)
         iterative_solve(s)
         st = s.workspace.stats or {}
@@ -176,7 +297,7 @@ class LinearizedModel:
         dx = self.invert(db)
         self.fe.tangent_rhs(self.N2, self.b_base, self.x_base, db, dx, out)
         self.Kh.mul(db, out, alpha=-self.c, beta=-1.0)
-        self.Kv.mul(db, out, alpha=-self.c, beta=1.0)
+        self._vertical_diffusion(db, out)
         self.n_applies += 1
         return out
 
@@ -192,7 +313,9 @@ class LinearizedModel:
         if not (P is None or isinstance(P, (Diagonal, LU, DenseInversePreconditioner))):
             raise NotImplementedError(f"LinearizedModel: the adjoint supports the inversion preconditioners Diagonal, LU and "
                                       f"DenseInversePreconditioner, not {type(P).__name__}: a transposed V-cycle is a follow-up")
-        if getattr(ms.A, "paired", False):
+        if self._A_plain is not None:
+            A_csr = self._A_plain.to_scipy_csr()            # closures="tangent" with the eddy closure: the own A(nu(b_base))
+        elif getattr(ms.A, "paired", False):
             # node records are an HBM layout that does not download as CSR: the same entries assembled once more into a plain
             # pattern, by the routine and the engine that assembled them (constant nu, Laplacian form: what InversionToolkit asks
             # of a matrix before it calls block_nodes), from the engine's tables as they stand
@@ -218,7 +341,7 @@ class LinearizedModel:
         kw = dict(self.inv_solver.kwargs)
         solver = IterativeSolverToolkit(A_T, P_T, DeviceVector(self.ctx, self.n_inv), ws, kw, "Linearised adjoint inversion")
         self.adj_solver, self.B_T = solver, B_T
-        self._adj = dict(gx=DeviceVector(self.ctx, self.n_inv), gb=DeviceVector(self.ctx, self.nb))
+        self._adj = dict(gx=DeviceVector(self.ctx, self.n_inv), gb=DeviceVector(self.ctx, self.nb), ge=DeviceVector(self.ctx, self.nb))
         return self._adj
 
     def invert_adjoint(self, g_x: DeviceVector, out: DeviceVector = None):
@@ -237,6 +360,9 @@ class LinearizedModel:
         self.n_inversions += 1
         self.n_adjoint_inversions += 1
         self.B_T.mul(s.x, out, alpha=1.0, beta=0.0)
+        if self._eddy is not None:  # + g(y): the adjoint of db -> r_x(db)
+            self.fe.tangent_eddy_adjoint(*self._eddy_args(), self.b_base, self.x_base, s.x, adj["ge"], **self._eddy_kw())
+            out.axpby(1.0, adj["ge"], 1.0)
         return out
 
     def apply_adjoint(self, lam: DeviceVector, out: DeviceVector = None):
@@ -248,7 +374,7 @@ class LinearizedModel:
         adj = self._adjoint()
         self.fe.tangent_adjoint(self.N2, self.b_base, self.x_base, lam, out, adj["gx"])
         self.Kh.mul(lam, out, alpha=-self.c, beta=-1.0)
-        self.Kv.mul(lam, out, alpha=-self.c, beta=1.0)
+        self._vertical_diffusion(lam, out)            # D_v is symmetric: its own adjoint
         out.axpby(-1.0, self.invert_adjoint(adj["gx"]), 1.0)
         self.n_adjoint_applies += 1
         return out
